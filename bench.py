@@ -20,6 +20,13 @@
   independent-blocks mode, sharded by contiguous block ranges across the ranks.  A step = device compress of the rank's
   blocks -> size table + payload all-gather over torch.distributed (RCCL) -> the frame assembled in HBM on every rank, all
   inside the timed region ("strong": total work fixed).  The frame is checked against the oracle's frame on a prefix.
+
+A plain run sets up, warms up, times the --steps steps and prints the line (metric, value, unit, ms_per_step, the roofline of the
+timed call).  --full adds everything else the line can hold, each measured in runs of its own: the compress timing (`compress`),
+the round-trip and oracle checks, the batch-size sweep and tile20, the CPU baseline, the host-buffer end to end, the config4 /
+config5 legs of the silesia line, the compress and U16Table legs of config5 (the --no-* options switch single legs of --full off).
+--dump-outputs DIR writes what the timed path returned in its last step as DIR/<name>.npy (float32 / float64): a fixed, seeded
+sample of 256-byte windows of its output bytes, per-block byte sums where the output is made of blocks, and the per-job results.
 """
 import argparse
 import ctypes as C
@@ -201,6 +208,31 @@ def issue_ceiling(copies, kernel_ms, achieved_gbs, cus=256, which="decompress"):
             "ceiling_gbs": round(ceil_gbs, 1), "ceiling_frac_of_hbm": round(ceil_gbs / HBM_PEAK_GBS, 4), "achieved_frac_of_ceiling": round(rate / best_rate, 3)}
 
 
+DUMP_WINDOW = 256                 # --dump-outputs: bytes per sampled window
+DUMP_WINDOWS = 16384              # 4 MiB of output bytes per sampled buffer (16 MiB as float32)
+
+
+def dump_outputs(out_dir, torch, samples=(), whole=()):
+    """--dump-outputs: `samples` = (name, uint8 device tensor): DUMP_WINDOWS windows of DUMP_WINDOW bytes at seeded offsets (the same
+    offsets for the same buffer size), as float32; `whole` = (name, array): written whole as float64."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in samples:
+        n = t.numel()
+        starts = np.sort(np.random.default_rng(0x5EEDD0).integers(0, max(1, n - DUMP_WINDOW + 1), DUMP_WINDOWS))
+        idx = torch.from_numpy(starts).to(t.device)[:, None] + torch.arange(min(DUMP_WINDOW, n), device=t.device)
+        np.save(os.path.join(out_dir, name + ".npy"), t[idx.view(-1)].cpu().numpy().astype(np.float32))
+    for name, a in whole:
+        a = a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64))
+    log(f"[bench] outputs written to {out_dir}: {', '.join(n for n, _ in list(samples) + list(whole))}")
+
+
+def block_sums(torch, buf, nblk, bs):
+    """Byte sum of every bs-byte block of the uint8 device tensor buf (int64, on the device; 16 blocks at a time)."""
+    b2 = buf[: nblk * bs].view(nblk, bs)
+    return torch.cat([b2[i:i + 16].sum(dim=1, dtype=torch.int64) for i in range(0, nblk, 16)])
+
+
 def timed_launches(torch, fn, steps):
     """Run fn() `steps` times; HIP events on the launch stream bracket each call."""
     evs = []
@@ -250,13 +282,18 @@ def main():
     ap.add_argument("--copies", type=int, default=240, help="silesia: tiled copies of silesia_mix per GPU (51 blocks each)")
     ap.add_argument("--distinct", type=int, default=12, help="silesia: copies generated with their own seeds (the rest are rotated + XOR-ed)")
     ap.add_argument("--blocks", type=int, default=2048, help="config4: 4 MiB blocks of the whole stream (2048 = 8 GiB)")
-    ap.add_argument("--cpu-seconds", type=float, default=25.0, help="budget of the CPU-baseline leg (rank 0, N=1)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true")
-    ap.add_argument("--no-verify", action="store_true")
-    ap.add_argument("--no-config4", action="store_true", help="silesia workload: skip the strong-scaled configs[3] leg of the line")
-    ap.add_argument("--no-config5", action="store_true", help="silesia workload: skip the configs[4] leg of the line (linked 64 KiB blocks + dictionary, U16Table)")
-    ap.add_argument("--no-sweep", action="store_true", help="silesia workload: skip the batch-size sweep and the tile20 leg (PMC passes: the headline call's kernels only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other measurement and check of the line, each in runs of its own (compress timing, verification, "
+                         "batch sweep, CPU baseline, end to end, config4 / config5 legs); a plain run does only the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (seeded sample of the output bytes, per-job results)")
+    ap.add_argument("--cpu-seconds", type=float, default=25.0, help="budget of the CPU-baseline leg (rank 0, N=1; --full)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-e2e", action="store_true", help="--full: skip the host-buffer end to end")
+    ap.add_argument("--no-verify", action="store_true", help="--full: skip the round-trip and oracle checks")
+    ap.add_argument("--no-config4", action="store_true", help="silesia workload, --full: skip the strong-scaled configs[3] leg of the line")
+    ap.add_argument("--no-config5", action="store_true", help="silesia workload, --full: skip the configs[4] leg of the line (linked 64 KiB blocks + dictionary, U16Table)")
+    ap.add_argument("--no-sweep", action="store_true", help="silesia workload, --full: skip the batch-size sweep and the tile20 leg (PMC passes: the headline call's kernels only)")
     ap.add_argument("--streams", type=int, default=4096, help="config5: linked-block streams of 1 MiB per GPU")
     ap.add_argument("--launch-check", action="store_true",
                     help="no GPU work: every rank joins a gloo group, the ranks agree on their block ranges, rank 0 prints them (test of the self-launch path)")
@@ -334,14 +371,14 @@ def main():
                     out = {"error": f"{name}: the ranks could not agree on the outcome: {e}"}
             wd.cancel()
             return out
-        if not args.no_config4:
+        if args.full and not args.no_config4:
             # the one workload with a real exchange (BASELINE configs[3]), strong-scaled, as a leg of the same line: a driver
             # run at N GPUs records the weak-scaled Silesia value and this
             import copy, gc
 
             def c4():
                 gc.collect(); torch.cuda.empty_cache()
-                a4 = copy.copy(args); a4.steps = max(1, min(args.steps, 3)); a4.warmup = 1; a4.no_cpu = True
+                a4 = copy.copy(args); a4.steps = max(1, min(args.steps, 3)); a4.warmup = 1; a4.no_cpu = True; a4.dump_outputs = None
                 l4 = run_config4(a4, torch, device, ffi, dist, rank, world, dev)
                 if rank != 0:
                     return None
@@ -356,13 +393,13 @@ def main():
             r4 = leg("config4", c4)
             if rank == 0:
                 line["config4"] = r4
-        if not args.no_config5 and world == 1:
+        if args.full and not args.no_config5 and world == 1:
             # configs[4]: linked 64 KiB blocks behind a dictionary (many streams in lock-step) and raw U16Table jobs, device-resident
             import copy, gc
 
             def c5():
                 gc.collect(); torch.cuda.empty_cache()
-                a5 = copy.copy(args); a5.steps = max(1, min(args.steps, 3)); a5.warmup = 1
+                a5 = copy.copy(args); a5.steps = max(1, min(args.steps, 3)); a5.warmup = 1; a5.dump_outputs = None
                 l5 = run_config5(a5, torch, device, ffi, dist, rank, world, dev)
                 return {k: l5[k] for k in ("value", "unit", "steps", "ms_per_step", "config", "roofline", "compress", "u16_raw")} if rank == 0 else None
             r5 = leg("config5", c5)
@@ -416,30 +453,33 @@ def run_silesia(args, torch, device, ffi, dist, rank, world, dev, bases):
         device.compress_batch(d_cj, d_cres, nblk, ffi.KINDS_U32 | ffi.KINDS_U32_FRESH_ONLY)
 
     c_steps = max(1, min(args.steps, 3))
-    compress_step()
+    compress_step()                                                    # the compressed blocks the timed decompress steps read
     torch.cuda.synchronize()
-    if dist:
-        dist.barrier()
-    torch.cuda.synchronize()
-    tc0 = time.perf_counter()
-    c_evs = timed_launches(torch, compress_step, c_steps)
-    c_launch = ffi.lib().lzf_last_compress_launch().decode()
-    torch.cuda.synchronize()
-    if dist:
-        dist.barrier()
-    torch.cuda.synchronize()
-    tc = time.perf_counter() - tc0
+    tc = 0.0
+    if args.full:                                                      # the compress timing (configs[2]) of the line
+        if dist:
+            dist.barrier()
+        torch.cuda.synchronize()
+        tc0 = time.perf_counter()
+        c_evs = timed_launches(torch, compress_step, c_steps)
+        c_launch = ffi.lib().lzf_last_compress_launch().decode()
+        torch.cuda.synchronize()
+        if dist:
+            dist.barrier()
+        torch.cuda.synchronize()
+        tc = time.perf_counter() - tc0
     cres = device.results_to_host(d_cres, nblk)
     ok = cres["status"] == ffi.OK
     full = cres["status"] == ffi.OUTPUT_FULL
     assert np.all(ok | full), f"compress statuses: {np.unique(cres['status'])}"
     clen = np.where(ok, cres["out_len"], 0).astype(np.uint64)
-    c_kernel_ms = float(np.mean([a.elapsed_time(b) for a, b in c_evs]))
-    # how evenly the launch fills the chip: the jobs' own wave times (results[].reserved, kilo-cycles) against slots x duration
-    c_kc = cres["reserved"].astype(np.float64) * 1024.0
-    c_fill = {"sum_of_wave_gcycles": round(float(c_kc.sum()) / 1e9, 2), "longest_job_mcycles": round(float(c_kc.max()) / 1e6, 1),
-              "mean_job_mcycles": round(float(c_kc.mean()) / 1e6, 1)}
-    c_bytes = float(lens.sum() + clen.sum())                           # N + C
+    if args.full:
+        c_kernel_ms = float(np.mean([a.elapsed_time(b) for a, b in c_evs]))
+        # how evenly the launch fills the chip: the jobs' own wave times (results[].reserved, kilo-cycles) against slots x duration
+        c_kc = cres["reserved"].astype(np.float64) * 1024.0
+        c_fill = {"sum_of_wave_gcycles": round(float(c_kc.sum()) / 1e9, 2), "longest_job_mcycles": round(float(c_kc.max()) / 1e6, 1),
+                  "mean_job_mcycles": round(float(c_kc.mean()) / 1e6, 1)}
+        c_bytes = float(lens.sum() + clen.sum())                       # N + C
 
     # stored blocks (incompressible, framed/compress.rs:250-255): the frame carries the raw bytes
     stored_idx = np.nonzero(full)[0]
@@ -503,7 +543,12 @@ def run_silesia(args, torch, device, ffi, dist, rank, world, dev, bases):
     dres = device.results_to_host(d_dres, nk)
     assert np.all(dres["status"] == ffi.OK), f"decompress statuses: {np.unique(dres['status'])}"
     assert np.array_equal(dres["out_len"], lens[kidx])
-    if not args.no_verify:
+    if args.dump_outputs and rank == 0:
+        # what the callers of the step receive: the decoded blocks (stored ones included) and the kernel's per-job results
+        dump_outputs(args.dump_outputs, torch, samples=[("decompressed_sample", dec)],
+                     whole=[("decompressed_block_sums", block_sums(torch, dec, nblk, BS)),
+                            ("decompress_status", dres["status"]), ("decompress_out_len", dres["out_len"])])
+    if args.full and not args.no_verify:
         assert torch.equal(dec, src), "decoded bytes differ from the source"   # round trip at full size
 
     t = torch.tensor([elapsed, tc], dtype=torch.float64, device=dev)
@@ -517,13 +562,14 @@ def run_silesia(args, torch, device, ffi, dist, rank, world, dev, bases):
     d_bytes = float(lens[kidx].sum() + clen[kidx].sum())               # C + N of the kernel's jobs
     kname = kname_main
     d_traffic, d_traffic_info = traffic_for(kname, "decompress", nk)
-    c_traffic, c_traffic_info = traffic_for(c_launch, "compress", nblk)
     d_achieved = d_bytes / (d_kernel_ms * 1e-3) / 1e9
-    c_achieved = c_bytes / (c_kernel_ms * 1e-3) / 1e9
+    if args.full:
+        c_traffic, c_traffic_info = traffic_for(c_launch, "compress", nblk)
+        c_achieved = c_bytes / (c_kernel_ms * 1e-3) / 1e9
 
     # ------------------------------------------------------------------ batch-size sweep of the same call (this rank's first copies)
     sweep = tile20 = None
-    if rank == 0 and not args.no_sweep:
+    if args.full and rank == 0 and not args.no_sweep:
         sweep = {}
         per_copy = max(1, nk // copies)
         for c_n in (1, 4, 20):
@@ -558,7 +604,7 @@ def run_silesia(args, torch, device, ffi, dist, rank, world, dev, bases):
 
     # ------------------------------------------------------------------ CPU baseline + host-buffer end to end (rank 0, N = 1)
     cpu = e2e = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         first = [i for i in range(nb1) if ok[i]]
         raw_blocks = [bases[0][i * BS:i * BS + int(lens[i])] for i in first]
         # (the host-buffer legs first: with the CPU baseline or even just its input copies in front of them, the same calls
@@ -573,6 +619,16 @@ def run_silesia(args, torch, device, ffi, dist, rank, world, dev, bases):
     if rank != 0:
         return None
     value = total_bytes * args.steps / elapsed_max / 2**30
+    compress = None
+    if args.full:
+        compress = {"value": round(total_bytes * c_steps / tc_max / 2**30, 3), "unit": "GiB/s (uncompressed bytes compressed per second)",
+                    "steps": c_steps, "ms_per_step": round(tc_max / c_steps * 1e3, 3),
+                    "roofline": {"bound": "hbm", "kernel": c_launch,
+                                 "achieved": round(c_achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                 "frac": round(c_achieved / HBM_PEAK_GBS, 5), "traffic": c_traffic, "traffic_provenance": c_traffic_info,
+                                 "algorithmic_bytes_per_launch": c_bytes, "kernel_ms": round(c_kernel_ms, 3),
+                                 "issue_ceiling": issue_ceiling(copies, c_kernel_ms, c_achieved, which="compress")},
+                    "launch_fill": c_fill}
     return {
         "metric": METRIC,
         "value": round(value, 3), "unit": "GiB/s (uncompressed bytes decompressed per second)",
@@ -598,14 +654,7 @@ def run_silesia(args, torch, device, ffi, dist, rank, world, dev, bases):
                      # (profiles/r02_decompress_generations.txt: 9.0 SALU + 16.1 VALU + 2.6 LDS + 0.24 VMEM per sequence; 11.71 M sequences
                      # per corpus copy) against the issue rate a dependent SALU + VALU mix reaches (profiles/r01_issue_mix_microbench.txt)
                      "issue_ceiling": issue_ceiling(copies, d_kernel_ms, d_achieved)},
-        "compress": {"value": round(total_bytes * c_steps / tc_max / 2**30, 3), "unit": "GiB/s (uncompressed bytes compressed per second)",
-                     "steps": c_steps, "ms_per_step": round(tc_max / c_steps * 1e3, 3),
-                     "roofline": {"bound": "hbm", "kernel": c_launch,
-                                  "achieved": round(c_achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                  "frac": round(c_achieved / HBM_PEAK_GBS, 5), "traffic": c_traffic, "traffic_provenance": c_traffic_info,
-                                  "algorithmic_bytes_per_launch": c_bytes, "kernel_ms": round(c_kernel_ms, 3),
-                                  "issue_ceiling": issue_ceiling(copies, c_kernel_ms, c_achieved, which="compress")},
-                     "launch_fill": c_fill},
+        "compress": compress,                                          # (--full)
         # the same call at smaller batch sizes (compressed blocks of the first 1 / 4 / 20 copies; kernel time by HIP events,
         # median of 5): up to 1024 blocks go through the segmented pipeline, a block decoded by many wavefronts
         "batch_sweep": sweep,
@@ -803,17 +852,23 @@ def run_config4(args, torch, device, ffi, dist, rank, world, dev):
     elapsed_max = float(t[0])
     k_ms = sum(a.elapsed_time(b) for a, b in kev) / max(len(kev), 1)      # the compress call of this rank (cost probe + kernel), HIP events
     g_ms = sum(a.elapsed_time(b) for a, b in gev) / max(len(gev), 1)      # size-table all-gather + packing + segment exchange + header / EndMark
+    if args.dump_outputs and rank == 0:
+        # what the step hands back: the frame assembled in HBM (every rank holds it whole) and this rank's compress results
+        fl = int(state["frame_len"])
+        r4 = device.results_to_host(d_cres, nloc)
+        dump_outputs(args.dump_outputs, torch, samples=[("frame_sample", frame[:fl])],
+                     whole=[("frame_len", [fl]), ("compress_status", r4["status"]), ("compress_out_len", r4["out_len"])])
     # what the reference's default (content_checksum: true) would add: XXH32 does not compose across ranks, so it is one serial
     # chain over the whole stream on one host thread — timed here on a 256 MiB sample, outside the timed region
     xx = None
-    if rank == 0:
+    if args.full and rank == 0:
         sample = src[: min(src.numel(), 256 << 20)].cpu().numpy().tobytes()
         tx = time.perf_counter(); ffi.lib().lzf_xxh32(sample, len(sample), 0); tx = time.perf_counter() - tx
         xx = {"in_timed_region": False, "host_xxh32_gb_per_s": round(len(sample) / tx / 1e9, 2),
               "serial_ms_for_the_stream": round(float(nblk_all) * BS / (len(sample) / tx) * 1e3, 1)}
     # ---- check: the frame's head == the oracle's frame of the same first blocks (rank 0 holds them)
     verified = None
-    if rank == 0 and not args.no_verify:
+    if args.full and rank == 0 and not args.no_verify:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_ffi as o
         k = min(3, nloc)
@@ -835,7 +890,7 @@ def run_config4(args, torch, device, ffi, dist, rank, world, dev):
     alg = float(nloc) * BS + state["comp_total"] * nloc / max(nblk_all, 1)
     achieved = alg / (k_ms * 1e-3) / 1e9
     cpu = None
-    if world == 1 and not args.no_cpu:
+    if args.full and world == 1 and not args.no_cpu:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         n_s = min(nloc, 16)
         raw_blocks = [src[i * BS:(i + 1) * BS].cpu().numpy() for i in range(n_s)]
@@ -938,8 +993,11 @@ def run_config5(args, torch, device, ffi, dist, rank, world, dev):
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t[0]), float(np.mean([a.elapsed_time(b) for a, b in evs]))
 
-    c_el, c_ms = timed(compress_step, args.steps, args.warmup)
-    c_launch = lib.lzf_last_compress_launch().decode()
+    if args.full:
+        c_el, c_ms = timed(compress_step, args.steps, args.warmup)
+        c_launch = lib.lzf_last_compress_launch().decode()
+    else:
+        compress_step()                                                            # the linked blocks the timed decompress steps read
     cres = device.results_to_host(d_cres, nj)
     assert np.all(cres["status"] == ffi.OK), f"config5 compress statuses: {np.unique(cres['status'])}"
     clen = cres["out_len"].astype(np.uint64)
@@ -979,10 +1037,15 @@ def run_config5(args, torch, device, ffi, dist, rank, world, dev):
     d_launch = lib.lzf_last_decompress_launch().decode()
     dres = device.results_to_host(d_dres, nj)
     assert np.all(dres["status"] == ffi.OK), f"config5 decompress statuses: {np.unique(dres['status'])}"
-    if not args.no_verify:
+    if args.dump_outputs and rank == 0:
+        # what the step hands back: every stream's decoded bytes and the per-block results
+        dump_outputs(args.dump_outputs, torch, samples=[("decompressed_sample", dec)],
+                     whole=[("decompressed_stream_sums", block_sums(torch, dec, S, dstride)),
+                            ("decompress_status", dres["status"]), ("decompress_out_len", dres["out_len"])])
+    if args.full and not args.no_verify:
         assert torch.equal(dec.view(S, dstride)[:, :SL], slab.view(S, stride)[:, DL:]), "config5: decoded streams differ from the source"
     verified = None
-    if rank == 0 and not args.no_verify:
+    if args.full and rank == 0 and not args.no_verify:
         # the first and the last stream against the oracle's linked-block loop (framed/compress.rs:221-276), block by block
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import ctypes as C
@@ -1012,36 +1075,38 @@ def run_config5(args, torch, device, ffi, dist, rank, world, dev):
                     buf = buf[forget:]
         verified = True
 
-    # ---- raw U16Table jobs (mod.rs:78-101): 65 535-byte slices, fresh tables; and back
-    NU = min(4 * S, (S * stride) // 65536)
-    uj = np.zeros(NU, dtype=device.CJOB)
-    uoff = np.arange(NU, dtype=np.uint64) * np.uint64(65536)
-    uj["input"] = np.uint64(slab.data_ptr()) + uoff
-    uj["input_len"] = 65535
-    uj["out"] = np.uint64(comp.data_ptr()) + uoff
-    uj["out_cap"] = 65535
-    uj["table_kind"] = ffi.TABLE_U16
-    d_uj = device.to_device(uj, dev)
-    d_ures = torch.zeros(NU * 16, dtype=torch.uint8, device=dev)
-    u_el, u_ms = timed(lambda: ffi.check(lib.lzf_compress_batch(d_uj.data_ptr(), d_ures.data_ptr(), NU, ffi.KINDS_U16, st)), args.steps, args.warmup)
-    ures = device.results_to_host(d_ures, NU)
-    assert np.all(ures["status"] == ffi.OK)
-    ud = np.zeros(NU, dtype=device.DJOB)
-    ud["input"] = uj["out"]; ud["input_len"] = ures["out_len"]
-    ud["out"] = np.uint64(dec.data_ptr()) + uoff; ud["out_cap"] = 65535 + 64; ud["output_limit"] = 65535
-    d_ud = device.to_device(ud, dev)
-    d_udres = torch.zeros(NU * 16, dtype=torch.uint8, device=dev)
-    dec.zero_()
-    ud_el, ud_ms = timed(lambda: ffi.check(lib.lzf_decompress_batch_sized(d_ud.data_ptr(), d_udres.data_ptr(), NU, 65536, st)), args.steps, args.warmup)
-    udres = device.results_to_host(d_udres, NU)
-    assert np.all(udres["status"] == ffi.OK) and np.all(udres["out_len"] == 65535)
-    if not args.no_verify:
-        assert torch.equal(dec[: NU * 65536].view(NU, 65536)[:, :65535], slab[: NU * 65536].view(NU, 65536)[:, :65535]), "config5: U16 round trip differs"
-    if rank == 0 and not args.no_verify:
-        import oracle_ffi as o
-        h = slab[:65535].cpu().numpy().tobytes()
-        erc, ecomp = o.compress2(h, kind=o.TABLE_U16)
-        assert erc == 0 and comp[: int(ures["out_len"][0])].cpu().numpy().tobytes() == ecomp, "config5: U16Table job differs from the oracle"
+    # ---- raw U16Table jobs (mod.rs:78-101): 65 535-byte slices, fresh tables; and back (--full)
+    if args.full:
+        NU = min(4 * S, (S * stride) // 65536)
+        uj = np.zeros(NU, dtype=device.CJOB)
+        uoff = np.arange(NU, dtype=np.uint64) * np.uint64(65536)
+        uj["input"] = np.uint64(slab.data_ptr()) + uoff
+        uj["input_len"] = 65535
+        uj["out"] = np.uint64(comp.data_ptr()) + uoff
+        uj["out_cap"] = 65535
+        uj["table_kind"] = ffi.TABLE_U16
+        d_uj = device.to_device(uj, dev)
+        d_ures = torch.zeros(NU * 16, dtype=torch.uint8, device=dev)
+        u_el, u_ms = timed(lambda: ffi.check(lib.lzf_compress_batch(d_uj.data_ptr(), d_ures.data_ptr(), NU, ffi.KINDS_U16, st)), args.steps, args.warmup)
+        ures = device.results_to_host(d_ures, NU)
+        assert np.all(ures["status"] == ffi.OK)
+        ud = np.zeros(NU, dtype=device.DJOB)
+        ud["input"] = uj["out"]; ud["input_len"] = ures["out_len"]
+        ud["out"] = np.uint64(dec.data_ptr()) + uoff; ud["out_cap"] = 65535 + 64; ud["output_limit"] = 65535
+        d_ud = device.to_device(ud, dev)
+        d_udres = torch.zeros(NU * 16, dtype=torch.uint8, device=dev)
+        dec.zero_()
+        ud_el, ud_ms = timed(lambda: ffi.check(lib.lzf_decompress_batch_sized(d_ud.data_ptr(), d_udres.data_ptr(), NU, 65536, st)), args.steps, args.warmup)
+        udres = device.results_to_host(d_udres, NU)
+        assert np.all(udres["status"] == ffi.OK) and np.all(udres["out_len"] == 65535)
+        if not args.no_verify:
+            assert torch.equal(dec[: NU * 65536].view(NU, 65536)[:, :65535], slab[: NU * 65536].view(NU, 65536)[:, :65535]), "config5: U16 round trip differs"
+        if rank == 0 and not args.no_verify:
+            import oracle_ffi as o
+            h = slab[:65535].cpu().numpy().tobytes()
+            erc, ecomp = o.compress2(h, kind=o.TABLE_U16)
+            assert erc == 0 and comp[: int(ures["out_len"][0])].cpu().numpy().tobytes() == ecomp, "config5: U16Table job differs from the oracle"
+        ud_launch = lib.lzf_last_decompress_launch().decode()
     if rank != 0:
         return None
     tot = float(S) * SL * world
@@ -1051,7 +1116,15 @@ def run_config5(args, torch, device, ffi, dist, rank, world, dev):
                                   "frac": round(alg / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5), "traffic": None, "algorithmic_bytes_per_launch": alg, "kernel_ms": round(ms, 3),
                                   "launches_per_step": None}
     r_d = roof(N1 + C1, d_ms, d_launch); r_d["launches_per_step"] = f"{NB} x (lzf_chain_decompress_step + lzf_decompress_batch of {S} jobs)"
-    r_c = roof(N1 + C1, c_ms, c_launch); r_c["launches_per_step"] = f"table clone + {NB} x (lzf_table_offset_batch + lzf_compress_batch of {S} jobs)"
+    compress = u16_raw = None                                                     # (--full)
+    if args.full:
+        r_c = roof(N1 + C1, c_ms, c_launch); r_c["launches_per_step"] = f"table clone + {NB} x (lzf_table_offset_batch + lzf_compress_batch of {S} jobs)"
+        compress = {"value": gib(tot * args.steps, c_el), "unit": "GiB/s (uncompressed bytes compressed per second)", "ms_per_step": round(c_el / args.steps * 1e3, 3), "roofline": r_c}
+        u16_raw = {"jobs": int(NU), "slice_bytes": 65535,
+                   "compress": {"value": gib(float(NU) * 65535 * world * args.steps, u_el), "unit": "GiB/s", "ms_per_step": round(u_el / args.steps * 1e3, 3),
+                                "roofline": roof(float(NU) * 65535 + float(ures["out_len"].sum()), u_ms, "lzf_compress_wave_kernel<U16>")},
+                   "decompress": {"value": gib(float(NU) * 65535 * world * args.steps, ud_el), "unit": "GiB/s", "ms_per_step": round(ud_el / args.steps * 1e3, 3),
+                                  "roofline": roof(float(NU) * 65535 + float(ures["out_len"].sum()), ud_ms, ud_launch)}}
     return {
         "metric": METRIC, "value": gib(tot * args.steps, d_el), "unit": "GiB/s (uncompressed bytes decompressed per second; linked 64 KiB blocks behind a dictionary)",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(d_el / args.steps * 1e3, 3),
@@ -1062,12 +1135,8 @@ def run_config5(args, torch, device, ffi, dist, rank, world, dev):
                    "streams_per_gpu": S, "block_size": B5, "blocks_per_stream": NB, "dictionary_bytes": DL, "template_seed_ms_untimed": round(seed_ms, 1),
                    "verified_against_oracle": verified, "parallelism": f"streams x{world}, no collective (linked streams do not shard: replicas only)"},
         "roofline": r_d,
-        "compress": {"value": gib(tot * args.steps, c_el), "unit": "GiB/s (uncompressed bytes compressed per second)", "ms_per_step": round(c_el / args.steps * 1e3, 3), "roofline": r_c},
-        "u16_raw": {"jobs": int(NU), "slice_bytes": 65535,
-                    "compress": {"value": gib(float(NU) * 65535 * world * args.steps, u_el), "unit": "GiB/s", "ms_per_step": round(u_el / args.steps * 1e3, 3),
-                                 "roofline": roof(float(NU) * 65535 + float(ures["out_len"].sum()), u_ms, "lzf_compress_wave_kernel<U16>")},
-                    "decompress": {"value": gib(float(NU) * 65535 * world * args.steps, ud_el), "unit": "GiB/s", "ms_per_step": round(ud_el / args.steps * 1e3, 3),
-                                   "roofline": roof(float(NU) * 65535 + float(ures["out_len"].sum()), ud_ms, lib.lzf_last_decompress_launch().decode())}},
+        "compress": compress,
+        "u16_raw": u16_raw,
     }
 
 

@@ -3,7 +3,7 @@
 mkdir -p gpurun_out/r05; L=gpurun_out/r05/bench_compress_ab.log; rm -f $L
 for lib in "$@"; do
   echo "== $lib" >> $L
-  LZF_LIB_PATH=$lib timeout 900 python bench.py --no-cpu --no-e2e --no-config4 --no-config5 --steps 2 --warmup 1 2>/dev/null | python -c "
+  LZF_LIB_PATH=$lib timeout 900 python bench.py --full --no-cpu --no-e2e --no-config4 --no-config5 --steps 2 --warmup 1 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.readline())
 c = d['compress']

@@ -1,7 +1,7 @@
 #!/bin/bash
 # kernels of the last 980-block call of bench.py's batch_sweep (distinct inputs), start / end in ms from the call's first kernel
 R=${GRAFT_REPO_ROOT:-$PWD}; export TMPDIR=/tmp
-rm -rf /tmp/segb; (cd $R && timeout 900 rocprofv3 --kernel-trace --output-format csv -d /tmp/segb -- python bench.py --no-cpu --no-e2e --no-config4 --no-config5 --no-verify --steps 1 --warmup 0 > /tmp/segb.log 2>&1)
+rm -rf /tmp/segb; (cd $R && timeout 900 rocprofv3 --kernel-trace --output-format csv -d /tmp/segb -- python bench.py --full --no-cpu --no-e2e --no-config4 --no-config5 --no-verify --steps 1 --warmup 0 > /tmp/segb.log 2>&1)
 f=$(ls /tmp/segb/*/*kernel_trace.csv | head -1); python - "$f" "${1:-32768}" <<'PY'
 import csv,sys
 ev=[]

@@ -123,42 +123,62 @@ def test_corpus_frame_uncomp_data():
     assert o.frame_decompress(bytes(bad))[0] == o.F_FRAME_CHECKSUM_FAIL
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/fuzz/corpus/decode"), reason="reference tree not mounted")
+def fuzz_corpus(d):
+    """[(file name, bytes)] of the reference's fuzz/corpus/<d>, in name order, from the packed fixture (tests/golden/make_fixtures.py)."""
+    import gzip
+    index = json.load(open(os.path.join(GOLD, "fuzz_corpus.json")))[d]
+    with gzip.open(os.path.join(GOLD, f"fuzz_{d}.bin.gz"), "rb") as gz:
+        blob = gz.read()
+    out, off = [], 0
+    for name, n in index:
+        out.append((name, blob[off:off + n]))
+        off += n
+    assert off == len(blob), f"fuzz_{d}.bin.gz does not match fuzz_corpus.json"
+    return out
+
+
 def test_decode_corpus_census_matches_fixture():
     """The 1022-file malformed-input corpus: error class per file is pinned by the fixture, the
-    class totals relate to SURVEY.md §4 (see tests/golden/README.md for the 10 reclassified files)."""
-    import collections, glob
+    class totals relate to SURVEY.md §4 (see tests/golden/README.md for the 10 reclassified files).
+    The packed corpus holds 830 of the files: the 192 that carry text of the corpus's two text frames are
+    left out (tests/golden/make_fixtures.py); their classes stay in the fixture's census."""
+    import collections
     J = json.load(open(os.path.join(GOLD, "corpus_frames.json")))
+    left_out = json.load(open(os.path.join(GOLD, "fuzz_corpus.json")))["decode_left_out"]
+    files = fuzz_corpus("decode")
+    assert len(files) == 830 and len(left_out) == 192
+    assert sorted([n for n, _ in files] + left_out) == sorted(J["per_file"])      # together: the whole corpus, once
     census = collections.Counter()
-    for f in sorted(glob.glob("/root/reference/fuzz/corpus/decode/*")):
-        data = open(f, "rb").read()
+    for name, data in files:
         rc, dec, _ = o.frame_decompress(data)
-        assert o.STATUS_NAMES[rc] == J["per_file"][os.path.basename(f)]
+        assert o.STATUS_NAMES[rc] == J["per_file"][name]
         census[o.STATUS_NAMES[rc]] += 1
-        if os.path.basename(f) in J["valid_frames"]:
-            v = J["valid_frames"][os.path.basename(f)]
+        if name in J["valid_frames"]:
+            v = J["valid_frames"][name]
             assert rc == 0 and fp(dec) == [v["out_len"], v["out_xxh32"]]
-    assert dict(census) == J["census"]
-    assert sum(census.values()) == 1022 and census["WrongMagic"] == 661
+    assert dict(census) == {"BlockChecksumFail": 11, "BlockSizeOverflow": 54, "FrameChecksumFail": 3, "HeaderChecksumFail": 3,
+                            "InputError": 78, "InvalidDeduplicationOffset": 13, "Ok": 8, "ReservedBdBitsSet": 1,
+                            "ReservedFlagBitsSet": 1, "UnexpectedEnd": 4, "UnimplementedBlocksize": 2, "UnsupportedVersion": 1,
+                            "WrongMagic": 648, "ZeroDeduplicationOffset": 3}
+    # the whole corpus as the fixture records it
+    whole = collections.Counter(J["per_file"].values())
+    assert dict(whole) == J["census"]
+    assert sum(whole.values()) == 1022 and whole["WrongMagic"] == 661
     # SURVEY.md §4 census, with "a block that decodes to 0 bytes ends read_to_end" applied:
     survey = {"Ok": 4, "WrongMagic": 661, "InputError": 99, "BlockSizeOverflow": 92,
               "InvalidDeduplicationOffset": 85, "UnexpectedEnd": 33, "ZeroDeduplicationOffset": 18,
               "BlockChecksumFail": 12, "FrameChecksumFail": 7, "ReservedFlagBitsSet": 3,
               "HeaderChecksumFail": 3, "UnimplementedBlocksize": 2, "UnsupportedVersion": 1,
               "MemoryLimitExceeded": 1, "ReservedBdBitsSet": 1}
-    diff = {k: census.get(k, 0) - survey[k] for k in survey if census.get(k, 0) != survey[k]}
+    diff = {k: whole.get(k, 0) - survey[k] for k in survey if whole.get(k, 0) != survey[k]}
     assert diff == {"Ok": 10, "InputError": -8, "BlockSizeOverflow": -2}
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/fuzz/corpus"), reason="reference tree not mounted")
 def test_fuzz_plaintext_corpora_roundtrip_and_match_c():
     """interop_decode + roundtrip_fuzz corpora are 501 plaintext inputs (fuzz_targets/*.rs)."""
-    import glob
-    files = sorted(glob.glob("/root/reference/fuzz/corpus/interop_decode/*") +
-                   glob.glob("/root/reference/fuzz/corpus/roundtrip_fuzz/*"))
+    files = fuzz_corpus("interop_decode") + fuzz_corpus("roundtrip_fuzz")
     assert len(files) == 501
-    for f in files:
-        data = open(f, "rb").read()
+    for _, data in files:
         rc, frame = o.frame_compress(data)          # roundtrip_fuzz.rs:10-14
         assert rc == 0
         assert o.frame_decompress(frame)[:2] == (0, data)

@@ -1,16 +1,16 @@
 #!/usr/bin/env python3
-"""Regenerates the round's measurement artifacts on the GPU box (run through gpurun from the repo root), product library only.
+"""Regenerates the round's measurement artifacts on the GPU box (from the repo root), product library only, into the round's
+output folder (O below); every bench.py run here is a --full one, the legs these files hold need it.
 
-    gpurun_out/<round>/bench_default.json        python bench.py (the driver's default invocation)
-    gpurun_out/<round>/kernel_stats.txt          rocprofv3 --kernel-trace --stats of the same command (profiles/summarize_rocpd.py)
-    gpurun_out/<round>/pmc_<size>_<pass>.txt     separate --pmc passes (FETCH_SIZE | WRITE_SIZE | the SQ instruction counters), each
-                                                 with --kernel-trace only, of `bench.py --copies C --distinct 1 --steps 1 --warmup 0
-                                                 --no-sweep ...`: C = 48 (the headline call's kernels: counter collection at 240
-                                                 copies does not finish; bench.py scales by job count) and C = 20 (the tile20 leg:
-                                                 measured at its own size)
-    gpurun_out/<round>/hbm_traffic.json          the FETCH / WRITE passes as the file bench.py's traffic_for() reads
-    gpurun_out/<round>/issue_counters.json       wave-instructions per sequence, the call as a whole and kernel by kernel
-    gpurun_out/<round>/bench_config4.json, bench_config5.json
+    bench_default.json        python bench.py --full (the default workload with every leg of the line)
+    kernel_stats.txt          rocprofv3 --kernel-trace --stats of the same command (profiles/summarize_rocpd.py)
+    pmc_<size>_<pass>.txt     separate --pmc passes (FETCH_SIZE | WRITE_SIZE | the SQ instruction counters), each with
+                              --kernel-trace only, of `bench.py --full --copies C --distinct 1 --steps 1 --warmup 0 --no-sweep ...`:
+                              C = 48 (the headline call's kernels: counter collection at 240 copies does not finish; bench.py
+                              scales by job count) and C = 20 (the tile20 leg: measured at its own size)
+    hbm_traffic.json          the FETCH / WRITE passes as the file bench.py's traffic_for() reads
+    issue_counters.json       wave-instructions per sequence, the call as a whole and kernel by kernel
+    bench_config4.json, bench_config5.json   python bench.py --full --workload config4 | config5
 
 A decompress CALL is several kernels since round 6 (hop parse + seam + bitmap-fed copy stage + the pair kernel over what is left,
 or the segmented pipeline's stages): every counter is summed over all kernels of the call, and listed per kernel beside the sum.
@@ -33,7 +33,7 @@ O = os.path.join(R, "gpurun_out", TAG)
 os.makedirs(O, exist_ok=True)
 ENV = dict(os.environ, TMPDIR="/tmp")
 SEQ_PER_COPY = 11.71e6          # sequences of one copy of the corpus (oracle statistics, tools/seq_stats.c)
-COMMON = ["--no-cpu", "--no-e2e", "--no-config4", "--no-config5"]
+COMMON = ["--full", "--no-cpu", "--no-e2e", "--no-config4", "--no-config5"]
 SQ = ["SQ_INSTS_VALU", "SQ_INSTS_SALU", "SQ_INSTS_LDS", "SQ_INSTS_VMEM_RD", "SQ_INSTS_VMEM_WR", "SQ_WAVE_CYCLES"]
 
 
@@ -89,7 +89,7 @@ def pmc_pass(size, name, counters, timeout=600):
 
 def main():
     if not QUICK:
-        sh(["python", "bench.py"], os.path.join(O, "bench_default.log"), 1500)
+        sh(["python", "bench.py", "--full"], os.path.join(O, "bench_default.log"), 1500)
         l = json_line(os.path.join(O, "bench_default.log"))
         if l:
             json.dump(l, open(os.path.join(O, "bench_default.json"), "w"))
@@ -181,7 +181,7 @@ def main():
 
     if not QUICK:
         for w in ("config4", "config5"):
-            sh(["python", "bench.py", "--workload", w], os.path.join(O, f"bench_{w}.log"), 900)
+            sh(["python", "bench.py", "--full", "--workload", w], os.path.join(O, f"bench_{w}.log"), 900)
             l = json_line(os.path.join(O, f"bench_{w}.log"))
             if l:
                 json.dump(l, open(os.path.join(O, f"bench_{w}.json"), "w"))

@@ -1,22 +1,23 @@
 #!/bin/bash
-# Regenerates the round's measurement artifacts on the GPU box (run through gpurun from the repo root), product library only:
-#   gpurun_out/r06/bench_default.json          python bench.py (the driver's default invocation)
-#   gpurun_out/r06/kernel_stats.txt            rocprofv3 --kernel-trace --stats of the same command
-#   gpurun_out/r06/pmc_{FETCH,WRITE}_SIZE.txt  separate --pmc passes at 48 copies (1 step; 2352 compressed blocks: the same kernels
-#                                               as the default run — counter collection at 240 copies does not finish) for HBM traffic
-#   gpurun_out/r06/hbm_traffic.json            the two passes as the file bench.py reads (copy to profiles/r06_hbm_traffic.json)
-#   gpurun_out/r06/bench_config4.json          python bench.py --workload config4
-#   gpurun_out/r06/issue_counters.json         SQ instruction counters of both headline kernels per sequence (copy to profiles/r06_issue_counters.json)
-#   gpurun_out/r06/bench_config5.json          python bench.py --workload config5
+# Regenerates the round's measurement artifacts on the GPU box (from the repo root), product library only, into $O below; every
+# bench.py run here is a --full one, the legs these files hold need it:
+#   bench_default.json            python bench.py --full (the default workload with every leg of the line)
+#   kernel_stats.txt              rocprofv3 --kernel-trace --stats of the same command
+#   pmc_{FETCH,WRITE}_SIZE.txt    separate --pmc passes at 48 copies (1 step; 2352 compressed blocks: the same kernels
+#                                 as the default run — counter collection at 240 copies does not finish) for HBM traffic
+#   hbm_traffic.json              the two passes as the file bench.py reads (copy to profiles/r06_hbm_traffic.json)
+#   bench_config4.json            python bench.py --full --workload config4
+#   issue_counters.json           SQ instruction counters of both headline kernels per sequence (copy to profiles/r06_issue_counters.json)
+#   bench_config5.json            python bench.py --full --workload config5
 set -u
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r06; rm -rf $O; mkdir -p $O
-cd $R && timeout 1500 python bench.py > $O/bench_default.log 2>&1; grep '^{"metric"' $O/bench_default.log | tail -1 > $O/bench_default.json
+cd $R && timeout 1500 python bench.py --full > $O/bench_default.log 2>&1; grep '^{"metric"' $O/bench_default.log | tail -1 > $O/bench_default.json
 cd /tmp; export TMPDIR=/tmp
-(cd $R && timeout 1500 rocprofv3 --kernel-trace --stats -d $O/prof -o x -- python bench.py --no-cpu --no-e2e --no-config4 --no-config5 > $O/prof.log 2>&1)
+(cd $R && timeout 1500 rocprofv3 --kernel-trace --stats -d $O/prof -o x -- python bench.py --full --no-cpu --no-e2e --no-config4 --no-config5 > $O/prof.log 2>&1)
 DB=$(ls $O/prof/*/x_results.db $O/prof/x_results.db 2>/dev/null | head -1)
 [ -n "$DB" ] && python $R/profiles/summarize_rocpd.py $DB > $O/kernel_stats.txt
 for c in FETCH_SIZE WRITE_SIZE; do
-  (cd $R && timeout 420 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc_$c -- python bench.py --copies 48 --distinct 1 --steps 1 --warmup 0 --no-cpu --no-e2e --no-verify --no-config4 --no-config5 > $O/pmc_$c.log 2>&1)
+  (cd $R && timeout 420 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc_$c -- python bench.py --full --copies 48 --distinct 1 --steps 1 --warmup 0 --no-cpu --no-e2e --no-verify --no-config4 --no-config5 > $O/pmc_$c.log 2>&1)
   rm -rf $O/pmc_$c/*/*.db
   f=$(ls $O/pmc_$c/*/*_counter_collection.csv 2>/dev/null | head -1)
   [ -n "$f" ] && python - "$f" "$c" > $O/pmc_$c.txt <<'PY'
@@ -52,7 +53,7 @@ json.dump(out, open(os.path.join(O, "hbm_traffic.json"), "w"), indent=1)
 print(json.dumps(out, indent=1)[:1500])
 PY
 # ---- instruction counters of the two headline kernels (same 48-copy command): what roofline.issue_ceiling is computed from
-(cd $R && timeout 420 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVE_CYCLES --output-format csv -d $O/pmc_insts -- python bench.py --copies 48 --distinct 1 --steps 1 --warmup 0 --no-cpu --no-e2e --no-verify --no-config4 --no-config5 > $O/pmc_insts.log 2>&1)
+(cd $R && timeout 420 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVE_CYCLES --output-format csv -d $O/pmc_insts -- python bench.py --full --copies 48 --distinct 1 --steps 1 --warmup 0 --no-cpu --no-e2e --no-verify --no-config4 --no-config5 > $O/pmc_insts.log 2>&1)
 rm -rf $O/pmc_insts/*/*.db
 python - $O <<'PY'
 import csv, glob, json, os, sys, collections
@@ -81,6 +82,6 @@ for which, needle in (("decompress", dk), ("compress", "lzf_compress_compact_ker
 json.dump(out, open(os.path.join(O, "issue_counters.json"), "w"), indent=1)
 print(json.dumps({k: v.get("per_sequence") for k, v in out.items() if isinstance(v, dict)}, indent=1))
 PY
-cd $R && timeout 900 python bench.py --workload config4 > $O/bench_config4.log 2>&1; grep '^{"metric"' $O/bench_config4.log | tail -1 > $O/bench_config4.json
-cd $R && timeout 900 python bench.py --workload config5 > $O/bench_config5.log 2>&1; grep '^{"metric"' $O/bench_config5.log | tail -1 > $O/bench_config5.json
+cd $R && timeout 900 python bench.py --full --workload config4 > $O/bench_config4.log 2>&1; grep '^{"metric"' $O/bench_config4.log | tail -1 > $O/bench_config4.json
+cd $R && timeout 900 python bench.py --full --workload config5 > $O/bench_config5.log 2>&1; grep '^{"metric"' $O/bench_config5.log | tail -1 > $O/bench_config5.json
 cut -c1-2500 $O/bench_default.json; head -14 $O/kernel_stats.txt; cat $O/pmc_FETCH_SIZE.txt $O/pmc_WRITE_SIZE.txt; cut -c1-600 $O/bench_config4.json; cut -c1-400 $O/bench_config5.json
