@@ -12,7 +12,7 @@
  * all independent blocks of a frame go to the GPU in ONE batch (lzf_compress_batch /
  * lzf_decompress_batch of lzfear_hip.h); linked-block frames are inherently sequential and run
  * block after block with the table / window carried between calls.
- * Buffers are host memory.  No CPU codec: the calls fail with LZF_E_NO_DEVICE without a GPU.
+ * Buffers are host memory (except for the "frames in device memory" section below).  No CPU codec: the calls fail with LZF_E_NO_DEVICE without a GPU.
  * Checksums: the header checksum (a few bytes) is hashed on the host; block checksums are computed on the device for
  * all blocks of a call in one launch; content checksums on the device for frames up to 32 MiB and on host worker
  * threads, overlapping the kernels, for longer ones (XXH32 is one serial chain per buffer).
@@ -178,6 +178,40 @@ typedef struct lzf_xxh32_state { uint32_t v[4]; uint8_t buf[16]; uint32_t fill; 
 void lzf_xxh32_reset(lzf_xxh32_state* st, uint32_t seed);
 void lzf_xxh32_update(lzf_xxh32_state* st, const uint8_t* p, size_t len);
 uint32_t lzf_xxh32_digest(const lzf_xxh32_state* st);
+
+/* ---- frames in device memory ------------------------------------------------------------------------------------------
+ * lzf_frame_decompress_many for frames that already live on the device (a tensor, shards a loader uploaded compressed),
+ * decoded into device memory: decompress_frame (src/framed/decompress.rs:284-288) of every frame, with the header parse of
+ * LZ4FrameReader::new (:102-161), the block walk and stop rules of decode_block (:198-282) and the dictionary / linked-block
+ * window of :238-269 run on the device.
+ *   d_in, in_len, d_out, out_cap: HOST arrays of n_frames entries; d_in[f] / d_out[f] are DEVICE addresses.  Frames may alias
+ *     each other (one tensor may serve as many frames); outputs must not overlap each other or any input.  d_dict: device.
+ *   d_out_len, d_consumed, d_status: DEVICE arrays of n_frames entries, written in stream order on `hip_stream` (a hipStream_t
+ *     of the current device; NULL = the legacy default stream).
+ * Per frame the results are those of lzf_frame_decompress_many on the same bytes: status, out_len bytes and consumed, also
+ * LZF_OUT_CAPACITY at the same block when out_cap[f] is short, and LZF_E_NO_MEMORY for a frame that does not fit the memory
+ * budget (lzf_frame_set_memory_budget) alone; with out_cap[f] >= lzf_frame_decompress_bound_device's bound no frame ends in
+ * LZF_OUT_CAPACITY.  Nothing in d_out[f] beyond out_len[f] is written.
+ * The host waits twice on the stream: for the per-frame scan summary and for the block table (24 bytes per block), which it
+ * needs to plan the decode; it then enqueues block checksums, decode, delivery, the copy into d_out and the content checksums,
+ * waits for its own small upload of job lists to leave host memory (it is first in the stream at that point), and returns.
+ * No host memory of the call is read after it returns.  The waits make the call NOT graph-capturable.  Scratch comes from the
+ * device's stream-ordered memory pool and is freed in stream order.  Frames go through in passes of the memory budget, with
+ * the host driver's accounting.  No state is kept between calls and lzf_frame_stats is not touched; the calls do not take the
+ * host drivers' lock, except to read the memory budget.
+ * Checksums are computed on the device only: block checksums in one launch per pass; a content checksum is one serial XXH32
+ * chain per frame (~1.3 GB/s each, many frames at once), so one huge frame with a content checksum is bounded by its chain.
+ * Returns LZF_OK or a negative LZF_E_* (bad arguments, HIP failure, LZF_E_NO_DEVICE without a device: no CPU fallback). */
+/* Per frame: the most its blocks can decode to.  For a frame whose header parses, this is the sum over the blocks the walk
+ * finds of (compressed ? min(255*len + 16, block_maxsize) : len); 0 for a frame whose header fails.  Synchronous. */
+int lzf_frame_decompress_bound_device(uint32_t n_frames, const uint8_t* const* d_in, const size_t* in_len,
+                                      size_t* out_bound, void* hip_stream);
+/* lzf_frame_decompress_many for frames that live in device memory, decoded into device memory. */
+int lzf_frame_decompress_device_many(uint32_t n_frames, const uint8_t* const* d_in, const size_t* in_len,
+                                     const uint8_t* d_dict, size_t dict_len,
+                                     uint8_t* const* d_out, const size_t* out_cap,
+                                     uint64_t* d_out_len, uint64_t* d_consumed, int32_t* d_status,
+                                     void* hip_stream);
 
 /* Frame assembly from already-compressed blocks (what rank 0 does after the RCCL all-gather of a
  * block-sharded compression): writes header, then for every block

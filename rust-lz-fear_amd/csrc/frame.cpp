@@ -15,6 +15,7 @@
 #include <mutex>
 #include "../../include/lzfear_frame.h"
 #include "host_staging.h"
+#include "frame_jobs.h"
 
 namespace {
 // a HIP failure inside a driver: nothing asynchronous may still read the caller's (or this call's) host arrays when it returns
@@ -798,14 +799,10 @@ namespace {
 
 struct DFrame {
     lzf_frame_info fi; std::vector<Blk> blocks; FrameScan sc; bool live = false, linked = false;
-    size_t in_off = 0, out_off = 0, out_size = 0;      // device offsets: the frame's bytes; linked: the stream's output buffer
-    std::vector<size_t> job;                             // per block: job index or SIZE_MAX (stored)
-    std::vector<size_t> slot;                            // independent: device offset of the block's output slot
-    uint32_t chain = 0;                                  // linked: index among the linked streams
+    size_t in_off = 0;                                   // device offset of the frame's bytes
     size_t need = 0;                                     // device bytes this frame asks for (input + output room + packed result)
 };
-// the most a block of `len` compressed bytes can decode to: every byte a 255-run length byte (raw/decompress.rs:40-56)
-inline size_t block_out_bound(size_t bmax, size_t len) { const size_t e = 255 * len + 16; return e < bmax ? e : bmax; }
+using lzf_frame_jobs::block_out_bound;
 
 // One pass over frames [f0, f1): everything on the device at once.
 int decompress_group(Staging& sg, std::vector<DFrame>& fr, uint32_t f0, uint32_t f1, const uint8_t* const* in, const size_t* in_len,
@@ -813,8 +810,7 @@ int decompress_group(Staging& sg, std::vector<DFrame>& fr, uint32_t f0, uint32_t
     hipStream_t cs = sg.stream(0), hs = sg.stream(3);
     if (!cs || !hs) return fail_hip();
     TRACE_BEGIN();
-    size_t in_total = 0, out_total = 0, max_steps = 0, n_sums = 0, pack_bound = 0;
-    uint32_t n_chain = 0;
+    size_t in_total = 0, n_sums = 0, pack_bound = 0;
     std::vector<Seg> up;
     for (uint32_t f = f0; f < f1; ++f) {
         DFrame& F = fr[f];
@@ -822,58 +818,36 @@ int decompress_group(Staging& sg, std::vector<DFrame>& fr, uint32_t f0, uint32_t
         const size_t nb = F.blocks.size(), bmax = (size_t)F.fi.block_maxsize;
         F.in_off = in_total; in_total = up256(in_total + F.sc.consumed);
         if (F.sc.consumed) up.push_back({F.in_off, const_cast<uint8_t*>(in[f]), F.sc.consumed});
-        F.job.assign(nb, SIZE_MAX); F.slot.assign(nb, 0);
         if (F.fi.flags & FL_BLOCKSUM) n_sums += nb;
         size_t bound = 0;
         for (size_t i = 0; i < nb; ++i) bound += F.blocks[i].compressed ? block_out_bound(bmax, F.blocks[i].len) : F.blocks[i].len;
         pack_bound = up256(pack_bound + bound);
-        if (F.linked) {
-            // a block may run past its limit by its literals before the stream is stopped: room for that
-            if (nb) { F.chain = n_chain++; F.out_off = out_total; F.out_size = bound + F.sc.consumed + 64; out_total = up256(out_total + F.out_size); if (nb > max_steps) max_steps = nb; }
-        } else {
-            for (size_t i = 0; i < nb; ++i) if (F.blocks[i].compressed) { F.slot[i] = out_total; out_total = up256(out_total + block_out_bound(bmax, F.blocks[i].len) + F.blocks[i].len); }   // limit + C
-        }
     }
     if (!sg.pinned(in_total > pack_bound ? in_total : pack_bound)) return fail_hip();
     uint8_t* const din = static_cast<uint8_t*>(sg.device(S_IN, in_total));
-    uint8_t* const dout = static_cast<uint8_t*>(sg.device(S_OUT, out_total));
-    uint8_t* d_dict = nullptr;
-    if (!din || !dout) return fail_hip();
-    if (dict_len) { d_dict = static_cast<uint8_t*>(sg.device(S_DICT, dict_len)); if (!d_dict) return fail_hip(); HIPOK(hipMemcpyAsync(d_dict, dict, dict_len, hipMemcpyHostToDevice, cs)); }
-    // ---- job list ordered by step: step 0 = every block of the independent frames + block 0 of the linked streams
-    std::vector<lzf_decompress_job> jobs;
-    std::vector<size_t> step_off;
-    const size_t n_steps = max_steps > 1 ? max_steps : 1;
-    std::vector<lzf_chain_step> csteps((size_t)n_chain * n_steps);
-    for (size_t k = 0; k < n_steps; ++k) {
-        step_off.push_back(jobs.size());
-        for (uint32_t f = f0; f < f1; ++f) {
-            DFrame& F = fr[f];
-            if (!F.live) continue;
-            const size_t nb = F.blocks.size(), bmax = (size_t)F.fi.block_maxsize;
-            auto add_job = [&](size_t i) {
-                lzf_decompress_job j;
-                memset(&j, 0, sizeof j);
-                j.input = din + F.in_off + (F.blocks[i].data - in[f]); j.input_len = F.blocks[i].len;
-                j.prefix = d_dict; j.prefix_len = dict_len;                                       // :239-245
-                const size_t lim = bmax;                                                          // :248
-                if (F.linked) { j.out = dout + F.out_off; j.out_cap = lim + F.blocks[i].len; j.output_limit = lim; }   // (patched per step)
-                else { j.out = dout + F.slot[i]; j.out_cap = block_out_bound(bmax, F.blocks[i].len) + F.blocks[i].len; j.output_limit = lim; }
-                F.job[i] = jobs.size(); jobs.push_back(j);
-            };
-            if (!F.linked) { if (k == 0) for (size_t i = 0; i < nb; ++i) if (F.blocks[i].compressed) add_job(i); continue; }
-            if (!nb) continue;
-            lzf_chain_step& st = csteps[k * n_chain + F.chain];
-            memset(&st, 0, sizeof st);
-            st.prev_job = (k > 0 && k - 1 < nb && F.blocks[k - 1].compressed) ? (uint32_t)F.job[k - 1] : UINT32_MAX;
-            st.job = UINT32_MAX; st.out = dout + F.out_off; st.block_maxsize = bmax;
-            if (k < nb) {
-                if (F.blocks[k].compressed) { add_job(k); st.job = (uint32_t)F.job[k]; }
-                else { st.stored_len = F.blocks[k].len; st.stored_src = din + F.in_off + (F.blocks[k].data - in[f]); }
-            }
-        }
+    if (!din) return fail_hip();
+    // ---- output layout and job list (frame_jobs.h): the blocks as device addresses in the uploaded input
+    std::vector<lzf_frame_jobs::Frame> jf(f1 - f0);
+    std::vector<lzf_frame_jobs::Frame*> jfl;
+    for (uint32_t f = f0; f < f1; ++f) {
+        const DFrame& F = fr[f];
+        if (!F.live) continue;
+        lzf_frame_jobs::Frame& J = jf[f - f0];
+        J.linked = F.linked; J.bmax = (size_t)F.fi.block_maxsize; J.consumed = F.sc.consumed;
+        for (const Blk& b : F.blocks) J.blocks.push_back({din + F.in_off + (b.data - in[f]), b.len, b.compressed});
+        jfl.push_back(&J);
     }
-    step_off.push_back(jobs.size());
+    lzf_frame_jobs::Plan plan;
+    lzf_frame_jobs::layout(jfl, plan);
+    uint8_t* const dout = static_cast<uint8_t*>(sg.device(S_OUT, plan.out_total));
+    uint8_t* d_dict = nullptr;
+    if (!dout) return fail_hip();
+    if (dict_len) { d_dict = static_cast<uint8_t*>(sg.device(S_DICT, dict_len)); if (!d_dict) return fail_hip(); HIPOK(hipMemcpyAsync(d_dict, dict, dict_len, hipMemcpyHostToDevice, cs)); }
+    lzf_frame_jobs::build(jfl, plan, dout, d_dict, dict_len);
+    const std::vector<lzf_decompress_job>& jobs = plan.jobs;
+    const std::vector<lzf_chain_step>& csteps = plan.csteps;
+    const size_t n_steps = plan.n_steps;
+    const uint32_t n_chain = plan.n_chain;
     const size_t n_jobs = jobs.size();
     if (n_jobs > 0x7FFFFFFFull) return LZF_E_INVALID;
     // results come back through the pinned mailbox: [block results | block checksums | content hashes]
@@ -915,12 +889,8 @@ int decompress_group(Staging& sg, std::vector<DFrame>& fr, uint32_t f0, uint32_t
         HIPOK(sg.join_copies(cs));
         for (size_t k = 0; k < n_steps; ++k) {
             if (n_chain) RCOK(lzf_chain_decompress_step(d_steps + k * n_chain, d_state, n_chain, d_jobs, d_res, cs));
-            const size_t a = step_off[k], cnt = step_off[k + 1] - a;
-            if (cnt) {
-                uint64_t max_in = 0;                                                       // (the host built the jobs: it knows their sizes)
-                for (size_t q = a; q < a + cnt; ++q) if (jobs[q].input_len > max_in) max_in = jobs[q].input_len;
-                RCOK(lzf_decompress_batch_sized(d_jobs + a, d_res + a, (uint32_t)cnt, max_in, cs));
-            }
+            const size_t a = plan.step_off[k], cnt = plan.step_off[k + 1] - a;
+            if (cnt) RCOK(lzf_decompress_batch_sized(d_jobs + a, d_res + a, (uint32_t)cnt, lzf_frame_jobs::step_max_input(plan, k), cs));
         }
         if (n_jobs) HIPOK(hipMemcpyAsync(mbox, d_res, sizeof(lzf_job_result) * n_jobs, hipMemcpyDeviceToHost, cs));
     } else {
@@ -939,6 +909,7 @@ int decompress_group(Staging& sg, std::vector<DFrame>& fr, uint32_t f0, uint32_t
     for (uint32_t f = f0; f < f1; ++f) {
         DFrame& F = fr[f];
         if (!F.live) continue;
+        const lzf_frame_jobs::Frame& J = jf[f - f0];
         const size_t nb = F.blocks.size(), bmax = (size_t)F.fi.block_maxsize;
         const bool csum = F.fi.flags & FL_CSUM, bsum = F.fi.flags & FL_BLOCKSUM;
         const size_t sum0 = sum_i; if (bsum) sum_i += nb;
@@ -957,11 +928,11 @@ int decompress_group(Staging& sg, std::vector<DFrame>& fr, uint32_t f0, uint32_t
             if (bsum && sums[sum0 + i] != b.want_sum) { st = LZF_F_BLOCK_CHECKSUM_FAIL; break; }   // :228-235
             size_t n; const uint8_t* dsrc;                                                    // device address of the block's bytes
             if (b.compressed) {
-                const lzf_job_result& r = res[F.job[i]];
+                const lzf_job_result& r = res[J.job[i]];
                 if (r.status != LZF_OK) { st = r.status; break; }                             // CodecError
-                if (F.linked) { n = (size_t)r.out_len - hist; dsrc = dout + F.out_off + hist; }
-                else { n = (size_t)r.out_len; dsrc = dout + F.slot[i]; }
-            } else { n = b.len; dsrc = F.linked ? dout + F.out_off + hist : din + F.in_off + (b.data - in[f]); }   // :250 stored
+                if (F.linked) { n = (size_t)r.out_len - hist; dsrc = dout + J.out_off + hist; }
+                else { n = (size_t)r.out_len; dsrc = dout + J.slot[i]; }
+            } else { n = b.len; dsrc = F.linked ? dout + J.out_off + hist : din + F.in_off + (b.data - in[f]); }   // :250 stored
             hist += n;
             if (n > bmax) { st = LZF_F_BLOCK_SIZE_OVERFLOW; break; }                          // :272-274
             if (out_cap[f] - w < n) { st = LZF_OUT_CAPACITY; break; }
@@ -1067,6 +1038,13 @@ void lzf_frame_set_memory_budget(size_t bytes) {
     std::lock_guard<std::mutex> g(sg.lock());
     g_budget = bytes;
 }
+}  // extern "C"
+size_t lzf_frame_jobs::memory_budget() {
+    Staging& sg = Staging::get();
+    std::lock_guard<std::mutex> g(sg.lock());
+    return g_budget;
+}
+extern "C" {
 
 // ---- streaming frame writer (compress.rs:138-157, :160-282 with the stream fed piece by piece) ------------------------------
 struct lzf_frame_writer {

@@ -1,0 +1,443 @@
+// frame_device.hip — the frame layer for frames that live in device memory (include/lzfear_frame.h, "frames in device memory").
+//
+// lzf_frame_decompress_many's work without the host round trip of the bytes: the host sees only what it needs to plan.
+//   1. scan, pass 1 (lzf_frame_scan_kernel, one lane per frame): header (decompress.rs:102-161) and block walk (:198-235) of
+//      lzf_frame_scan.h; a 64-byte summary per frame comes back (wait 1).
+//   2. scan, pass 2 (lzf_frame_table_kernel): the block table, 24 bytes per block, comes back (wait 2).
+//   3. the host builds the decode jobs from the table (frame_jobs.h, the same layout as the host driver), uploads them and
+//      enqueues, pass after pass of the memory budget: block checksums (lzf_xxh32_batch), decode (lzf_decompress_batch_sized /
+//      lzf_chain_decompress_step), delivery (lzf_frame_deliver_kernel: the reader's stop rules in stream order, :198-288),
+//      the copy into the caller's outputs (lzf_copy_ranges), content checksums (lzf_xxh32_batch + lzf_frame_content_check_kernel).
+// Results (status, out_len, consumed) are written to device arrays in stream order; scratch comes from the stream-ordered pool.
+#include <hip/hip_runtime.h>
+#include <cstring>
+#include <vector>
+#include "../../include/lzfear_frame.h"
+#include "lzf_frame_scan.h"
+#include "frame_jobs.h"
+
+namespace {
+
+// per frame, scan pass 1 (fixed size: the host reads n of them back)
+struct FSum {
+    int32_t status;             // header error, or the walk's structural error (OK: the walk reached the EndMark)
+    uint32_t flags;             // FLG byte | kLive (the header parsed) | kEndmark
+    uint64_t consumed;          // bytes read when the header parse or the walk ended
+    uint64_t n_blocks, n_compressed;
+    uint64_t out_bound;         // sum of (compressed ? block_out_bound : len): the most the blocks can decode to
+    uint64_t need;              // sum of (compressed ? block_out_bound : 0) + len + 256: the host driver's device memory accounting
+    uint32_t max_len;           // largest block (compressed bytes)
+    uint32_t want_content;      // content checksum behind the EndMark
+    uint64_t block_maxsize;
+};
+static_assert(sizeof(FSum) == 64, "scan summary");
+constexpr uint32_t kLive = 0x100u, kEndmark = 0x200u;
+
+// per block, scan pass 2
+struct TBlk { uint64_t off; uint32_t len; uint32_t want_sum; uint64_t end_off; };      // len | INCOMPRESSIBLE for a stored block
+static_assert(sizeof(TBlk) == 24, "block table entry");
+
+// per frame and per block of a pass, for the delivery kernel
+constexpr uint32_t kNone = 0xFFFFFFFFu;
+constexpr uint32_t kLinked = 1u, kCheckContent = 2u;
+struct DFrameDesc {
+    uint8_t* dst;               // the caller's output
+    const uint8_t* stream;      // linked: the stream buffer
+    uint64_t out_cap, scan_consumed, bmax;
+    uint32_t blk0, nb;          // the frame's blocks: DBlkDesc [blk0, blk0 + nb) of the pass
+    int32_t scan_err;
+    uint32_t flags;             // kLinked | kCheckContent (EndMark read, content checksum present, walk ended without error)
+    uint32_t frame, hash_idx, link_idx, pad;
+};
+struct DBlkDesc {
+    const uint8_t* src;         // independent: the decoded block's slot, or the stored block in the input
+    uint64_t end_off;           // input read once the block's checksum word is
+    uint32_t job;               // decode job of the pass, kNone: stored
+    uint32_t sum_idx;           // block checksum of the pass, kNone: none
+    uint32_t want_sum, len;     // len: a stored block's length
+};
+
+__global__ __launch_bounds__(64) void lzf_frame_scan_kernel(const uint8_t* const* __restrict__ in, const uint64_t* __restrict__ in_len, uint32_t n,
+                                                            FSum* __restrict__ sums, int32_t* __restrict__ d_status,
+                                                            uint64_t* __restrict__ d_out_len, uint64_t* __restrict__ d_consumed) {
+    const uint32_t f = blockIdx.x * 64u + threadIdx.x;
+    if (f >= n) return;
+    const uint8_t* p = in[f];
+    const uint64_t len = in_len[f];
+    const lzf_scan::Header h = lzf_scan::read_header(p, len);
+    FSum s;
+    memset(&s, 0, sizeof s);
+    if (h.status != lzf_scan::OK) {
+        s.status = h.status; s.consumed = h.consumed;
+    } else {
+        const uint64_t bmax = h.block_maxsize;
+        const lzf_scan::Walk w = lzf_scan::walk_blocks(p, len, h, [&](const lzf_scan::Block& b) {
+            const uint64_t bob = lzf_scan::block_out_bound(bmax, b.len);
+            ++s.n_blocks;
+            if (b.compressed) { ++s.n_compressed; s.out_bound += bob; s.need += bob; } else s.out_bound += b.len;
+            s.need += (uint64_t)b.len + 256u;
+            if (b.len > s.max_len) s.max_len = b.len;
+        });
+        s.status = w.status; s.consumed = w.consumed; s.want_content = w.want_content; s.block_maxsize = bmax;
+        s.flags = h.flags | kLive | (w.endmark ? kEndmark : 0u);
+    }
+    sums[f] = s;
+    if (d_status) {                     // final for a frame whose header fails; the delivery kernel overwrites the others
+        d_status[f] = h.status; d_out_len[f] = 0; d_consumed[f] = h.status != lzf_scan::OK ? h.consumed : s.consumed;
+    }
+}
+
+__global__ __launch_bounds__(64) void lzf_frame_table_kernel(const uint8_t* const* __restrict__ in, const uint64_t* __restrict__ in_len,
+                                                             const uint64_t* __restrict__ blk0, const uint64_t* __restrict__ cnt, uint32_t n,
+                                                             TBlk* __restrict__ table) {
+    const uint32_t f = blockIdx.x * 64u + threadIdx.x;
+    if (f >= n || blk0[f] == ~0ull) return;
+    const uint8_t* p = in[f];
+    const uint64_t len = in_len[f];
+    const lzf_scan::Header h = lzf_scan::read_header(p, len);
+    if (h.status != lzf_scan::OK) return;
+    TBlk* t = table + blk0[f];
+    const uint64_t room = cnt[f];       // what pass 1 found: never more entries than the host allocated
+    uint64_t k = 0;
+    lzf_scan::walk_blocks(p, len, h, [&](const lzf_scan::Block& b) {
+        if (k < room) t[k] = TBlk{b.off, b.len | (b.compressed ? 0u : lzf_scan::INCOMPRESSIBLE), b.want_sum, b.end_off};
+        ++k;
+    });
+}
+
+// The reader's delivery loop (decompress.rs:198-288; frame.cpp's decompress_group) for one frame per wavefront, 64 blocks per
+// round.  Per block, in stream order: block checksum (:228-235), codec status (CodecError), n > block_maxsize (:272-274), room
+// in the caller's output (LZF_OUT_CAPACITY), n == 0 (the io::Read adapter stops at an empty block, :52-71,:286).  The first
+// stop fixes status, out_len and consumed; without one the scan's status and consumed stand and the content checksum is due.
+__global__ __launch_bounds__(64) void lzf_frame_deliver_kernel(const DFrameDesc* __restrict__ frames, const DBlkDesc* __restrict__ blks,
+                                                               const lzf_decompress_job* __restrict__ jobs, const lzf_job_result* __restrict__ res,
+                                                               const uint32_t* __restrict__ sums,
+                                                               const uint8_t** __restrict__ r_src, uint8_t** __restrict__ r_dst, uint64_t* __restrict__ r_len,
+                                                               const uint8_t** __restrict__ l_src, uint8_t** __restrict__ l_dst, uint64_t* __restrict__ l_len,
+                                                               uint64_t* __restrict__ h_len, uint32_t* __restrict__ h_check,
+                                                               int32_t* __restrict__ d_status, uint64_t* __restrict__ d_out_len, uint64_t* __restrict__ d_consumed) {
+    const DFrameDesc F = frames[blockIdx.x];
+    const uint32_t lane = threadIdx.x;
+    const bool linked = (F.flags & kLinked) != 0;
+    uint64_t w = 0, consumed = F.scan_consumed;
+    int st = LZF_OK;
+    bool stopped = false;
+    for (uint32_t base = 0; base < F.nb; base += 64u) {
+        const uint32_t i = base + lane;
+        const bool act = i < F.nb;
+        uint64_t n = 0, end_off = 0;
+        int code = 0;
+        const uint8_t* src = nullptr;
+        if (act) {
+            const DBlkDesc b = blks[F.blk0 + i];
+            end_off = b.end_off; src = b.src;
+            if (b.sum_idx != kNone && sums[b.sum_idx] != b.want_sum) code = LZF_F_BLOCK_CHECKSUM_FAIL;
+            else if (b.job != kNone) {
+                const lzf_job_result r = res[b.job];
+                if (r.status != LZF_OK) code = r.status;
+                else n = r.out_len - (linked ? jobs[b.job].out_existing_len : 0ull);   // linked: the chain step set the stream's length before the job
+            } else n = b.len;
+            if (!code && n > F.bmax) code = LZF_F_BLOCK_SIZE_OVERFLOW;
+        }
+        uint64_t incl = n;                                      // inclusive scan of n over the wave
+        for (uint32_t d = 1; d < 64u; d <<= 1) {
+            const uint64_t v = __shfl_up(incl, d, 64);
+            if (lane >= d) incl += v;
+        }
+        const uint64_t at = w + (incl - n);                     // where the block goes in the caller's output
+        const bool cap = act && !code && (at > F.out_cap || F.out_cap - at < n);
+        const bool zero = act && !code && !cap && n == 0;
+        const uint64_t stops = __ballot(act && (code || cap || zero));
+        const uint32_t first = stops ? (uint32_t)__builtin_ctzll(stops) : 64u;
+        if (!linked && act) {
+            const bool give = lane < first;
+            r_src[F.blk0 + i] = src; r_dst[F.blk0 + i] = F.dst + (give ? at : 0ull); r_len[F.blk0 + i] = give ? n : 0ull;
+        }
+        if (stops) {
+            const int c = __shfl(code, (int)first, 64);
+            const int cp = __shfl((int)cap, (int)first, 64);
+            w = __shfl(at, (int)first, 64);
+            consumed = __shfl(end_off, (int)first, 64);
+            st = c ? c : cp ? LZF_OUT_CAPACITY : LZF_OK;
+            stopped = true;
+            break;
+        }
+        w += __shfl(incl, 63, 64);
+    }
+    if (lane != 0) return;
+    if (linked && F.nb) { l_src[F.link_idx] = F.stream; l_dst[F.link_idx] = F.dst; l_len[F.link_idx] = w; }
+    d_out_len[F.frame] = w;
+    if (stopped) { d_status[F.frame] = st; d_consumed[F.frame] = consumed; }
+    else { d_status[F.frame] = F.scan_err; d_consumed[F.frame] = F.scan_consumed; }
+    if (F.hash_idx != kNone) {
+        const bool check = !stopped && (F.flags & kCheckContent);
+        h_len[F.hash_idx] = check ? w : 0ull; h_check[F.hash_idx] = check ? 1u : 0u;
+    }
+}
+
+// decompress.rs:207-211: FrameChecksumFail where the EndMark was read, nothing stopped the frame and the hash differs
+__global__ __launch_bounds__(256) void lzf_frame_content_check_kernel(const uint32_t* __restrict__ got, const uint32_t* __restrict__ want,
+                                                                      const uint32_t* __restrict__ check, const uint32_t* __restrict__ frame,
+                                                                      uint32_t n, int32_t* __restrict__ d_status) {
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k < n && check[k] && got[k] != want[k]) d_status[frame[k]] = LZF_F_FRAME_CHECKSUM_FAIL;
+}
+
+// a frame that does not fit the memory budget alone
+__global__ void lzf_frame_no_memory_kernel(uint32_t f, int32_t* d_status, uint64_t* d_out_len, uint64_t* d_consumed) {
+    if (threadIdx.x == 0) { d_status[f] = LZF_E_NO_MEMORY; d_out_len[f] = 0; d_consumed[f] = 0; }
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------
+struct PoolAlloc {                      // stream-ordered scratch, handed back in stream order on every way out
+    void* p = nullptr; hipStream_t st = nullptr;
+    explicit PoolAlloc(hipStream_t s) : st(s) {}
+    ~PoolAlloc() { if (p) (void)hipFreeAsync(p, st); }
+    bool get(size_t bytes) { if (hipMallocAsync(&p, bytes ? bytes : 256, st) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return false; } return true; }
+    template <class T> T* at(size_t off) const { return reinterpret_cast<T*>(static_cast<uint8_t*>(p) + off); }
+};
+// (on failure: nothing enqueued may still read host memory of the call when it returns)
+#define DEV_TRY(e) do { if ((e) != hipSuccess) { (void)hipGetLastError(); (void)hipStreamSynchronize(st); return LZF_E_HIP; } } while (0)
+#define RC_TRY(e) do { const int rc__ = (e); if (rc__ != LZF_OK) { (void)hipStreamSynchronize(st); return rc__; } } while (0)
+#define KERNEL(...) do { hipLaunchKernelGGL(__VA_ARGS__); DEV_TRY(hipGetLastError()); } while (0)
+
+int usable_device() {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { (void)hipGetLastError(); return LZF_E_NO_DEVICE; }
+    return LZF_OK;
+}
+using lzf_frame_jobs::up256;
+
+// Scan pass 1 of n frames: summaries back on the host (the call's first wait).  `args` keeps [ptrs | lens | blk0 | cnt] for pass 2.
+int scan_summaries(uint32_t n, const uint8_t* const* d_in, const size_t* in_len, hipStream_t st, PoolAlloc& args, std::vector<FSum>& sums,
+                   int32_t* d_status, uint64_t* d_out_len, uint64_t* d_consumed) {
+    const size_t o_sum = up256(32 * (size_t)n);
+    if (!args.get(o_sum + sizeof(FSum) * (size_t)n)) return LZF_E_HIP;
+    std::vector<uint64_t> h(2 * (size_t)n);
+    for (uint32_t f = 0; f < n; ++f) { h[f] = reinterpret_cast<uintptr_t>(d_in[f]); h[n + f] = in_len[f]; }
+    DEV_TRY(hipMemcpyAsync(args.p, h.data(), 16 * (size_t)n, hipMemcpyHostToDevice, st));
+    KERNEL(lzf_frame_scan_kernel, dim3((n + 63u) / 64u), dim3(64), 0, st, args.at<const uint8_t* const>(0), args.at<const uint64_t>(8 * (size_t)n), n,
+           args.at<FSum>(o_sum), d_status, d_out_len, d_consumed);
+    sums.resize(n);
+    DEV_TRY(hipMemcpyAsync(sums.data(), args.at<FSum>(o_sum), sizeof(FSum) * (size_t)n, hipMemcpyDeviceToHost, st));
+    DEV_TRY(hipStreamSynchronize(st));
+    return LZF_OK;
+}
+
+// host image of the small arrays of every pass: one upload
+struct Image {
+    std::vector<uint8_t> h;
+    size_t add(const void* p, size_t bytes) { const size_t o = h.size(); h.resize(up256(o + bytes)); if (bytes && p) memcpy(h.data() + o, p, bytes); return o; }
+};
+struct Scratch {                         // device-only arrays (written by kernels), after the image
+    size_t total = 0;
+    size_t add(size_t bytes) { const size_t o = total; total = up256(total + bytes); return o; }
+};
+
+struct Pass {
+    uint32_t f0 = 0, f1 = 0;
+    bool no_memory = false;
+    std::vector<lzf_frame_jobs::Frame> jf;
+    std::vector<uint32_t> jf_frame;
+    lzf_frame_jobs::Plan plan;
+    uint32_t n_frames = 0, n_blks = 0, n_sums = 0, n_hash = 0, n_link = 0;
+    uint64_t ind_max = 0, link_max = 0;
+    // image offsets
+    size_t i_jobs = 0, i_steps = 0, i_sptr = 0, i_slen = 0, i_frames = 0, i_blks = 0, i_hptr = 0, i_hwant = 0, i_hframe = 0;
+    // scratch offsets
+    size_t s_res = 0, s_state = 0, s_sums = 0, s_rsrc = 0, s_rdst = 0, s_rlen = 0, s_lsrc = 0, s_ldst = 0, s_llen = 0, s_hlen = 0, s_hcheck = 0, s_hout = 0;
+};
+
+}  // namespace
+
+extern "C" {
+
+int lzf_frame_decompress_bound_device(uint32_t n_frames, const uint8_t* const* d_in, const size_t* in_len, size_t* out_bound, void* hip_stream) {
+    if (n_frames && (!d_in || !in_len || !out_bound)) return LZF_E_INVALID;
+    if (usable_device() != LZF_OK) return LZF_E_NO_DEVICE;
+    if (n_frames == 0) return LZF_OK;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    PoolAlloc args(st);
+    std::vector<FSum> sums;
+    RC_TRY(scan_summaries(n_frames, d_in, in_len, st, args, sums, nullptr, nullptr, nullptr));
+    for (uint32_t f = 0; f < n_frames; ++f) out_bound[f] = (sums[f].flags & kLive) ? (size_t)sums[f].out_bound : 0;
+    return LZF_OK;
+}
+
+int lzf_frame_decompress_device_many(uint32_t n_frames, const uint8_t* const* d_in, const size_t* in_len,
+                                     const uint8_t* d_dict, size_t dict_len,
+                                     uint8_t* const* d_out, const size_t* out_cap,
+                                     uint64_t* d_out_len, uint64_t* d_consumed, int32_t* d_status, void* hip_stream) {
+    if (n_frames && (!d_in || !in_len || !d_out || !out_cap || !d_out_len || !d_consumed || !d_status)) return LZF_E_INVALID;
+    if (!d_dict) dict_len = 0;
+    if (usable_device() != LZF_OK) return LZF_E_NO_DEVICE;
+    if (n_frames == 0) return LZF_OK;
+    const uint32_t n = n_frames;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    // ---- scan pass 1: summaries (wait 1)
+    PoolAlloc args(st);
+    std::vector<FSum> sum;
+    RC_TRY(scan_summaries(n, d_in, in_len, st, args, sum, d_status, d_out_len, d_consumed));
+    // ---- scan pass 2: the block table of every frame whose header parses (wait 2)
+    std::vector<uint64_t> blk0(n, ~0ull), cnt(n, 0);
+    uint64_t n_table = 0;
+    for (uint32_t f = 0; f < n; ++f) if (sum[f].flags & kLive) { blk0[f] = n_table; cnt[f] = sum[f].n_blocks; n_table += sum[f].n_blocks; }
+    if (n_table > 0x7FFFFFFFull) { (void)hipStreamSynchronize(st); return LZF_E_INVALID; }
+    std::vector<TBlk> table((size_t)n_table);
+    if (n_table) {
+        std::vector<uint64_t> h(2 * (size_t)n);
+        memcpy(h.data(), blk0.data(), 8 * (size_t)n); memcpy(h.data() + n, cnt.data(), 8 * (size_t)n);
+        DEV_TRY(hipMemcpyAsync(args.at<uint64_t>(16 * (size_t)n), h.data(), 16 * (size_t)n, hipMemcpyHostToDevice, st));
+        PoolAlloc tab(st);
+        if (!tab.get(sizeof(TBlk) * (size_t)n_table)) { (void)hipStreamSynchronize(st); return LZF_E_HIP; }
+        KERNEL(lzf_frame_table_kernel, dim3((n + 63u) / 64u), dim3(64), 0, st, args.at<const uint8_t* const>(0), args.at<const uint64_t>(8 * (size_t)n),
+               args.at<const uint64_t>(16 * (size_t)n), args.at<const uint64_t>(24 * (size_t)n), n, tab.at<TBlk>(0));
+        DEV_TRY(hipMemcpyAsync(table.data(), tab.p, sizeof(TBlk) * (size_t)n_table, hipMemcpyDeviceToHost, st));
+        DEV_TRY(hipStreamSynchronize(st));
+    }
+    // ---- passes: as many frames as the memory budget holds, with the host driver's accounting (frame.cpp); a frame that does
+    //      not fit alone gets LZF_E_NO_MEMORY
+    std::vector<size_t> need(n, 0);
+    for (uint32_t f = 0; f < n; ++f) if (sum[f].flags & kLive) need[f] = (size_t)sum[f].consumed + 2 * (size_t)sum[f].need + 4096;
+    size_t budget = lzf_frame_jobs::memory_budget();
+    if (!budget) { size_t free_b = 0, total_b = 0; DEV_TRY(hipMemGetInfo(&free_b, &total_b)); budget = free_b / 2; }
+    std::vector<Pass> passes;
+    for (uint32_t f0 = 0; f0 < n;) {
+        size_t s = 0; uint32_t f1 = f0;
+        while (f1 < n && (f1 == f0 || s + need[f1] <= budget)) { s += need[f1]; ++f1; }
+        Pass P; P.f0 = f0; P.f1 = f1;
+        P.no_memory = f1 == f0 + 1 && (sum[f0].flags & kLive) && need[f0] > budget;
+        passes.push_back(std::move(P));
+        f0 = f1;
+    }
+    // ---- output layout of every pass; the passes share one slot allocation (stream order: pass p + 1 decodes after pass p's copy)
+    size_t slots_bytes = 0;
+    for (Pass& P : passes) {
+        if (P.no_memory) continue;
+        P.jf.reserve(P.f1 - P.f0);
+        for (uint32_t f = P.f0; f < P.f1; ++f) {
+            if (!(sum[f].flags & kLive)) continue;
+            P.jf.emplace_back();
+            lzf_frame_jobs::Frame& J = P.jf.back();
+            J.linked = !(sum[f].flags & lzf_scan::FL_INDEP); J.bmax = (size_t)sum[f].block_maxsize; J.consumed = (size_t)sum[f].consumed;
+            for (uint64_t k = 0; k < cnt[f]; ++k) {
+                const TBlk& t = table[blk0[f] + k];
+                J.blocks.push_back({d_in[f] + t.off, t.len & ~lzf_scan::INCOMPRESSIBLE, (t.len & lzf_scan::INCOMPRESSIBLE) == 0});
+            }
+            P.jf_frame.push_back(f);
+        }
+        std::vector<lzf_frame_jobs::Frame*> jfl;
+        for (auto& J : P.jf) jfl.push_back(&J);
+        lzf_frame_jobs::layout(jfl, P.plan);
+        if (P.plan.out_total > slots_bytes) slots_bytes = P.plan.out_total;
+    }
+    PoolAlloc slots(st);
+    if (slots_bytes && !slots.get(slots_bytes)) { (void)hipStreamSynchronize(st); return LZF_E_HIP; }
+    uint8_t* const dslots = static_cast<uint8_t*>(slots.p);
+    // ---- jobs and descriptors of every pass into one image
+    Image img; Scratch scr;
+    for (Pass& P : passes) {
+        if (P.no_memory) continue;
+        std::vector<lzf_frame_jobs::Frame*> jfl;
+        for (auto& J : P.jf) jfl.push_back(&J);
+        lzf_frame_jobs::build(jfl, P.plan, dslots, d_dict, dict_len);
+        if (P.plan.jobs.size() > 0x7FFFFFFFull) { (void)hipStreamSynchronize(st); return LZF_E_INVALID; }
+        std::vector<DFrameDesc> fd; std::vector<DBlkDesc> bd;
+        std::vector<const uint8_t*> sptr; std::vector<uint64_t> slen;
+        std::vector<const uint8_t*> hptr; std::vector<uint32_t> hwant, hframe;
+        for (size_t q = 0; q < P.jf.size(); ++q) {
+            const lzf_frame_jobs::Frame& J = P.jf[q];
+            const uint32_t f = P.jf_frame[q];
+            const FSum& S = sum[f];
+            DFrameDesc d;
+            memset(&d, 0, sizeof d);
+            d.dst = d_out[f]; d.stream = J.linked && !J.blocks.empty() ? dslots + J.out_off : nullptr;
+            d.out_cap = out_cap[f]; d.scan_consumed = S.consumed; d.bmax = J.bmax;
+            d.blk0 = (uint32_t)bd.size(); d.nb = (uint32_t)J.blocks.size(); d.scan_err = S.status;
+            d.flags = (J.linked ? kLinked : 0u);
+            d.frame = f; d.hash_idx = kNone; d.link_idx = kNone;
+            if ((S.flags & kEndmark) && (S.flags & lzf_scan::FL_CSUM) && S.status == LZF_OK) {
+                d.flags |= kCheckContent; d.hash_idx = (uint32_t)hptr.size();
+                hptr.push_back(d_out[f]); hwant.push_back(S.want_content); hframe.push_back(f);
+            }
+            if (J.linked && !J.blocks.empty()) {
+                d.link_idx = P.n_link++;
+                const uint64_t m = (uint64_t)J.blocks.size() * J.bmax, c = out_cap[f] < m ? out_cap[f] : m;
+                if (c > P.link_max) P.link_max = c;
+            } else if (!J.blocks.empty() && J.bmax > P.ind_max) P.ind_max = J.bmax;
+            const bool bsum = (S.flags & lzf_scan::FL_BLOCKSUM) != 0;
+            for (size_t i = 0; i < J.blocks.size(); ++i) {
+                const TBlk& t = table[blk0[f] + i];
+                DBlkDesc b;
+                b.src = J.blocks[i].compressed ? (J.linked ? nullptr : dslots + J.slot[i]) : J.blocks[i].src;
+                b.end_off = t.end_off; b.job = J.job[i] == SIZE_MAX ? kNone : (uint32_t)J.job[i];
+                b.sum_idx = kNone; b.want_sum = t.want_sum; b.len = J.blocks[i].len;
+                if (bsum) { b.sum_idx = (uint32_t)sptr.size(); sptr.push_back(J.blocks[i].src); slen.push_back(J.blocks[i].len); }
+                bd.push_back(b);
+            }
+            fd.push_back(d);
+        }
+        P.n_frames = (uint32_t)fd.size(); P.n_blks = (uint32_t)bd.size(); P.n_sums = (uint32_t)sptr.size(); P.n_hash = (uint32_t)hptr.size();
+        P.i_jobs = img.add(P.plan.jobs.data(), sizeof(lzf_decompress_job) * P.plan.jobs.size());
+        P.i_steps = img.add(P.plan.csteps.data(), sizeof(lzf_chain_step) * P.plan.csteps.size());
+        P.i_sptr = img.add(sptr.data(), sizeof(void*) * sptr.size()); P.i_slen = img.add(slen.data(), 8 * slen.size());
+        P.i_frames = img.add(fd.data(), sizeof(DFrameDesc) * fd.size()); P.i_blks = img.add(bd.data(), sizeof(DBlkDesc) * bd.size());
+        P.i_hptr = img.add(hptr.data(), sizeof(void*) * hptr.size()); P.i_hwant = img.add(hwant.data(), 4 * hwant.size()); P.i_hframe = img.add(hframe.data(), 4 * hframe.size());
+        P.s_res = scr.add(sizeof(lzf_job_result) * P.plan.jobs.size()); P.s_state = scr.add(sizeof(lzf_chain_state) * P.plan.n_chain);
+        P.s_sums = scr.add(4 * (size_t)P.n_sums);
+        P.s_rsrc = scr.add(8 * (size_t)P.n_blks); P.s_rdst = scr.add(8 * (size_t)P.n_blks); P.s_rlen = scr.add(8 * (size_t)P.n_blks);
+        P.s_lsrc = scr.add(8 * (size_t)P.n_link); P.s_ldst = scr.add(8 * (size_t)P.n_link); P.s_llen = scr.add(8 * (size_t)P.n_link);
+        P.s_hlen = scr.add(8 * (size_t)P.n_hash); P.s_hcheck = scr.add(4 * (size_t)P.n_hash); P.s_hout = scr.add(4 * (size_t)P.n_hash);
+    }
+    // ---- one upload, then the kernels of every pass
+    const size_t img_bytes = img.h.size();
+    PoolAlloc meta(st);
+    if (!meta.get(img_bytes + scr.total)) { (void)hipStreamSynchronize(st); return LZF_E_HIP; }
+    hipEvent_t uploaded = nullptr;
+    DEV_TRY(hipEventCreateWithFlags(&uploaded, hipEventDisableTiming));
+    struct EventOwner { hipEvent_t e; ~EventOwner() { if (e) (void)hipEventDestroy(e); } } owner{uploaded};
+    if (img_bytes) DEV_TRY(hipMemcpyAsync(meta.p, img.h.data(), img_bytes, hipMemcpyHostToDevice, st));
+    DEV_TRY(hipEventRecord(uploaded, st));
+    if (scr.total) DEV_TRY(hipMemsetAsync(meta.at<uint8_t>(img_bytes), 0, scr.total, st));       // chain states, range and hash lengths start at 0
+    auto I = [&](size_t off) { return meta.at<uint8_t>(off); };
+    auto S = [&](size_t off) { return meta.at<uint8_t>(img_bytes + off); };
+    for (Pass& P : passes) {
+        if (P.no_memory) { KERNEL(lzf_frame_no_memory_kernel, dim3(1), dim3(64), 0, st, P.f0, d_status, d_out_len, d_consumed); continue; }
+        if (!P.n_frames) continue;
+        lzf_decompress_job* const d_jobs = reinterpret_cast<lzf_decompress_job*>(I(P.i_jobs));
+        lzf_job_result* const d_res = reinterpret_cast<lzf_job_result*>(S(P.s_res));
+        uint32_t* const d_sums = reinterpret_cast<uint32_t*>(S(P.s_sums));
+        if (P.n_sums) RC_TRY(lzf_xxh32_batch(reinterpret_cast<const uint8_t* const*>(I(P.i_sptr)), reinterpret_cast<const uint64_t*>(I(P.i_slen)), d_sums, P.n_sums, st));
+        const lzf_frame_jobs::Plan& pl = P.plan;
+        for (size_t k = 0; k < pl.n_steps; ++k) {
+            if (pl.n_chain) RC_TRY(lzf_chain_decompress_step(reinterpret_cast<const lzf_chain_step*>(I(P.i_steps)) + k * pl.n_chain,
+                                                             reinterpret_cast<lzf_chain_state*>(S(P.s_state)), pl.n_chain, d_jobs, d_res, st));
+            const size_t a = pl.step_off[k], c = pl.step_off[k + 1] - a;
+            if (c) RC_TRY(lzf_decompress_batch_sized(d_jobs + a, d_res + a, (uint32_t)c, lzf_frame_jobs::step_max_input(pl, k), st));
+        }
+        KERNEL(lzf_frame_deliver_kernel, dim3(P.n_frames), dim3(64), 0, st,
+               reinterpret_cast<const DFrameDesc*>(I(P.i_frames)), reinterpret_cast<const DBlkDesc*>(I(P.i_blks)), (const lzf_decompress_job*)d_jobs,
+               (const lzf_job_result*)d_res, (const uint32_t*)d_sums,
+               reinterpret_cast<const uint8_t**>(S(P.s_rsrc)), reinterpret_cast<uint8_t**>(S(P.s_rdst)), reinterpret_cast<uint64_t*>(S(P.s_rlen)),
+               reinterpret_cast<const uint8_t**>(S(P.s_lsrc)), reinterpret_cast<uint8_t**>(S(P.s_ldst)), reinterpret_cast<uint64_t*>(S(P.s_llen)),
+               reinterpret_cast<uint64_t*>(S(P.s_hlen)), reinterpret_cast<uint32_t*>(S(P.s_hcheck)), d_status, d_out_len, d_consumed);
+        if (P.n_blks && P.ind_max)
+            RC_TRY(lzf_copy_ranges(reinterpret_cast<const uint8_t* const*>(S(P.s_rsrc)), reinterpret_cast<uint8_t* const*>(S(P.s_rdst)),
+                                   reinterpret_cast<const uint64_t*>(S(P.s_rlen)), P.n_blks, P.ind_max, st));
+        if (P.n_link && P.link_max)
+            RC_TRY(lzf_copy_ranges(reinterpret_cast<const uint8_t* const*>(S(P.s_lsrc)), reinterpret_cast<uint8_t* const*>(S(P.s_ldst)),
+                                   reinterpret_cast<const uint64_t*>(S(P.s_llen)), P.n_link, P.link_max, st));
+        if (P.n_hash) {
+            RC_TRY(lzf_xxh32_batch(reinterpret_cast<const uint8_t* const*>(I(P.i_hptr)), reinterpret_cast<const uint64_t*>(S(P.s_hlen)),
+                                   reinterpret_cast<uint32_t*>(S(P.s_hout)), P.n_hash, st));
+            KERNEL(lzf_frame_content_check_kernel, dim3((P.n_hash + 255u) / 256u), dim3(256), 0, st,
+                   reinterpret_cast<const uint32_t*>(S(P.s_hout)), reinterpret_cast<const uint32_t*>(I(P.i_hwant)),
+                   reinterpret_cast<const uint32_t*>(S(P.s_hcheck)), reinterpret_cast<const uint32_t*>(I(P.i_hframe)), P.n_hash, d_status);
+        }
+    }
+    // the image left host memory long ago (it was first in the stream behind the table read-back); the kernels run on
+    DEV_TRY(hipEventSynchronize(uploaded));
+    return LZF_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,105 @@
+// frame_jobs.h — the decode jobs of one pass of frames, shared by lzf_frame_decompress_many (frame.cpp: frames in host
+// memory, uploaded) and lzf_frame_decompress_device_many (frame_device.hip: frames in device memory).
+//
+// Layout of decompress.rs:238-269 on the device: an independent frame's compressed blocks each get an output slot of
+// block_out_bound + input length (the limit plus what the literals may overshoot); a linked frame is one stream
+// buffer that lzf_chain_decompress_step grows block after block, with the dictionary as every job's prefix (:239-245).
+// Stored blocks get no job: independent ones are read straight from the input, linked ones are appended by the chain step.
+#ifndef LZF_FRAME_JOBS_H
+#define LZF_FRAME_JOBS_H
+
+#include <cstdint>
+#include <cstring>
+#include <vector>
+#include "../../include/lzfear_hip.h"
+
+namespace lzf_frame_jobs {
+
+inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+// the most a block of `len` compressed bytes can decode to: every byte a 255-run length byte (raw/decompress.rs:40-56)
+inline size_t block_out_bound(size_t bmax, size_t len) { const size_t e = 255 * len + 16; return e < bmax ? e : bmax; }
+
+struct BlockRef { const uint8_t* src; uint32_t len; bool compressed; };    // src: device address of the block's bytes
+struct Frame {
+    bool linked = false;
+    size_t bmax = 0, consumed = 0;                // consumed: the frame's input bytes (linked stream room, see layout)
+    std::vector<BlockRef> blocks;
+    // filled by layout / build
+    size_t out_off = 0, out_size = 0;             // linked: the stream's output buffer
+    uint32_t chain = 0;                           // linked: index among the linked streams
+    std::vector<size_t> job;                      // per block: job index or SIZE_MAX (stored)
+    std::vector<size_t> slot;                     // independent: offset of the block's output slot
+};
+struct Plan {
+    std::vector<lzf_decompress_job> jobs;         // ordered by step: step 0 = every block of the independent frames + block 0 of the linked streams
+    std::vector<size_t> step_off;                 // jobs of step k are [step_off[k], step_off[k + 1])
+    std::vector<lzf_chain_step> csteps;           // n_steps x n_chain
+    size_t out_total = 0, n_steps = 1;
+    uint32_t n_chain = 0;
+};
+
+// Output offsets of every frame, in frame order.
+inline void layout(const std::vector<Frame*>& fs, Plan& p) {
+    size_t max_steps = 0;
+    for (Frame* F : fs) {
+        const size_t nb = F->blocks.size();
+        F->job.assign(nb, SIZE_MAX); F->slot.assign(nb, 0);
+        if (F->linked) {
+            size_t bound = 0;
+            for (const BlockRef& b : F->blocks) bound += b.compressed ? block_out_bound(F->bmax, b.len) : b.len;
+            // a block may run past its limit by its literals before the stream is stopped: room for that
+            if (nb) { F->chain = p.n_chain++; F->out_off = p.out_total; F->out_size = bound + F->consumed + 64; p.out_total = up256(p.out_total + F->out_size); if (nb > max_steps) max_steps = nb; }
+        } else {
+            for (size_t i = 0; i < nb; ++i) if (F->blocks[i].compressed) { F->slot[i] = p.out_total; p.out_total = up256(p.out_total + block_out_bound(F->bmax, F->blocks[i].len) + F->blocks[i].len); }
+        }
+    }
+    p.n_steps = max_steps > 1 ? max_steps : 1;
+}
+
+// Jobs and chain steps against the output allocation `dout` (p.out_total bytes) and the device dictionary.
+inline void build(const std::vector<Frame*>& fs, Plan& p, uint8_t* dout, const uint8_t* d_dict, size_t dict_len) {
+    p.jobs.clear(); p.step_off.clear();
+    p.csteps.assign((size_t)p.n_chain * p.n_steps, lzf_chain_step{});
+    for (size_t k = 0; k < p.n_steps; ++k) {
+        p.step_off.push_back(p.jobs.size());
+        for (Frame* Fp : fs) {
+            Frame& F = *Fp;
+            const size_t nb = F.blocks.size(), bmax = F.bmax;
+            auto add_job = [&](size_t i) {
+                lzf_decompress_job j;
+                memset(&j, 0, sizeof j);
+                j.input = F.blocks[i].src; j.input_len = F.blocks[i].len;
+                j.prefix = d_dict; j.prefix_len = dict_len;                                       // :239-245
+                const size_t lim = bmax;                                                          // :248
+                if (F.linked) { j.out = dout + F.out_off; j.out_cap = lim + F.blocks[i].len; j.output_limit = lim; }   // (patched per step)
+                else { j.out = dout + F.slot[i]; j.out_cap = block_out_bound(bmax, F.blocks[i].len) + F.blocks[i].len; j.output_limit = lim; }
+                F.job[i] = p.jobs.size(); p.jobs.push_back(j);
+            };
+            if (!F.linked) { if (k == 0) for (size_t i = 0; i < nb; ++i) if (F.blocks[i].compressed) add_job(i); continue; }
+            if (!nb) continue;
+            lzf_chain_step& st = p.csteps[k * p.n_chain + F.chain];
+            memset(&st, 0, sizeof st);
+            st.prev_job = (k > 0 && k - 1 < nb && F.blocks[k - 1].compressed) ? (uint32_t)F.job[k - 1] : UINT32_MAX;
+            st.job = UINT32_MAX; st.out = dout + F.out_off; st.block_maxsize = bmax;
+            if (k < nb) {
+                if (F.blocks[k].compressed) { add_job(k); st.job = (uint32_t)F.job[k]; }
+                else { st.stored_len = F.blocks[k].len; st.stored_src = F.blocks[k].src; }
+            }
+        }
+    }
+    p.step_off.push_back(p.jobs.size());
+}
+
+// the largest input of the jobs of step k (lzf_decompress_batch_sized's bound: the host built the jobs, it knows their sizes)
+inline uint64_t step_max_input(const Plan& p, size_t k) {
+    uint64_t m = 0;
+    for (size_t q = p.step_off[k]; q < p.step_off[k + 1]; ++q) if (p.jobs[q].input_len > m) m = p.jobs[q].input_len;
+    return m;
+}
+
+// lzf_frame_set_memory_budget's value (0: half of the free device memory), read under the frame layer's lock (frame.cpp)
+size_t memory_budget();
+
+}  // namespace lzf_frame_jobs
+
+#endif  // LZF_FRAME_JOBS_H

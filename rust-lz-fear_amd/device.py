@@ -1,6 +1,8 @@
 """Device-resident batches for the C ABI: job arrays built with numpy, kept in HBM as torch
 uint8 tensors.  torch is plumbing here (device memory + streams), not the product: the codec
 is liblzfear_hip.so and every launch goes through its extern "C" entry points."""
+import ctypes as C
+
 import numpy as np
 import torch
 
@@ -78,3 +80,52 @@ class BlockSet:
         j["out_cap"] = self.lens
         j["table_kind"] = ffi.TABLE_U32
         return j
+
+
+# ---- frames in device memory (include/lzfear_frame.h, "frames in device memory") -------------------------------------------
+
+def _frame_args(frames):
+    for t in frames:
+        assert t.dtype == torch.uint8 and t.is_cuda and t.dim() == 1 and t.is_contiguous(), "frames: 1-D contiguous uint8 CUDA tensors"
+    n = len(frames)
+    return n, (C.c_void_p * n)(*[t.data_ptr() for t in frames]), (C.c_size_t * n)(*[t.numel() for t in frames])
+
+
+def frame_decompress_bound(frames, stream=None):
+    """lzf_frame_decompress_bound_device: per frame the most its blocks can decode to (0 for a frame whose header fails).
+    Synchronous: the frames are scanned on the device and the bounds come back to the host."""
+    n, ptrs, lens = _frame_args(frames)
+    if n == 0:
+        return []
+    bound = (C.c_size_t * n)()
+    ffi.check(ffi.lib().lzf_frame_decompress_bound_device(n, ptrs, lens, bound, _stream_ptr(stream)))
+    return list(bound)
+
+
+def frame_decompress_many(frames, outs, dictionary=None, stream=None):
+    """lzf_frame_decompress_device_many: frames (1-D uint8 CUDA tensors) decoded into `outs` (1-D uint8 CUDA tensors, their
+    lengths are the capacities).  Returns (status int32, out_len int64, consumed int64) as CUDA tensors, written in order on
+    `stream`; nothing is synchronised beyond the call's own scan."""
+    n, ptrs, lens = _frame_args(frames)
+    assert len(outs) == n
+    dev = frames[0].device if n else torch.device("cuda", torch.cuda.current_device())
+    status = torch.empty(n, dtype=torch.int32, device=dev)         # (empty: no fill kernel on another stream; the call writes every entry)
+    out_len = torch.empty(n, dtype=torch.int64, device=dev)
+    consumed = torch.empty(n, dtype=torch.int64, device=dev)
+    if n == 0:
+        return status, out_len, consumed
+    for t in outs:
+        assert t.dtype == torch.uint8 and t.is_cuda and t.dim() == 1 and t.is_contiguous(), "outs: 1-D contiguous uint8 CUDA tensors"
+    optr = (C.c_void_p * n)(*[t.data_ptr() for t in outs])
+    caps = (C.c_size_t * n)(*[t.numel() for t in outs])
+    dptr, dlen = None, 0
+    if dictionary is not None and dictionary.numel():
+        assert dictionary.dtype == torch.uint8 and dictionary.is_cuda and dictionary.is_contiguous()
+        dptr, dlen = dictionary.data_ptr(), dictionary.numel()
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    # (the results are written by kernels on `s`: keep torch's caching allocator from handing them out elsewhere meanwhile)
+    for t in (status, out_len, consumed):
+        t.record_stream(s)
+    ffi.check(ffi.lib().lzf_frame_decompress_device_many(n, ptrs, lens, dptr, dlen, optr, caps, out_len.data_ptr(), consumed.data_ptr(),
+                                                         status.data_ptr(), s.cuda_stream))
+    return status, out_len, consumed

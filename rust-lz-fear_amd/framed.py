@@ -233,6 +233,27 @@ def decompress_frames(frames, dictionary=b"", caps=None, with_consumed=False):
     return [(st[f], C.string_at(outs[f], olen[f])) for f in range(n)]
 
 
+def decompress_frames_device(frames, dictionary=None, caps=None, stream=None):
+    """`decompress_frames` for frames that live on the device (1-D uint8 CUDA tensors), decoded on the device
+    (lzf_frame_decompress_device_many).  Outputs are sized from lzf_frame_decompress_bound_device when `caps` is None.
+    Returns [(status, out_tensor[:out_len], consumed)] once `stream` (default: the current stream) has finished the call."""
+    import torch
+    from . import device
+    frames = list(frames)
+    if not frames:
+        return []
+    dev = frames[0].device
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    if caps is None:
+        caps = device.frame_decompress_bound(frames, stream=s)
+    outs = [torch.empty(int(c), dtype=torch.uint8, device=dev) for c in caps]
+    with torch.cuda.stream(s):
+        status, out_len, consumed = device.frame_decompress_many(frames, outs, dictionary=dictionary, stream=s)
+    s.synchronize()
+    st, ol, co = status.cpu().tolist(), out_len.cpu().tolist(), consumed.cpu().tolist()
+    return [(st[f], outs[f][:ol[f]], co[f]) for f in range(len(frames))]
+
+
 class FrameBlockReader:
     """The C ABI's block-by-block reader (lzf_frame_reader_*, include/lzfear_frame.h) over a frame in memory:
     `LZ4FrameReader::new` + `decode_block` (src/framed/decompress.rs:102-161,198-282), one call = one block."""
