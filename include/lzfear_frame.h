@@ -212,6 +212,32 @@ int lzf_frame_decompress_device_many(uint32_t n_frames, const uint8_t* const* d_
                                      uint8_t* const* d_out, const size_t* out_cap,
                                      uint64_t* d_out_len, uint64_t* d_consumed, int32_t* d_status,
                                      void* hip_stream);
+/* lzf_frame_compress_many for inputs that live in device memory, compressed into device memory: compress_internal
+ * (src/framed/compress.rs:160-282) of every frame with the settings `s` (a host struct, shared by all frames as in
+ * lzf_frame_compress_many: flags, dictionary id and content size of the header come from it).  s->dictionary must be NULL
+ * (else LZF_E_INVALID: no host pointer reaches a kernel); the dictionary is d_dict / dict_len in device memory, NULL = none.
+ *   d_in, in_len, d_out, out_cap: HOST arrays of n_frames entries; d_in[f] / d_out[f] are DEVICE addresses at any alignment.
+ *     Inputs may alias each other; outputs must not overlap each other or any input.
+ *   d_out_len, d_status: DEVICE arrays of n_frames entries, written in stream order on `hip_stream`.
+ * Per frame the status, out_len and bytes are those of lzf_frame_compress_many with the same settings, dictionary bytes and
+ * input: LZF_OUT_CAPACITY when out_cap[f] < lzf_frame_compress_bound(s, in_len[f]), LZF_F_INVALID_BLOCK_SIZE / LZF_F_PANIC on
+ * every frame for a bad block size, and a block status other than LZF_OK / LZF_OUTPUT_FULL (stored raw) fails the frame with the
+ * first such status in block order and out_len 0.  Nothing outside d_out[f][0, out_len) is written; a frame whose status is
+ * not LZF_OK gets no writes at all.
+ * The host plans the whole call from in_len[] and the settings and reads nothing back from the device: it enqueues the work,
+ * waits for its own upload of job lists to leave host memory and returns; no host memory of the call is read after that.  Not
+ * a goal: graph capture.  Scratch comes from the stream-ordered pool, freed in stream order.  Frames go through in passes of the
+ * memory budget (lzf_frame_set_memory_budget) counted in scratch (output slots, dictionary copies, tables); a frame whose
+ * scratch alone is over it is a pass of its own — the call never reports LZF_E_NO_MEMORY.  lzf_frame_stats is not touched and
+ * no host-driver lock is taken, except to read the budget.  Checksums are computed on the device only: block checksums in one
+ * launch per pass, content checksums over d_in[f] directly, one serial XXH32 chain per frame (~1.3 GB/s each, many frames at
+ * once), so one huge frame with a content checksum is bounded by its chain.
+ * Returns LZF_OK or a negative LZF_E_* (bad arguments, HIP failure, LZF_E_NO_DEVICE without a device: no CPU fallback). */
+int lzf_frame_compress_device_many(const lzf_settings* s, uint32_t n_frames,
+                                   const uint8_t* const* d_in, const size_t* in_len,
+                                   const uint8_t* d_dict, size_t dict_len,
+                                   uint8_t* const* d_out, const size_t* out_cap,
+                                   uint64_t* d_out_len, int32_t* d_status, void* hip_stream);
 
 /* Frame assembly from already-compressed blocks (what rank 0 does after the RCCL all-gather of a
  * block-sharded compression): writes header, then for every block

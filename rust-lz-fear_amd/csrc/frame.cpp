@@ -16,6 +16,7 @@
 #include "../../include/lzfear_frame.h"
 #include "host_staging.h"
 #include "frame_jobs.h"
+#include "lzf_frame_layout.h"
 
 namespace {
 // a HIP failure inside a driver: nothing asynchronous may still read the caller's (or this call's) host arrays when it returns
@@ -57,36 +58,8 @@ struct Xxh32 {
 constexpr uint8_t FL_INDEP = 0x20, FL_BLOCKSUM = 0x10, FL_CSIZE = 0x08, FL_CSUM = 0x04, FL_DICTID = 0x01;
 constexpr uint32_t INCOMPRESSIBLE = 0x80000000u;   // framed/mod.rs:18
 
-// header.rs:53-62 BlockDescriptor::new
-int bd_new(uint64_t maxsize, uint8_t* bd) {
-    unsigned tz = maxsize ? (unsigned)__builtin_ctzll(maxsize) : 64;
-    unsigned maybe = ((tz > 8 ? tz - 8 : 0) / 2) & 0xFF;
-    uint8_t b = (uint8_t)(maybe << 4);
-    if (b & 0x8F) return LZF_F_PANIC;                           // :55 parse(..).unwrap()
-    unsigned size = (b >> 4) & 7;
-    if (size < 4 || (1ull << (size * 2 + 8)) != maxsize) return LZF_F_INVALID_BLOCK_SIZE;
-    *bd = b;
-    return LZF_OK;
-}
-
-// compress.rs:163-200: magic, FLG, BD, [content size], [dict id], HC
-size_t write_header(const lzf_settings* s, uint8_t bd, uint8_t* out) {
-    uint8_t flags = 0;
-    if (s->independent_blocks) flags |= FL_INDEP;
-    if (s->block_checksums) flags |= FL_BLOCKSUM;
-    if (s->content_checksum) flags |= FL_CSUM;
-    if (s->has_dictionary_id) flags |= FL_DICTID;
-    if (s->has_content_size) flags |= FL_CSIZE;
-    size_t w = 0;
-    wr32(out, LZF_MAGIC); w += 4;
-    out[w++] = (uint8_t)((1 << 6) | flags);
-    out[w++] = bd;
-    if (s->has_content_size) { wr32(out + w, (uint32_t)s->content_size); wr32(out + w + 4, (uint32_t)(s->content_size >> 32)); w += 8; }
-    if (s->has_dictionary_id) { wr32(out + w, s->dictionary_id); w += 4; }
-    Xxh32 h; h.update(out + 4, w - 4);
-    out[w++] = (uint8_t)(h.digest() >> 8);
-    return w;
-}
+using lzf_layout::bd_new;          // header.rs:53-62 (lzf_frame_layout.h)
+using lzf_layout::write_header;    // compress.rs:163-200
 
 // Template table of compress.rs:202-214 built by the GPU seeding kernel.
 int seeded_template(const uint8_t* dict, size_t dict_len, lzf_u32_table* host_table) {
@@ -592,48 +565,45 @@ static int compress_many_pass(const lzf_settings* s, uint32_t n_frames, const ui
     }
 
     size_t jn = 0;
+    std::vector<std::vector<lzf_frame_jobs::CWindow>> win(n_frames);             // every block's input window (frame_jobs.h)
+    for (uint32_t f = 0; f < n_frames; ++f) if (fr[f].nb) lzf_frame_jobs::compress_windows(in_len[f], bs, dict_len, indep, win[f]);
     if (indep) {
         for (uint32_t f = 0; f < n_frames; ++f) {
             fr[f].job0 = jn; up_first[f] = up.size();
             size_t w = fr[f].in_off;
             if (fr[f].nb && !per_block_prefix) seg(w, in[f], in_len[f]);
             for (size_t i = 0; i < fr[f].nb; ++i, ++jn) {
-                const size_t off = i * bs, n = in_len[f] - off < bs ? in_len[f] - off : bs;
+                const lzf_frame_jobs::CWindow& W = win[f][i];
                 lzf_compress_job& j = jobs[jn];
                 memset(&j, 0, sizeof j);
-                if (per_block_prefix) {
-                    seg(w, dict, dict_len); seg(w + dict_len, in[f] + off, n);
-                    j.input = din_at(f, w); j.input_len = dict_len + n; j.cursor = dict_len; w += dict_len + n;
-                } else { j.input = din_at(f, fr[f].in_off + off); j.input_len = n; j.cursor = 0; }
-                j.out_cap = n; j.table_kind = LZF_TABLE_U32;                   // :242, :202
+                if (per_block_prefix) {                                         // dict ++ block, a copy of its own
+                    seg(w, dict, dict_len); seg(w + dict_len, in[f] + W.off, W.n);
+                    j.input = din_at(f, w); w += W.hist + W.n;
+                } else j.input = din_at(f, fr[f].in_off + W.lo);
+                j.input_len = W.hist + W.n; j.cursor = W.hist;
+                j.out_cap = W.n; j.table_kind = LZF_TABLE_U32;                 // :242, :202
                 if (dict_len >= 8) { j.table = d_tmpl; j.flags = LZF_CJOB_TABLE_READONLY; }       // :220,:270 template.clone()
-                job_frame[jn] = f; job_block[jn] = (uint32_t)i; job_out_off[jn] = out_total; out_total += n;
+                job_frame[jn] = f; job_block[jn] = (uint32_t)i; job_out_off[jn] = out_total; out_total += W.n;
             }
         }
         step_off = {0, n_jobs};
     } else {
         // linked blocks (:271-275): in_buffer = the last <= 64 KiB of (dict ++ data so far) ++ block, a pointer into the
-        // stream's slab; the table's offset grows by what the window forgets
-        struct Ls { size_t lo, len; };                                          // in_buffer = slab[lo, lo + len)
-        std::vector<Ls> ls(n_frames, Ls{0, dict_len});
+        // stream's slab (dict ++ data); the table's offset grows by what the window forgets
         for (uint32_t f = 0; f < n_frames; ++f) if (fr[f].nb) { seg(fr[f].in_off, dict, dict_len); seg(fr[f].in_off + dict_len, in[f], in_len[f]); }
-        std::vector<uint64_t> pending_add(n_frames, 0);
         for (size_t k = 0; k < max_nb; ++k) {
             step_off.push_back(jn);
             for (uint32_t f = 0; f < n_frames; ++f) {
                 if (k >= fr[f].nb) continue;
-                const size_t off = k * bs, n = in_len[f] - off < bs ? in_len[f] - off : bs;
+                const lzf_frame_jobs::CWindow& W = win[f][k];
                 lzf_compress_job& j = jobs[jn];
                 memset(&j, 0, sizeof j);
-                j.input = din_at(f, fr[f].in_off + ls[f].lo); j.input_len = ls[f].len + n; j.cursor = ls[f].len;   // :222,:243
-                j.out_cap = n; j.table_kind = LZF_TABLE_U32;
+                j.input = din_at(f, fr[f].in_off + W.lo); j.input_len = W.hist + W.n; j.cursor = W.hist;   // :222,:243
+                j.out_cap = W.n; j.table_kind = LZF_TABLE_U32;
                 j.table = d_tabs + lf_index[f];
-                h_tabptr[jn] = j.table; h_adds[jn] = pending_add[f];           // applied before this step
-                job_frame[jn] = f; job_block[jn] = (uint32_t)k; job_out_off[jn] = out_total; out_total += n;
+                h_tabptr[jn] = j.table; h_adds[jn] = W.add;                     // applied before this step
+                job_frame[jn] = f; job_block[jn] = (uint32_t)k; job_out_off[jn] = out_total; out_total += W.n;
                 ++jn;
-                ls[f].len += n;
-                pending_add[f] = 0;
-                if (ls[f].len > LZF_WINDOW_SIZE) { const size_t forget = ls[f].len - LZF_WINDOW_SIZE; pending_add[f] = forget; ls[f].lo += forget; ls[f].len = LZF_WINDOW_SIZE; }
             }
         }
         step_off.push_back(jn);

@@ -9,12 +9,21 @@
 //      lzf_chain_decompress_step), delivery (lzf_frame_deliver_kernel: the reader's stop rules in stream order, :198-288),
 //      the copy into the caller's outputs (lzf_copy_ranges), content checksums (lzf_xxh32_batch + lzf_frame_content_check_kernel).
 // Results (status, out_len, consumed) are written to device arrays in stream order; scratch comes from the stream-ordered pool.
+//
+// lzf_frame_compress_device_many is lzf_frame_compress_many's work on inputs in device memory.  The host plans the whole call
+// from in_len[] and the settings (frame_jobs.h's input windows, the same as the host driver's) and reads nothing back; per
+// pass of the memory budget it enqueues: the dict ++ block copies (lzf_copy_ranges), the tables (lzf_table_seed_from_dictionary
+// once, copied into every linked stream's table), the compression (lzf_compress_batch; linked streams in lock-step with
+// lzf_table_offset_batch between the steps), assembly (lzf_frame_assemble_kernel: header, length words, EndMark, status and
+// out_len, and the lists of the steps behind it, by lzf_frame_layout.h's rule), the payload copy (lzf_copy_ranges), block and
+// content checksums (lzf_xxh32_batch) and the checksum words (lzf_frame_patch_kernel).
 #include <hip/hip_runtime.h>
 #include <cstring>
 #include <vector>
 #include "../../include/lzfear_frame.h"
 #include "lzf_frame_scan.h"
 #include "frame_jobs.h"
+#include "lzf_frame_layout.h"
 
 namespace {
 
@@ -186,6 +195,84 @@ __global__ __launch_bounds__(256) void lzf_frame_content_check_kernel(const uint
 // a frame that does not fit the memory budget alone
 __global__ void lzf_frame_no_memory_kernel(uint32_t f, int32_t* d_status, uint64_t* d_out_len, uint64_t* d_consumed) {
     if (threadIdx.x == 0) { d_status[f] = LZF_E_NO_MEMORY; d_out_len[f] = 0; d_consumed[f] = 0; }
+}
+
+// ---- compress: per frame and per block of a pass, for the assembly kernel
+struct CFrameDesc {
+    uint8_t* dst;               // the caller's output
+    uint32_t blk0, nb;          // the frame's blocks: CBlkDesc [blk0, blk0 + nb) of the pass, in block order
+    int32_t status0;            // what the host decided: LZF_OK, LZF_OUT_CAPACITY or the block size's error (then nb = 0)
+    uint32_t frame, hash_idx;   // hash_idx: the frame's content checksum in the pass, kNone: none
+    uint32_t pad;
+};
+static_assert(sizeof(CFrameDesc) == 32, "compress frame descriptor");
+struct CBlkDesc {
+    const uint8_t* raw;         // the block in the caller's input: a stored block's payload
+    const uint8_t* slot;        // its job's output: a compressed block's payload
+    uint32_t job, raw_len;      // job of the pass (its result), the block's length
+};
+constexpr uint32_t kBlockSums = 1u, kContentSum = 2u;
+
+// compress.rs:221-281 once the blocks are compressed, one frame per wavefront, 64 blocks per round (lzf_frame_layout.h's rule).
+// Round one finds the frame's status: the first block, in block order, whose status is neither LZF_OK nor LZF_OUTPUT_FULL.
+// Round two is a wave-wide exclusive scan of block_span: where each block's length word, payload and checksum go.  A frame that
+// stays LZF_OK gets its header (the call's one image), length words and EndMark here; the payload copies (r_*), the checksum
+// words (s_at: block i's, c_at: the content's) are left to the launches behind.  A failed frame gets no byte: empty ranges and
+// NULL checksum places.  Every word is written bytewise: frames start at any address.
+__global__ __launch_bounds__(64) void lzf_frame_assemble_kernel(const CFrameDesc* __restrict__ frames, const CBlkDesc* __restrict__ blks,
+                                                                const lzf_job_result* __restrict__ res, const uint8_t* __restrict__ hdr,
+                                                                uint32_t hdr_len, uint32_t flags,
+                                                                const uint8_t** __restrict__ r_src, uint8_t** __restrict__ r_dst,
+                                                                uint64_t* __restrict__ r_len, uint8_t** __restrict__ s_at, uint8_t** __restrict__ c_at,
+                                                                int32_t* __restrict__ d_status, uint64_t* __restrict__ d_out_len) {
+    const CFrameDesc F = frames[blockIdx.x];
+    const uint32_t lane = threadIdx.x;
+    const bool bsum = (flags & kBlockSums) != 0, csum = (flags & kContentSum) != 0;
+    int st = F.status0;
+    for (uint32_t base = 0; st == LZF_OK && base < F.nb; base += 64u) {
+        const uint32_t i = base + lane;
+        lzf_layout::Block b{0u, false, false, LZF_OK};
+        if (i < F.nb) { const CBlkDesc c = blks[F.blk0 + i]; const lzf_job_result r = res[c.job]; b = lzf_layout::block_of(r.status, r.out_len, c.raw_len); }
+        const uint64_t bad = __ballot(b.bad);
+        if (bad) st = __shfl(b.status, (int)__builtin_ctzll(bad), 64);
+    }
+    const bool ok = st == LZF_OK;
+    uint64_t w = hdr_len;
+    for (uint32_t base = 0; base < F.nb; base += 64u) {
+        const uint32_t i = base + lane;
+        const bool act = i < F.nb;
+        CBlkDesc c{nullptr, nullptr, 0u, 0u};
+        lzf_layout::Block b{0u, false, false, LZF_OK};
+        if (act) { c = blks[F.blk0 + i]; const lzf_job_result r = res[c.job]; b = lzf_layout::block_of(r.status, r.out_len, c.raw_len); }
+        const uint64_t span = act ? lzf_layout::block_span(b.len, bsum) : 0ull;
+        uint64_t incl = span;                                   // inclusive scan of the spans over the wave
+        for (uint32_t d = 1; d < 64u; d <<= 1) {
+            const uint64_t v = __shfl_up(incl, d, 64);
+            if (lane >= d) incl += v;
+        }
+        if (act) {
+            const uint32_t g = F.blk0 + i;
+            uint8_t* const at = F.dst + (w + incl - span);      // the block's length word
+            if (ok) {
+                lzf_layout::wr32(at, lzf_layout::size_word(b));
+                r_src[g] = b.stored ? c.raw : c.slot; r_dst[g] = at + 4; r_len[g] = b.len;
+            } else { r_src[g] = c.raw; r_dst[g] = F.dst; r_len[g] = 0; }
+            if (bsum) s_at[g] = ok ? at + 4 + b.len : nullptr;
+        }
+        w += __shfl(incl, 63, 64);
+    }
+    if (ok && lane < hdr_len) F.dst[lane] = hdr[lane];
+    if (ok && lane < 4u) F.dst[w + lane] = 0;                   // EndMark (:277)
+    if (lane != 0) return;
+    d_status[F.frame] = st;
+    d_out_len[F.frame] = ok ? w + lzf_layout::tail_len(csum) : 0ull;
+    if (F.hash_idx != kNone) c_at[F.hash_idx] = ok ? F.dst + w + 4 : nullptr;     // (:279-281)
+}
+
+// the checksum words at their unaligned places (NULL: the frame failed)
+__global__ __launch_bounds__(256) void lzf_frame_patch_kernel(uint8_t* const* __restrict__ at, const uint32_t* __restrict__ val, uint32_t n) {
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k < n && at[k]) lzf_layout::wr32(at[k], val[k]);
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
@@ -437,6 +524,219 @@ int lzf_frame_decompress_device_many(uint32_t n_frames, const uint8_t* const* d_
     }
     // the image left host memory long ago (it was first in the stream behind the table read-back); the kernels run on
     DEV_TRY(hipEventSynchronize(uploaded));
+    return LZF_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// one pass of lzf_frame_compress_device_many: frames [f0, f1), everything in the image (i_*) and the scratch (s_*)
+struct CPass {
+    uint32_t f0 = 0, f1 = 0;
+    uint32_t n_jobs = 0, n_copies = 0, n_linked = 0, n_hash = 0, n_frames = 0;
+    size_t slots = 0, copies = 0, tables = 0;                   // bytes of the pass's part of the work allocation
+    std::vector<size_t> step_off;                               // linked: jobs of step k are [step_off[k], step_off[k + 1])
+    size_t i_jobs = 0, i_tabptr = 0, i_adds = 0, i_cps = 0, i_cpd = 0, i_cpl = 0, i_tps = 0, i_tpd = 0, i_tpl = 0, i_frames = 0, i_blks = 0,
+           i_hptr = 0, i_hlen = 0;
+    size_t s_res = 0, s_rsrc = 0, s_rdst = 0, s_rlen = 0, s_at = 0, s_val = 0;
+};
+}  // namespace
+
+extern "C" {
+
+int lzf_frame_compress_device_many(const lzf_settings* s, uint32_t n_frames, const uint8_t* const* d_in, const size_t* in_len,
+                                   const uint8_t* d_dict, size_t dict_len, uint8_t* const* d_out, const size_t* out_cap,
+                                   uint64_t* d_out_len, int32_t* d_status, void* hip_stream) {
+    if (!s || (n_frames && (!d_in || !in_len || !d_out || !out_cap || !d_out_len || !d_status))) return LZF_E_INVALID;
+    if (s->dictionary) return LZF_E_INVALID;                    // the dictionary is d_dict: no host pointer may reach a kernel
+    if (!d_dict) dict_len = 0;
+    if (usable_device() != LZF_OK) return LZF_E_NO_DEVICE;
+    if (n_frames == 0) return LZF_OK;
+    const uint32_t n = n_frames;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    uint8_t bd = 0;
+    const int bd_rc = lzf_layout::bd_new(s->block_size, &bd);  // compress.rs:183
+    const size_t bs = bd_rc == LZF_OK ? (size_t)s->block_size : 1;
+    const bool indep = s->independent_blocks != 0, bsum = s->block_checksums != 0, csum = s->content_checksum != 0;
+    const bool per_block_prefix = indep && dict_len > 0;       // :218,:268 in_buffer = dict ++ block, for every block
+    uint8_t hdr[lzf_layout::kMaxHeader] = {0};
+    const uint32_t hdr_len = bd_rc == LZF_OK ? (uint32_t)lzf_layout::write_header(s, bd, hdr) : 0u;
+    // ---- per frame: the host driver's status up front, the blocks and the scratch they need
+    std::vector<int32_t> status0(n);
+    std::vector<size_t> nb(n, 0), need(n, 0);
+    // the scratch copies of frame f: dict ++ block of every block (independent blocks with a dictionary), dict ++ block 0 (linked)
+    auto copies_of = [&](uint32_t f) -> size_t {
+        return per_block_prefix ? nb[f] * dict_len + in_len[f] : (!indep && nb[f] && dict_len) ? dict_len + (in_len[f] < bs ? in_len[f] : bs) : 0;
+    };
+    for (uint32_t f = 0; f < n; ++f) {
+        status0[f] = bd_rc != LZF_OK ? bd_rc : out_cap[f] < lzf_frame_compress_bound(s, in_len[f]) ? LZF_OUT_CAPACITY : LZF_OK;
+        if (status0[f] != LZF_OK) continue;
+        nb[f] = (in_len[f] + bs - 1) / bs;
+        need[f] = in_len[f] + copies_of(f) + (indep ? 0 : sizeof(lzf_u32_table)) + 256 * nb[f] + 4096;   // output slots, copies, table, lists
+    }
+    // ---- passes of the memory budget; a frame whose scratch alone is over it is a pass of its own
+    size_t budget = lzf_frame_jobs::memory_budget();
+    if (!budget) { size_t free_b = 0, total_b = 0; DEV_TRY(hipMemGetInfo(&free_b, &total_b)); budget = free_b / 2; }
+    std::vector<CPass> passes;
+    for (uint32_t f0 = 0; f0 < n;) {
+        size_t sum = 0; uint32_t f1 = f0;
+        while (f1 < n && (f1 == f0 || sum + need[f1] <= budget)) { sum += need[f1]; ++f1; }
+        CPass P; P.f0 = f0; P.f1 = f1;
+        passes.push_back(std::move(P));
+        f0 = f1;
+    }
+    // ---- work allocation (output slots | copies | linked tables), shared by the passes (stream order: pass p + 1 compresses
+    //      after pass p's payload copy); the template table of a dictionary of >= 8 bytes
+    size_t work_bytes = 0;
+    for (CPass& P : passes) {
+        for (uint32_t f = P.f0; f < P.f1; ++f) {
+            if (!nb[f]) continue;
+            P.n_jobs += (uint32_t)nb[f]; P.slots += in_len[f]; P.copies += copies_of(f);
+            if (!indep) ++P.n_linked;
+        }
+        P.tables = sizeof(lzf_u32_table) * (size_t)P.n_linked;
+        const size_t b = up256(P.slots) + up256(P.copies) + P.tables;
+        if (b > work_bytes) work_bytes = b;
+    }
+    PoolAlloc work(st), tmpl(st);
+    if (work_bytes && !work.get(work_bytes)) { (void)hipStreamSynchronize(st); return LZF_E_HIP; }
+    lzf_u32_table* d_tmpl = nullptr;
+    if (dict_len >= 8 && work_bytes) {                          // compress.rs:202-211, on the caller's stream
+        if (!tmpl.get(sizeof(lzf_u32_table))) { (void)hipStreamSynchronize(st); return LZF_E_HIP; }
+        d_tmpl = tmpl.at<lzf_u32_table>(0);
+        RC_TRY(lzf_table_seed_from_dictionary(d_tmpl, d_dict, dict_len, st));
+    }
+    // ---- jobs, copies and descriptors of every pass into one image
+    Image img; Scratch scr;
+    const size_t i_hdr = img.add(hdr, sizeof hdr);
+    for (CPass& P : passes) {
+        uint8_t* const dslots = work.at<uint8_t>(0);
+        uint8_t* const dcopies = work.at<uint8_t>(up256(P.slots));
+        lzf_u32_table* const dtabs = work.at<lzf_u32_table>(up256(P.slots) + up256(P.copies));
+        std::vector<lzf_compress_job> jobs(P.n_jobs);
+        std::vector<void*> tabptr; std::vector<uint64_t> adds;
+        std::vector<const uint8_t*> cps, tps, hptr; std::vector<uint8_t*> cpd, tpd; std::vector<uint64_t> cpl, tpl, hlen;
+        std::vector<CFrameDesc> fd; std::vector<CBlkDesc> bdesc(P.n_jobs);
+        std::vector<std::vector<uint32_t>> frame_job(P.f1 - P.f0);
+        size_t slot = 0, copy = 0;
+        uint32_t linked = 0;
+        // the jobs: independent blocks in frame order, linked streams step after step (block k of every stream in step k)
+        std::vector<std::vector<lzf_frame_jobs::CWindow>> wins(P.f1 - P.f0);
+        size_t max_nb = 0;
+        for (uint32_t f = P.f0; f < P.f1; ++f) if (nb[f]) { lzf_frame_jobs::compress_windows(in_len[f], bs, dict_len, indep, wins[f - P.f0]); if (nb[f] > max_nb) max_nb = nb[f]; }
+        std::vector<uint32_t> lf(P.f1 - P.f0, 0);
+        if (!indep) for (uint32_t f = P.f0; f < P.f1; ++f) if (nb[f]) {
+            lf[f - P.f0] = linked++;
+            if (d_tmpl) { tps.push_back(reinterpret_cast<const uint8_t*>(d_tmpl)); tpd.push_back(reinterpret_cast<uint8_t*>(dtabs + lf[f - P.f0])); tpl.push_back(sizeof(lzf_u32_table)); }
+        }
+        uint32_t jn = 0;
+        auto add_job = [&](uint32_t f, size_t k) {
+            const lzf_frame_jobs::CWindow& W = wins[f - P.f0][k];
+            lzf_compress_job& j = jobs[jn];
+            memset(&j, 0, sizeof j);
+            const bool copied = per_block_prefix || (!indep && W.lo < dict_len);      // linked: block 0 behind the whole dictionary
+            if (copied) {                                                             // S[lo, lo + hist + n) = dict[lo, ..) ++ data[0, ..)
+                uint8_t* const c = dcopies + copy;
+                const size_t from_dict = per_block_prefix ? dict_len : dict_len - W.lo;
+                cps.push_back(d_dict + (per_block_prefix ? 0 : W.lo)); cpd.push_back(c); cpl.push_back(from_dict);
+                cps.push_back(d_in[f] + W.off + W.n - (W.hist + W.n - from_dict)); cpd.push_back(c + from_dict); cpl.push_back(W.hist + W.n - from_dict);
+                j.input = c; copy += W.hist + W.n;
+            } else j.input = d_in[f] + (W.lo - (indep ? 0 : dict_len));
+            j.input_len = W.hist + W.n; j.cursor = W.hist;                             // :222,:243
+            j.out = dslots + slot; j.out_cap = W.n; j.table_kind = LZF_TABLE_U32;      // :242, :202
+            if (indep) { if (d_tmpl) { j.table = d_tmpl; j.flags = LZF_CJOB_TABLE_READONLY; } }   // :220,:270 template.clone()
+            else { j.table = dtabs + lf[f - P.f0]; tabptr.push_back(j.table); adds.push_back(W.add); }
+            bdesc[jn] = CBlkDesc{d_in[f] + W.off, dslots + slot, jn, (uint32_t)W.n};
+            slot += W.n;
+            frame_job[f - P.f0].push_back(jn);
+            ++jn;
+        };
+        if (indep) {
+            for (uint32_t f = P.f0; f < P.f1; ++f) for (size_t k = 0; k < nb[f]; ++k) add_job(f, k);
+            P.step_off = {0, jn};
+        } else {
+            for (size_t k = 0; k < max_nb; ++k) {
+                P.step_off.push_back(jn);
+                for (uint32_t f = P.f0; f < P.f1; ++f) if (k < nb[f]) add_job(f, k);
+            }
+            P.step_off.push_back(jn);
+        }
+        // the frames: their blocks in block order (CBlkDesc, reordered), content checksums over the caller's input
+        std::vector<CBlkDesc> blks; blks.reserve(P.n_jobs);
+        for (uint32_t f = P.f0; f < P.f1; ++f) {
+            CFrameDesc d;
+            memset(&d, 0, sizeof d);
+            d.dst = d_out[f]; d.blk0 = (uint32_t)blks.size(); d.nb = (uint32_t)nb[f]; d.status0 = status0[f]; d.frame = f; d.hash_idx = kNone;
+            for (uint32_t q : frame_job[f - P.f0]) blks.push_back(bdesc[q]);
+            if (csum && status0[f] == LZF_OK) {                 // (an empty input: no bytes to read, any valid address)
+                d.hash_idx = (uint32_t)hptr.size(); hptr.push_back(in_len[f] ? d_in[f] : d_out[f]); hlen.push_back(in_len[f]);
+            }
+            fd.push_back(d);
+        }
+        P.n_copies = (uint32_t)cps.size(); P.n_hash = (uint32_t)hptr.size(); P.n_frames = (uint32_t)fd.size();
+        P.i_jobs = img.add(jobs.data(), sizeof(lzf_compress_job) * jobs.size());
+        P.i_tabptr = img.add(tabptr.data(), sizeof(void*) * tabptr.size()); P.i_adds = img.add(adds.data(), 8 * adds.size());
+        P.i_cps = img.add(cps.data(), 8 * cps.size()); P.i_cpd = img.add(cpd.data(), 8 * cpd.size()); P.i_cpl = img.add(cpl.data(), 8 * cpl.size());
+        P.i_tps = img.add(tps.data(), 8 * tps.size()); P.i_tpd = img.add(tpd.data(), 8 * tpd.size()); P.i_tpl = img.add(tpl.data(), 8 * tpl.size());
+        P.i_frames = img.add(fd.data(), sizeof(CFrameDesc) * fd.size()); P.i_blks = img.add(blks.data(), sizeof(CBlkDesc) * blks.size());
+        P.i_hptr = img.add(hptr.data(), 8 * hptr.size()); P.i_hlen = img.add(hlen.data(), 8 * hlen.size());
+        const size_t n_at = (bsum ? (size_t)P.n_jobs : 0) + P.n_hash;
+        P.s_res = scr.add(sizeof(lzf_job_result) * (size_t)P.n_jobs);
+        P.s_rsrc = scr.add(8 * (size_t)P.n_jobs); P.s_rdst = scr.add(8 * (size_t)P.n_jobs); P.s_rlen = scr.add(8 * (size_t)P.n_jobs);
+        P.s_at = scr.add(8 * n_at); P.s_val = scr.add(4 * n_at);
+    }
+    // ---- one upload, then the launches of every pass
+    const size_t img_bytes = img.h.size();
+    PoolAlloc meta(st);
+    if (!meta.get(img_bytes + scr.total)) { (void)hipStreamSynchronize(st); return LZF_E_HIP; }
+    hipEvent_t uploaded = nullptr;
+    DEV_TRY(hipEventCreateWithFlags(&uploaded, hipEventDisableTiming));
+    struct EventOwner { hipEvent_t e; ~EventOwner() { if (e) (void)hipEventDestroy(e); } } owner{uploaded};
+    DEV_TRY(hipMemcpyAsync(meta.p, img.h.data(), img_bytes, hipMemcpyHostToDevice, st));
+    DEV_TRY(hipEventRecord(uploaded, st));
+    auto I = [&](size_t off) { return meta.at<uint8_t>(off); };
+    auto S = [&](size_t off) { return meta.at<uint8_t>(img_bytes + off); };
+    const uint32_t flags = (bsum ? kBlockSums : 0u) | (csum ? kContentSum : 0u);
+    for (CPass& P : passes) {
+        lzf_compress_job* const jobs = reinterpret_cast<lzf_compress_job*>(I(P.i_jobs));
+        lzf_job_result* const res = reinterpret_cast<lzf_job_result*>(S(P.s_res));
+        if (P.n_copies)
+            RC_TRY(lzf_copy_ranges(reinterpret_cast<const uint8_t* const*>(I(P.i_cps)), reinterpret_cast<uint8_t* const*>(I(P.i_cpd)),
+                                   reinterpret_cast<const uint64_t*>(I(P.i_cpl)), P.n_copies, dict_len > bs ? dict_len : bs, st));
+        if (P.n_linked) {                                       // :213-214 table = template.clone() (U32Table::default() without one)
+            if (d_tmpl) RC_TRY(lzf_copy_ranges(reinterpret_cast<const uint8_t* const*>(I(P.i_tps)), reinterpret_cast<uint8_t* const*>(I(P.i_tpd)),
+                                               reinterpret_cast<const uint64_t*>(I(P.i_tpl)), P.n_linked, sizeof(lzf_u32_table), st));
+            else DEV_TRY(hipMemsetAsync(work.at<uint8_t>(up256(P.slots) + up256(P.copies)), 0, P.tables, st));
+        }
+        if (P.n_jobs && indep) RC_TRY(lzf_compress_batch(jobs, res, P.n_jobs, LZF_KINDS_U32 | LZF_KINDS_U32_FRESH_ONLY, st));
+        else if (P.n_jobs) {
+            for (size_t k = 0; k + 1 < P.step_off.size(); ++k) {    // no host round trip between the steps
+                const size_t a = P.step_off[k], c = P.step_off[k + 1] - a;
+                if (!c) continue;
+                if (k > 0) RC_TRY(lzf_table_offset_batch(reinterpret_cast<void* const*>(I(P.i_tabptr)) + a, reinterpret_cast<const uint64_t*>(I(P.i_adds)) + a,
+                                                         (uint32_t)c, LZF_TABLE_U32, st));
+                RC_TRY(lzf_compress_batch(jobs + a, res + a, (uint32_t)c, LZF_KINDS_U32, st));
+            }
+        }
+        const size_t n_sums = bsum ? (size_t)P.n_jobs : 0;
+        uint8_t** const at = reinterpret_cast<uint8_t**>(S(P.s_at));
+        uint32_t* const val = reinterpret_cast<uint32_t*>(S(P.s_val));
+        KERNEL(lzf_frame_assemble_kernel, dim3(P.n_frames), dim3(64), 0, st,
+               reinterpret_cast<const CFrameDesc*>(I(P.i_frames)), reinterpret_cast<const CBlkDesc*>(I(P.i_blks)), (const lzf_job_result*)res,
+               (const uint8_t*)I(i_hdr), hdr_len, flags,
+               reinterpret_cast<const uint8_t**>(S(P.s_rsrc)), reinterpret_cast<uint8_t**>(S(P.s_rdst)), reinterpret_cast<uint64_t*>(S(P.s_rlen)),
+               at, at + n_sums, d_status, d_out_len);
+        if (P.n_jobs)
+            RC_TRY(lzf_copy_ranges(reinterpret_cast<const uint8_t* const*>(S(P.s_rsrc)), reinterpret_cast<uint8_t* const*>(S(P.s_rdst)),
+                                   reinterpret_cast<const uint64_t*>(S(P.s_rlen)), P.n_jobs, bs, st));
+        if (n_sums)
+            RC_TRY(lzf_xxh32_batch(reinterpret_cast<const uint8_t* const*>(S(P.s_rsrc)), reinterpret_cast<const uint64_t*>(S(P.s_rlen)), val, (uint32_t)n_sums, st));
+        if (P.n_hash)                                           // (on the caller's stream: a forked checksum stream did not pay)
+            RC_TRY(lzf_xxh32_batch(reinterpret_cast<const uint8_t* const*>(I(P.i_hptr)), reinterpret_cast<const uint64_t*>(I(P.i_hlen)), val + n_sums, P.n_hash, st));
+        const size_t n_at = n_sums + P.n_hash;
+        if (n_at) KERNEL(lzf_frame_patch_kernel, dim3((uint32_t)((n_at + 255u) / 256u)), dim3(256), 0, st, (uint8_t* const*)at, (const uint32_t*)val, (uint32_t)n_at);
+    }
+    DEV_TRY(hipEventSynchronize(uploaded));                     // the image has left host memory; the launches run on
     return LZF_OK;
 }
 

@@ -1,5 +1,6 @@
 // frame_jobs.h — the decode jobs of one pass of frames, shared by lzf_frame_decompress_many (frame.cpp: frames in host
-// memory, uploaded) and lzf_frame_decompress_device_many (frame_device.hip: frames in device memory).
+// memory, uploaded) and lzf_frame_decompress_device_many (frame_device.hip: frames in device memory); at the end the input
+// windows of the compress jobs, shared the same way by lzf_frame_compress_many and lzf_frame_compress_device_many.
 //
 // Layout of decompress.rs:238-269 on the device: an independent frame's compressed blocks each get an output slot of
 // block_out_bound + input length (the limit plus what the literals may overshoot); a linked frame is one stream
@@ -11,7 +12,7 @@
 #include <cstdint>
 #include <cstring>
 #include <vector>
-#include "../../include/lzfear_hip.h"
+#include "../../include/lzfear_frame.h"
 
 namespace lzf_frame_jobs {
 
@@ -95,6 +96,30 @@ inline uint64_t step_max_input(const Plan& p, size_t k) {
     uint64_t m = 0;
     for (size_t q = p.step_off[k]; q < p.step_off[k + 1]; ++q) if (p.jobs[q].input_len > m) m = p.jobs[q].input_len;
     return m;
+}
+
+// ---- the compress side: every block's input window (src/framed/compress.rs:217-275), shared by lzf_frame_compress_many
+//      (frame.cpp) and lzf_frame_compress_device_many (frame_device.hip)
+// Block k's payload is data[off, off + n).  Its job compresses S[lo, lo + hist + n) from cursor `hist`, where
+//   linked blocks (:271-275): S = dict ++ data and the history is the last <= 64 KiB of what came before it (block 0: the whole
+//     dictionary); `add` is what the window forgot since the block before: the stream's table.offset(add) is due before it.
+//     Every non-final block is a whole block of >= 64 KiB, so from block 1 on the window lies inside data (lo >= dict_len);
+//   independent blocks with a dictionary (:218,:268): S = dict ++ this block alone, lo = 0, hist = dict_len;
+//   independent blocks without one: S = data, lo = off, hist = 0.
+struct CWindow { size_t off, n, lo, hist; uint64_t add; };
+inline void compress_windows(size_t in_len, size_t bs, size_t dict_len, bool indep, std::vector<CWindow>& w) {
+    w.clear();
+    const size_t nb = (in_len + bs - 1) / bs;
+    size_t lo = 0, len = dict_len;                        // linked: the history is S[lo, lo + len)
+    uint64_t pending = 0;
+    for (size_t k = 0; k < nb; ++k) {
+        const size_t off = k * bs, n = in_len - off < bs ? in_len - off : bs;
+        if (indep) { w.push_back(dict_len ? CWindow{off, n, 0, dict_len, 0} : CWindow{off, n, off, 0, 0}); continue; }
+        w.push_back(CWindow{off, n, lo, len, pending});
+        len += n;
+        pending = 0;
+        if (len > LZF_WINDOW_SIZE) { const size_t forget = len - LZF_WINDOW_SIZE; pending = forget; lo += forget; len = LZF_WINDOW_SIZE; }
+    }
 }
 
 // lzf_frame_set_memory_budget's value (0: half of the free device memory), read under the frame layer's lock (frame.cpp)

@@ -129,3 +129,31 @@ def frame_decompress_many(frames, outs, dictionary=None, stream=None):
     ffi.check(ffi.lib().lzf_frame_decompress_device_many(n, ptrs, lens, dptr, dlen, optr, caps, out_len.data_ptr(), consumed.data_ptr(),
                                                          status.data_ptr(), s.cuda_stream))
     return status, out_len, consumed
+
+
+def frame_compress_many(settings, frames, outs, dictionary=None, stream=None):
+    """lzf_frame_compress_device_many: every input of `frames` (1-D uint8 CUDA tensors) compressed into an LZ4 frame in `outs`
+    (1-D uint8 CUDA tensors, their lengths are the capacities) with `settings` (an ffi.Settings whose `dictionary` is NULL; the
+    dictionary is the uint8 CUDA tensor `dictionary`).  Returns (status int32, out_len int64) as CUDA tensors, written in order on
+    `stream`; nothing is synchronised."""
+    n, ptrs, lens = _frame_args(frames)
+    assert len(outs) == n
+    dev = frames[0].device if n else torch.device("cuda", torch.cuda.current_device())
+    status = torch.empty(n, dtype=torch.int32, device=dev)         # (empty: the call writes every entry)
+    out_len = torch.empty(n, dtype=torch.int64, device=dev)
+    if n == 0:
+        return status, out_len
+    for t in outs:
+        assert t.dtype == torch.uint8 and t.is_cuda and t.dim() == 1 and t.is_contiguous(), "outs: 1-D contiguous uint8 CUDA tensors"
+    optr = (C.c_void_p * n)(*[t.data_ptr() for t in outs])
+    caps = (C.c_size_t * n)(*[t.numel() for t in outs])
+    dptr, dlen = None, 0
+    if dictionary is not None and dictionary.numel():
+        assert dictionary.dtype == torch.uint8 and dictionary.is_cuda and dictionary.is_contiguous()
+        dptr, dlen = dictionary.data_ptr(), dictionary.numel()
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    for t in (status, out_len):
+        t.record_stream(s)
+    ffi.check(ffi.lib().lzf_frame_compress_device_many(C.byref(settings), n, ptrs, lens, dptr, dlen, optr, caps, out_len.data_ptr(),
+                                                       status.data_ptr(), s.cuda_stream))
+    return status, out_len

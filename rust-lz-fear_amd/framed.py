@@ -175,6 +175,38 @@ class CompressionSettings:
                 raise FrameError(st[f])
         return [C.string_at(outs[f], olen[f]) for f in range(n)]
 
+    def compress_many_device(self, tensors, content_size=None, stream=None):
+        """`compress_many` for inputs that live on the device (1-D uint8 CUDA tensors), compressed on the device into device
+        memory (lzf_frame_compress_device_many); `content_size` goes into every header (compress_with_size_unchecked).
+        Outputs are sized with lzf_frame_compress_bound; the dictionary is uploaded.  Returns one uint8 CUDA tensor per input,
+        the frame's bytes, once `stream` (default: the current stream) has finished the call; raises FrameError like
+        `compress_many`."""
+        import torch
+        from . import device
+        tensors = list(tensors)
+        if not tensors:
+            return []
+        dev = tensors[0].device
+        s = self._struct(content_size)
+        s.dictionary = None                                 # (the device call takes the dictionary in device memory)
+        s.dictionary_len = 0
+        d_dict = None
+        if self._dictionary:
+            d_dict = torch.frombuffer(bytearray(self._dictionary), dtype=torch.uint8).to(dev)
+        L = ffi.lib()
+        outs = [torch.empty(L.lzf_frame_compress_bound(C.byref(s), t.numel()), dtype=torch.uint8, device=dev) for t in tensors]
+        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        if d_dict is not None:
+            st.wait_stream(torch.cuda.current_stream(dev))   # (the upload ran on the current stream)
+        with torch.cuda.stream(st):
+            status, out_len = device.frame_compress_many(s, tensors, outs, dictionary=d_dict, stream=st)
+        st.synchronize()
+        codes, lens = status.cpu().tolist(), out_len.cpu().tolist()
+        for c in codes:
+            if c != 0:
+                raise FrameError(c)
+        return [outs[f][:lens[f]] for f in range(len(tensors))]
+
     def compress_with_size(self, data):          # :147-157
         return self._run(data, len(data))
 
