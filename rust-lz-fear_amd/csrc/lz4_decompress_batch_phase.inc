@@ -3,11 +3,14 @@
 // Expects in scope: lane, in, out, prefix, len, plen, cap, limit, rb, ring, ring_a, RIDX(), ring_fill(), ring_flush(),
 // rdb(), rd4(), cstart, Tc (tokens listed for this chunk), o, safe, status, the constants RING, kSpanMax, kNearHist,
 // STAGE / cbuf_a / kCB (chunk staged in LDS or not) and the macro LZF_TOKEN_AT(i) = chunk offset of listed token i.
+// With LZF_FED_DECODE (the bitmap-fed kernel, lz4_decompress_feed_phase.inc) instead of rd4() and LZF_TOKEN_AT: toks (round
+// offsets, not yet verified), expect (where the chain's next token starts) and bail; the set-up then decodes each token once and
+// checks the chain's links before the batch writes anything (a broken link or UnexpectedEnd: bail, the loop ends).
             // =====================================================================
             // B. batches of up to 64 sequences: lane j owns token tidx + j
             // =====================================================================
             uint32_t tidx = 0;
-            if (LZF_DBG_SKIP & 1) { tidx = Tc; o += Tc; }
+            if (LZF_DBG_SKIP & 1) { tidx = Tc; o += Tc; }      // (LZF_FED_DECODE: no decode either, the chain stops after one round)
             while (tidx < Tc && status == LZF_OK) {
                 PHASE(0);
 #if defined(LZF_DBG_ROUNDS) && defined(LZF_DBG_ROUNDS_HERE)
@@ -19,6 +22,51 @@
                 // ---- re-read the token (decompress.rs:61-71), per lane
                 uint32_t L = 0, M = 0, src = 0;
                 bool has = false;
+#if defined(LZF_FED_DECODE)
+                // Each token is decoded here and nowhere else.  The common token (no 0xFF length byte, its match-length byte staged)
+                // without branches; the rest through the serial routine.  Lanes past nb_try decode lane 0's token again (masked off).
+                uint32_t next;                                     // where the token's successor starts (len: the last literals)
+                const uint32_t pos = toks[act0 ? tidx + lane : tidx];
+                const uint32_t tp = cstart + pos;
+                uint32_t w;                                        // token + first literal-length byte (pos < kRound: staged)
+                asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(w) : "v"(cbuf_a + pos) : "memory");
+                const uint32_t l0 = (w >> 4) & 15u, b1 = (w >> 8) & 255u, m0 = w & 15u;
+                const bool lx = l0 == 15u;
+                L = l0 + (lx ? b1 : 0u);
+                src = tp + (lx ? 2u : 1u);
+                const uint32_t q = src + L;                        // the offset (a missing extension byte reads as 0: q > len then)
+                has = q + 2u <= len;                               // :70 read_u16 fails: last literals
+                const bool mx = has && m0 == 15u;
+                const uint32_t r1 = q + 2u - cstart;               // the match-length byte
+                const uint32_t m1 = lds_ld8(cbuf_a + (r1 < kCB ? r1 : 0u));
+                M = has ? (mx ? 19u + m1 : m0 + 4u) : 0u;
+                next = has ? q + (mx ? 3u : 2u) : len;
+                bool bad = q > len || (mx && q + 2u >= len);       // :67 read_exact, read_lsic: UnexpectedEnd
+                const bool general = (lx && b1 == 255u) || (mx && (r1 >= kCB || m1 == 255u));
+                if (__ballot(act0 && general)) {
+                    if (general) {                                 // decompress.rs:61-71 without the copies, byte by byte
+                        uint32_t p = tp + 1u, b = 0;
+                        L = l0; M = 0; has = false; next = len; bad = false;
+                        if (lx) {
+                            do { if (p >= len) { bad = true; break; } b = rdb(p); ++p; L += b; if (L > kMaxPosB) L = kMaxPosB; } while (b == 255u);
+                        }
+                        src = p;
+                        if (!bad && len - p < L) bad = true;       // :67 read_exact
+                        p += L;
+                        if (!bad && len - p >= 2u) {
+                            has = true; p += 2u; M = m0;
+                            if (m0 == 15u) {
+                                do { if (p >= len) { bad = true; break; } b = rdb(p); ++p; M += b; if (M > kMaxPosB) M = kMaxPosB; } while (b == 255u);
+                            }
+                            M += 4u; next = p;
+                        }
+                    }
+                }
+                // the chain: lane 0's token is where the chain goes on, every other lane's token where the lane before it ends (the
+                // batch's last token is checked against its successor as lane 0 of the next batch or round)
+                if (tp != wave_prev(next, expect)) bad = true;
+                if (__ballot(act0 && bad)) { bail = true; break; }
+#else
 #ifdef LZF_TOKEN_WORD
                 // the parser already decoded the lengths of plain tokens (entry = offset | L << 16 | (M - 4) << 24)
                 bool decode = act0;
@@ -53,6 +101,7 @@
                         M += 4u;
                     }
                 }
+#endif
                 // ---- output positions
                 uint32_t tot = L + M; if (tot > kTotClamp || tot < L) tot = kTotClamp;
                 const uint32_t incl = wave_scan_add(act0 ? tot : 0u);
@@ -60,6 +109,9 @@
                 const uint32_t mo = lo + L;
                 const uint32_t c = first_lane(__ballot(act0 && incl > kSpanMax));
                 const uint32_t nb = c < nb_try ? c : nb_try;       // sequences in this batch
+#if defined(LZF_FED_DECODE)
+                expect = __builtin_amdgcn_readlane(next, nb ? nb - 1u : 0u);
+#endif
 
                 if (nb == 0u) {
                     // =============================================================

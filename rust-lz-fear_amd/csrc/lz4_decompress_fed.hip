@@ -2,8 +2,9 @@
 // with the PARSE taken out of the block's own wavefronts: the token positions of every block of the batch come from the hop
 // parse of the segmented pipeline (lzf_seg_parse_kernel + lzf_seg_seam_kernel: one bit per compressed byte, 3.8
 // wave-instructions per sequence against the 13.0 of the in-kernel region parse of lz4_decompress_paired.hip), and the kernel
-// here only FEEDS its copy stage from that map (lz4_decompress_feed_phase.inc: bit map -> token list, lengths pre-decoded, the
-// chain verified link by link) and runs the unchanged COPY stage (lz4_decompress_batch_phase.inc).
+// here only FEEDS its copy stage from that map (lz4_decompress_feed_phase.inc: bit map -> token list) and runs the COPY stage
+// (lz4_decompress_batch_phase.inc) with a set-up of its own (LZF_FED_DECODE: each listed token decoded once, the chain verified
+// link by link before a batch writes anything).
 //
 //   lzf_decompress_fed_kernel<RING, W, TOKCAP>        one wavefront per block: feed a round of 32 * W compressed bytes, copy it
 //   lzf_decompress_fed_pair_kernel<RING, W, TOKCAP>   two per block: wave 0 feeds round k + 1 while wave 1 copies round k
@@ -52,7 +53,7 @@ __global__ __launch_bounds__(64) void lzf_decompress_fed_kernel(fed_args a) {
     static_assert(kCB % 16 == 0, "the round is staged in 16-byte pieces");
     __shared__ __attribute__((aligned(16))) uint8_t ring[RING];
     __shared__ __attribute__((aligned(16))) uint8_t cbuf[kCB];
-    __shared__ __attribute__((aligned(16))) uint32_t toks[TOKCAP];
+    __shared__ __attribute__((aligned(16))) uint16_t toks[TOKCAP];
 
     const uint32_t lane = threadIdx.x;
     if (a.census) {
@@ -159,8 +160,8 @@ __global__ __launch_bounds__(64) void lzf_decompress_fed_kernel(fed_args a) {
         }
         uint32_t safe = o;   // out[0, safe) is visible to this wave's global loads
         if (o > 0) ring_fill(o > (uint32_t)RING ? o - RING : 0u, o);   // Vec content on entry (or what the other slot wrote) = history
-#ifdef LZF_DBG_PHASE_SEL   // analysis: cycles the wave spends in section LZF_DBG_PHASE_SEL (section i ends at PHASE(i); 0-5: the copy stage's, lz4_decompress_paired.hip;
-                           // 6 stage + bit map, 7 bit map -> list, 8 lengths + chain check) -> results[].reserved
+#ifdef LZF_DBG_PHASE_SEL   // analysis: cycles the wave spends in section LZF_DBG_PHASE_SEL (section i ends at PHASE(i); 0-5: the copy stage's, lz4_decompress_paired.hip,
+                           // 1 here with the tokens' decode and the chain check; 6 stage + bit map, 7 bit map -> list) -> results[].reserved
         long long ph_t = clock64(), ph_acc = 0;
 #define PHASE(i) do { const long long tn__ = clock64(); if ((i) == LZF_DBG_PHASE_SEL) ph_acc += tn__ - ph_t; ph_t = tn__; } while (0)
 #else
@@ -170,18 +171,16 @@ __global__ __launch_bounds__(64) void lzf_decompress_fed_kernel(fed_args a) {
             if (cstart >= piece_end) { parked = true; break; }      // the next piece's
             __syncthreads();                 // (one wave: orders the re-use of cbuf / toks between rounds)
 #include "lz4_decompress_feed_phase.inc"
-            if (bail) { bailed = true; break; }
             if (Tc) {
-#define LZF_TOKEN_AT(i) (toks[(i)] & 0xFFFFu)
-#define LZF_TOKEN_WORD(i) toks[(i)]
+#define LZF_FED_DECODE
 #ifdef LZF_FED_FAR_LATE
 #define LZF_FAR_LATE
 #endif
 #include "lz4_decompress_batch_phase.inc"
 #undef LZF_FAR_LATE
-#undef LZF_TOKEN_WORD
-#undef LZF_TOKEN_AT
+#undef LZF_FED_DECODE
             }
+            if (bail) { bailed = true; break; }
             // the next round the chain has a token in
             const uint32_t nx = expect & ~(kRound - 1u);
             cstart = nx > cstart ? nx : cstart + kRound;

@@ -1,24 +1,24 @@
 // lz4_decompress_feed_phase.inc — the FEED stage of the bitmap-fed decompress kernels (lz4_decompress_fed.hip): what the PARSE
-// stage of lz4_decompress_parse_phase.inc produces for a chunk — the token list of the chunk, lengths pre-decoded — taken from
-// the token bit map the hop parse of the segmented pipeline wrote for the whole batch (lzf_seg_parse_kernel + lzf_seg_seam_kernel,
+// stage of lz4_decompress_parse_phase.inc produces for a chunk — the token list of the chunk — taken from the token bit map the
+// hop parse of the segmented pipeline wrote for the whole batch (lzf_seg_parse_kernel + lzf_seg_seam_kernel,
 // lz4_decompress_seg.hip) instead of being worked out in the kernel.  Textual include inside the kernel's round loop.
 //
 // A ROUND is kRound = 32 * W bytes of compressed input at a kRound-aligned position (W bit-map words, one per lane).  Rounds
 // subdivide the 2 KiB tiles of the segmented pipeline, so a round lies inside ONE chunk's share of the bit map (kernels.h).
 //
 // Nothing of the bit map is trusted: the listed tokens are accepted only as a VERIFIED CHAIN.  The first token of the job
-// must sit at position 0, and every listed token's successor position — worked out here from the token's own bytes
-// (decompress.rs:61-71 without the copies) — must be the next listed token; the carry between rounds is `expect`.  By
-// induction the accepted tokens are exactly the tokens decompress_raw visits.  Anything else (a missing or an extra bit, a
-// token whose body leaves the input: UnexpectedEnd) ends the job for this kernel with `bail`: it is left to the pair kernel,
-// which decodes it from its first byte and reports the reference's status.
+// must sit at position 0, and every listed token must sit where its predecessor ends — worked out from the predecessor's own
+// bytes (decompress.rs:61-71 without the copies); the carry between batches and rounds is `expect`.  By induction the accepted
+// tokens are exactly the tokens decompress_raw visits.  The copy stage checks the links of a batch as it decodes the batch's
+// tokens (lz4_decompress_batch_phase.inc, LZF_FED_DECODE), before it writes anything of the batch; here only the list is made.
+// Anything else (a missing or an extra bit, a token whose body leaves the input: UnexpectedEnd) ends the job for this kernel
+// with `bail`: it is left to the pair kernel, which decodes it from its first byte and reports the reference's status.
 //
-// Expects in scope: lane, in, len, cstart (round start), cbuf / cbuf_a (kCB staged bytes), toks (uint32_t[TOKCAP]),
+// Expects in scope: lane, in, len, cstart (round start), cbuf / cbuf_a (kCB staged bytes), toks (uint16_t[TOKCAP]),
 // fed_bits / fed_vf (the job's rows of seg_ctx::bits / ::vfrom), expect (uniform), the constants W, TOKCAP, kRound, kCB.
-// Leaves: Tc (tokens listed for this round, 0 when the chain jumps over it), bail (uniform), expect (updated), and the
-// lambdas rdb / rd4 for the copy stage.  Token-list entry = round offset | L << 16 | (M - 4) << 24 with the encodings of
-// lz4_decompress_paired.hip (L = 255 / M - 4 = 255: the copier decodes the token itself; M - 4 = 254: last sequence).
-// (Three-byte entries — LDS is what limits the kernel's residency — were measured: 97.5 -> 110 ms per call, misaligned DS accesses.)
+// Leaves: Tc (tokens listed for this round, 0 when the chain jumps over it), bail (uniform), and the lambda rdb for the copy
+// stage.  Token-list entry = the token's offset in the round (< kRound), two aligned bytes.
+// (Three-byte entries of offset and pre-decoded lengths were measured: 97.5 -> 110 ms per call, misaligned DS accesses.)
             uint32_t Tc = 0;
             bool bail = false;
             // byte of the input at absolute position q >= cstart (LDS while staged; asm on purpose, see lz4_decompress_parse_phase.inc)
@@ -26,14 +26,6 @@
                 const uint32_t r = q - cstart;
                 if (r < kCB) return lds_ld8(cbuf_a + r);
                 return (uint32_t)in[q];
-            };
-            // 4 input bytes at q (missing bytes past the end read as 0)
-            auto rd4 = [&](uint32_t q) -> uint32_t {
-                const uint32_t r = q - cstart;
-                if (r + 4u <= kCB) { uint32_t v; asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(cbuf_a + r) : "memory"); return v; }
-                uint32_t v = 0;
-                for (uint32_t i = 0; i < 4u && q + i < len; ++i) v |= rdb(q + i) << (8u * i);
-                return v;
             };
             if (expect < cstart + kRound) {
                 // ---- F0. stage in[cstart, cstart + kCB) (zeros beyond the input) and fetch the round's words of the bit map
@@ -78,82 +70,5 @@
                 }
                 PHASE(7);
                 if (Tc == 0u && !bail) bail = true;                            // the chain enters this round but no token is marked in it
-                // ---- F2. lengths of the listed tokens, 64 at a time, and the chain check
-                // One token at p (p < len): position of the next token; false on UnexpectedEnd (decompress.rs:61-71 without the copies).
-                auto token_next = [&](uint32_t p, uint32_t& next) -> bool {
-                    const uint32_t w = rd4(p);
-                    const uint32_t tok = w & 255u;
-                    uint32_t q = p + 1u;
-                    uint32_t L = tok >> 4;
-                    if (L == 15u) {
-                        if (q >= len) return false;
-                        uint32_t b = (w >> 8) & 255u; ++q;
-                        L += b;
-                        while (b == 255u) {
-                            if (q >= len) return false;
-                            b = rdb(q); ++q;
-                            L += b; if (L > kMaxPosB) L = kMaxPosB;
-                        }
-                    }
-                    if (len - q < L) return false;                    // :67 read_exact
-                    q += L;
-                    if (len - q < 2u) { next = len; return true; }    // :70 read_u16 fails: last literals
-                    q += 2u;
-                    if ((tok & 15u) == 15u) {
-                        for (;;) {
-                            if (q >= len) return false;
-                            const uint32_t b = rdb(q); ++q;
-                            if (b != 255u) break;
-                        }
-                    }
-                    next = q;
-                    return true;
-                };
-                bool bad = false;
-                uint32_t last_next = expect;
-                for (uint32_t t0 = 0; t0 < Tc; t0 += kWave) {
-                    const uint32_t t = t0 + lane;
-                    if (t < Tc) {
-                        const uint32_t pos = toks[t] & 0xFFFFu;
-                        const uint32_t tp = cstart + pos;
-                        const uint32_t w = rd4(tp);
-                        const uint32_t l0 = (w >> 4) & 15u, b1 = (w >> 8) & 255u;
-                        uint32_t L = l0 + (l0 == 15u ? b1 : 0u);
-                        uint32_t q = tp + 1u + (l0 == 15u ? 1u : 0u) + L;        // where the offset is (plain literal length)
-                        uint32_t Lc = 255u, Mc = 255u, next = 0;
-                        bool general = l0 == 15u && b1 == 255u;
-                        if (!general) {
-                            if (q > len) bad = true;                          // :67 read_exact (a missing extension byte reads as 0: q is beyond len then too)
-                            else if (len - q < 2u) { next = len; Lc = L < 255u ? L : 255u; Mc = 254u; }      // :70 last literals
-                            else {
-                                const uint32_t m0 = w & 15u;
-                                next = q + 2u;
-                                Lc = L < 255u ? L : 255u;
-                                Mc = m0;
-                                if (m0 == 15u) {
-                                    if (q + 2u >= len) bad = true;            // read_lsic: UnexpectedEnd
-                                    else {
-                                        const uint32_t m1 = rdb(q + 2u);
-                                        if (m1 == 255u) general = true;
-                                        else { Mc = m1 < 239u ? 15u + m1 : 255u; next = q + 3u; }
-                                    }
-                                }
-                            }
-                        }
-                        if (general) {                                        // 0xFF length bytes: the serial routine, rare
-                            Lc = 255u; Mc = 255u;
-                            if (!token_next(tp, next)) bad = true;
-                        }
-                        if (Lc == 255u) Mc = 255u;                            // (the copier decodes such a token as a whole)
-                        // the chain: this token is where its predecessor ends, the next listed token where this one ends
-                        if (t == 0u && tp != expect) bad = true;
-                        if (t + 1u < Tc) { if (cstart + (toks[t + 1u] & 0xFFFFu) != next) bad = true; }
-                        else last_next = next;
-                        toks[t] = pos | (Lc << 16) | (Mc << 24);
-                    }
-                }
-                PHASE(8);
-                if (__ballot(bad)) bail = true;
-                if (!bail && Tc) expect = __builtin_amdgcn_readlane(last_next, (Tc - 1u) & 63u);
                 if (bail) Tc = 0;
             }
