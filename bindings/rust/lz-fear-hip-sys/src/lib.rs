@@ -97,6 +97,9 @@ extern "C" {
     pub fn lzf_copy_ranges(d_src: *const *const u8, d_dst: *const *mut u8, d_len: *const u64, n: u32, max_len: u64, hip_stream: *mut c_void) -> c_int;
     pub fn lzf_xxh32_batch_host(ptrs: *const *const u8, lens: *const u64, out: *mut u32, n: u32) -> c_int;
     pub fn lzf_decompress_batch_sized(d_jobs: *const lzf_decompress_job, d_results: *mut lzf_job_result, n_jobs: u32, max_input_len: u64, hip_stream: *mut c_void) -> c_int;
+    // decompress_raw's status and output.len() per job without decoding (prefix, out and out_cap of the jobs are never dereferenced)
+    pub fn lzf_decompressed_size_batch(d_jobs: *const lzf_decompress_job, d_results: *mut lzf_job_result, n_jobs: u32, max_input_len: u64, hip_stream: *mut c_void) -> c_int;
+    pub fn lzf_decompressed_size_batch_host(jobs: *const lzf_decompress_job, results: *mut lzf_job_result, n_jobs: u32) -> c_int;
     pub fn lzf_last_decompress_launch() -> *const c_char;
     pub fn lzf_last_compress_launch() -> *const c_char;
     // EncoderTable::replace / ::offset on host tables (src/raw/compress/mod.rs:64-74, :88-99)
@@ -118,6 +121,10 @@ extern "C" {
                                          out: *mut u8, out_cap: usize, out_len: *mut usize) -> c_int;
     pub fn lzf_frame_reader_finished(r: *const lzf_frame_reader) -> c_int;
     pub fn lzf_frame_reader_consumed(r: *const lzf_frame_reader) -> usize;
+    // frames in device memory: what lzf_frame_decompress_device_many would report (status, out_len, consumed), found without decoding;
+    // d_in / in_len are host arrays of device addresses, the results device arrays written in stream order (d_consumed may be null)
+    pub fn lzf_frame_decompressed_size_device(n_frames: u32, d_in: *const *const u8, in_len: *const usize, dict_len: usize,
+                                              d_out_len: *mut u64, d_consumed: *mut u64, d_status: *mut i32, hip_stream: *mut c_void) -> c_int;
     pub fn lzf_frame_release_scratch();
     pub fn lzf_frame_set_host_threads(n: u32);
     pub fn lzf_frame_set_memory_budget(bytes: usize);

@@ -212,6 +212,26 @@ int lzf_frame_decompress_device_many(uint32_t n_frames, const uint8_t* const* d_
                                      uint8_t* const* d_out, const size_t* out_cap,
                                      uint64_t* d_out_len, uint64_t* d_consumed, int32_t* d_status,
                                      void* hip_stream);
+/* Per frame: what lzf_frame_decompress_device_many would report, found without decoding — no output memory is needed, none is
+ * allocated.  Conventions of lzf_frame_decompress_device_many: d_in / in_len are HOST arrays, d_in[f] a DEVICE address; d_out_len,
+ * d_consumed (may be NULL), d_status are DEVICE arrays written in stream order.
+ *   d_out_len[f]   the out_len lzf_frame_decompress_device_many reports for the same bytes, a dictionary of dict_len bytes and
+ *                  unlimited out_cap[f] — also the partial length of a frame that stops early (block checksum, codec error, a
+ *                  block that decodes past block_maxsize, an empty block, truncated input).
+ *   d_status[f]    that call's status, with ONE exception: the content checksum is not verified (it needs the content), so a
+ *                  frame that would end in LZF_F_FRAME_CHECKSUM_FAIL reports LZF_OK.  Block checksums ARE verified: they
+ *                  decide where delivery stops, hence the size.  Never LZF_OUT_CAPACITY and never LZF_E_NO_MEMORY: a frame
+ *                  too large for the memory budget to decode still gets its size.
+ *   d_consumed[f]  that call's consumed.
+ * Only the dictionary's length matters (every block's decode may reach dict_len bytes behind its output); no dictionary bytes
+ * are passed.  The host waits twice, as for the decode (scan summary, block table), then enqueues block checksums
+ * (lzf_xxh32_batch), lzf_decompressed_size_batch over the blocks (linked frames in lock-step, history carried as a length) and
+ * the decode's stop rules, waits for its own upload of job lists and returns.  Scratch (jobs, results, 24 bytes per block) comes
+ * from the stream-ordered pool and does not depend on the decoded sizes. */
+int lzf_frame_decompressed_size_device(uint32_t n_frames, const uint8_t* const* d_in, const size_t* in_len,
+                                       size_t dict_len,
+                                       uint64_t* d_out_len, uint64_t* d_consumed, int32_t* d_status,
+                                       void* hip_stream);
 /* lzf_frame_compress_many for inputs that live in device memory, compressed into device memory: compress_internal
  * (src/framed/compress.rs:160-282) of every frame with the settings `s` (a host struct, shared by all frames as in
  * lzf_frame_compress_many: flags, dictionary id and content size of the header come from it).  s->dictionary must be NULL

@@ -145,6 +145,23 @@ int lzf_decompress_batch(const lzf_decompress_job* d_jobs, lzf_job_result* d_res
  * 64 KiB the pipeline is skipped.  Results are identical either way. */
 int lzf_decompress_batch_sized(const lzf_decompress_job* d_jobs, lzf_job_result* d_results,
                                uint32_t n_jobs, uint64_t max_input_len, void* hip_stream);
+/* raw::decompress_raw's status and output.len() for every job WITHOUT decoding it: no output memory is needed.  Every DecodeError
+ * depends on positions and lengths only, never on an output byte, so a pass that parses tokens and adds lengths answers exactly.
+ * Same job struct as the decoder (size, then decode, with one array).  Read: input, input_len, prefix_len, out_existing_len,
+ * output_limit.  `prefix`, `out` and `out_cap` are ignored and never dereferenced (NULL / 0 / dangling are fine).
+ *   status   what decompress_raw returns, i.e. what lzf_decompress_batch writes for the job whenever its out_cap is large enough:
+ *            LZF_OK or 1..4, never LZF_OUT_CAPACITY.  The first failing sequence in stream order wins; inside a sequence the
+ *            reference's order (UnexpectedEnd, then the limit :72-74, then the offset checks :83-89; literals are not
+ *            limit-checked).  LZF_CONTRACT where the decoder refuses the job: input_len, out_existing_len or prefix_len of 2 GiB - 256 or more.
+ *   out_len  on LZF_OK output.len(), out_existing_len included; unspecified on an error.  The decoder stops at 2 GiB of
+ *            output; this call does not: a block that decodes to more (LZ4 expands up to 255 x) gets its true 64-bit length.
+ *   reserved kilo-cycles, as for the decoder.
+ * max_input_len: as for lzf_decompress_batch_sized (~0 = unknown); it may size scratch only.  Scratch (a job counter, and 4
+ * bytes per job for the launch order of batches larger than the device holds at once) is independent of the decoded sizes and
+ * comes from the stream-ordered pool, freed in stream order.  The call enqueues its kernels and returns; no host wait.  One
+ * wavefront per job. */
+int lzf_decompressed_size_batch(const lzf_decompress_job* d_jobs, lzf_job_result* d_results,
+                                uint32_t n_jobs, uint64_t max_input_len, void* hip_stream);
 /* Diagnostic: the kernels the calling thread's last lzf_decompress_batch launched (the batch size picks them: the
  * segmented pipeline — one block decoded by many wavefronts — up to four blocks per CU, one workgroup per block beyond). */
 const char* lzf_last_decompress_launch(void);
@@ -204,6 +221,9 @@ int lzf_copy_ranges(const uint8_t* const* d_src, uint8_t* const* d_dst, const ui
  * place.  Used by the frame layer and by callers that have not moved their data to HBM. */
 int lzf_compress_batch_host(const lzf_compress_job* jobs, lzf_job_result* results, uint32_t n_jobs);
 int lzf_decompress_batch_host(const lzf_decompress_job* jobs, lzf_job_result* results, uint32_t n_jobs);
+/* lzf_decompressed_size_batch over host buffers: `input` of every job is a HOST pointer (staged to the device), `results` a
+ * host array; prefix, out and out_cap are ignored as above.  Synchronous. */
+int lzf_decompressed_size_batch_host(const lzf_decompress_job* jobs, lzf_job_result* results, uint32_t n_jobs);
 /* EncoderTable::replace on a HOST table — src/raw/compress/mod.rs:19-25 (trait), :64-71 (U32Table), :88-96 (U16Table):
  * swaps `pos + table.offset` into the slot of hash(input[pos..]) and returns the previous entry minus table.offset,
  * saturating at 0 (stale entries read as position 0).  hash = hash_for_u32 (:40-51: 5 bytes of an 8-byte little-endian

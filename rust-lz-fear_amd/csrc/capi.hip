@@ -721,6 +721,39 @@ int lzf_decompress_batch_sized(const lzf_decompress_job* d_jobs, lzf_job_result*
     return LZF_OK;
 }
 
+// decompress_raw's status and output.len() of every job, nothing decoded (lz4_decoded_size.hip).  One wavefront per job; as many
+// workgroups as the device holds at once draw jobs from a 4-byte counter; with more jobs than that, in the order of their input
+// lengths, longest first (4 bytes per job).  That is all the scratch there is.
+int lzf_decompressed_size_batch(const lzf_decompress_job* d_jobs, lzf_job_result* d_results, uint32_t n_jobs, uint64_t max_input_len, void* hip_stream) {
+    (void)max_input_len;               // (sizes no scratch today: the counter and the launch order depend on n_jobs alone)
+    if (n_jobs == 0) return LZF_OK;
+    if (!d_jobs || !d_results) { g_last_error = "lzf_decompressed_size_batch: NULL job/result array"; return LZF_E_INVALID; }
+    int rc = ensure_device();
+    if (rc < 0) return rc;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    keep_pool_memory();
+    constexpr auto k_size = lzf::lzf_decoded_size_kernel<48, 768>;
+    static thread_local int resident_for = -1; static thread_local uint32_t resident = 0;      // workgroups of the kernel per CU
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    if (dev != resident_for) {
+        int per = 0;
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_size, 64, 0));
+        resident = per > 0 ? (uint32_t)per : 1u; resident_for = dev;
+    }
+    const uint64_t room = (uint64_t)resident * cu_count();
+    const bool ordered = n_jobs > room;              // more jobs than resident waves: longest input first (4 bytes per job of scratch)
+    AsyncScratch ticket; ticket.st = st;
+    HIP_TRY(hipMallocAsync(&ticket.p, 256 + (ordered ? sizeof(uint32_t) * (size_t)n_jobs : 0u), st));
+    HIP_TRY(hipMemsetAsync(ticket.p, 0, 4, st));
+    uint32_t* const perm = ordered ? static_cast<uint32_t*>(ticket.p) + 64 : nullptr;
+    if (ordered) LAUNCH(lzf::lzf_order_by_input_len_kernel, dim3(1), dim3(1024), 0, st, d_jobs, perm, n_jobs);
+    const uint32_t grid = n_jobs < room ? n_jobs : (uint32_t)room;
+    LAUNCH(k_size, dim3(grid), dim3(64), 0, st, d_jobs, d_results, n_jobs, static_cast<uint32_t*>(ticket.p), (const uint32_t*)perm);
+    HIP_TRY(ticket.release());
+    return LZF_OK;
+}
+
 int lzf_table_seed_from_dictionary(lzf_u32_table* d_table, const uint8_t* d_dict, uint64_t dict_len, void* hip_stream) {
     if (!d_table || (!d_dict && dict_len)) { g_last_error = "lzf_table_seed_from_dictionary: NULL argument"; return LZF_E_INVALID; }
     if (dict_len > 0xFFFFFFFFull) { g_last_error = "dictionary beyond u32 positions (reference panics, mod.rs:67)"; return LZF_E_INVALID; }
@@ -942,6 +975,44 @@ int lzf_decompress_batch_host(const lzf_decompress_job* jobs, lzf_job_result* re
             down.push_back({out_off[i] + (size_t)jobs[i].out_existing_len, jobs[i].out + jobs[i].out_existing_len, (size_t)(n - jobs[i].out_existing_len)});
     }
     HIP_TRY(sg.download(down, out_total, dout, cs));
+    return LZF_OK;
+}
+
+int lzf_decompressed_size_batch_host(const lzf_decompress_job* jobs, lzf_job_result* results, uint32_t n_jobs) {
+    if (n_jobs == 0) return LZF_OK;
+    if (!jobs || !results) { g_last_error = "lzf_decompressed_size_batch_host: NULL argument"; return LZF_E_INVALID; }
+    int rc = ensure_device();
+    if (rc < 0) return rc;
+    using lzf_host::Seg; using lzf_host::Staging;
+    // the inputs go up; prefix, out and out_cap are not read by the size call and stay what they are (never dereferenced)
+    std::vector<size_t> in_off(n_jobs);
+    size_t in_total = 0;
+    uint64_t max_in = 0;
+    std::vector<Seg> up;
+    for (uint32_t i = 0; i < n_jobs; ++i) {
+        in_off[i] = in_total; in_total = align_up(in_total + jobs[i].input_len, 256);
+        if (jobs[i].input_len) {
+            if (!jobs[i].input) { g_last_error = "lzf_decompressed_size_batch_host: NULL input"; return LZF_E_INVALID; }
+            up.push_back({in_off[i], const_cast<uint8_t*>(jobs[i].input), (size_t)jobs[i].input_len});
+        }
+        if (jobs[i].input_len > max_in) max_in = jobs[i].input_len;
+    }
+    Staging& sg = Staging::get();
+    std::lock_guard<std::mutex> guard(sg.lock());
+    hipStream_t cs = sg.stream(0);
+    uint8_t* const din = static_cast<uint8_t*>(sg.device(0, in_total ? in_total : 256));
+    lzf_decompress_job* const djobs = static_cast<lzf_decompress_job*>(sg.device(3, sizeof(lzf_decompress_job) * n_jobs));
+    lzf_job_result* const dres = static_cast<lzf_job_result*>(sg.device(4, sizeof(lzf_job_result) * n_jobs));
+    if (!cs || !din || !djobs || !dres || !sg.pinned(in_total ? in_total : 256)) return fail_hip(hipErrorOutOfMemory, "staging memory");
+    std::vector<lzf_decompress_job> dj(jobs, jobs + n_jobs);
+    for (uint32_t i = 0; i < n_jobs; ++i) dj[i].input = din + in_off[i];
+    HIP_TRY(sg.upload(up, in_total, din));
+    HIP_TRY(hipMemcpyAsync(djobs, dj.data(), sizeof(lzf_decompress_job) * n_jobs, hipMemcpyHostToDevice, cs));
+    HIP_TRY(sg.join_copies(cs));
+    rc = lzf_decompressed_size_batch(djobs, dres, n_jobs, max_in, cs);
+    if (rc != LZF_OK) { (void)hipDeviceSynchronize(); return rc; }
+    HIP_TRY(hipMemcpyAsync(results, dres, sizeof(lzf_job_result) * n_jobs, hipMemcpyDeviceToHost, cs));
+    HIP_TRY(hipStreamSynchronize(cs));
     return LZF_OK;
 }
 

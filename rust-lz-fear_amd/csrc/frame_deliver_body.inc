@@ -1,0 +1,69 @@
+// frame_deliver_body.inc — the body of the frame layer's delivery kernels (frame_device.hip; textual include inside the kernel,
+// as the decompress kernels share their stages): lzf_frame_deliver_kernel with LZF_DELIVER_COUNT_ONLY 0, and the size query's
+// lzf_frame_size_deliver_kernel with LZF_DELIVER_COUNT_ONLY 1 — the same stops fix the same status, out_len and consumed, and
+// nothing else is written: no copy lists, no content checksum (the kernel has no r_ / l_ / h_ arrays).
+// Expects in scope: frames, blks, jobs, res, sums, d_status, d_out_len, d_consumed and, when not counting only, r_src / r_dst /
+// r_len, l_src / l_dst / l_len, h_len / h_check.
+    const DFrameDesc F = frames[blockIdx.x];
+    const uint32_t lane = threadIdx.x;
+    const bool linked = (F.flags & kLinked) != 0;
+    uint64_t w = 0, consumed = F.scan_consumed;
+    int st = LZF_OK;
+    bool stopped = false;
+    for (uint32_t base = 0; base < F.nb; base += 64u) {
+        const uint32_t i = base + lane;
+        const bool act = i < F.nb;
+        uint64_t n = 0, end_off = 0;
+        int code = 0;
+        const uint8_t* src = nullptr;
+        if (act) {
+            const DBlkDesc b = blks[F.blk0 + i];
+            end_off = b.end_off; src = b.src;
+            if (b.sum_idx != kNone && sums[b.sum_idx] != b.want_sum) code = LZF_F_BLOCK_CHECKSUM_FAIL;
+            else if (b.job != kNone) {
+                const lzf_job_result r = res[b.job];
+                if (r.status != LZF_OK) code = r.status;
+                else n = r.out_len - (linked ? jobs[b.job].out_existing_len : 0ull);   // linked: the chain step set the stream's length before the job
+            } else n = b.len;
+            if (!code && n > F.bmax) code = LZF_F_BLOCK_SIZE_OVERFLOW;
+        }
+        uint64_t incl = n;                                      // inclusive scan of n over the wave
+        for (uint32_t d = 1; d < 64u; d <<= 1) {
+            const uint64_t v = __shfl_up(incl, d, 64);
+            if (lane >= d) incl += v;
+        }
+        const uint64_t at = w + (incl - n);                     // where the block goes in the caller's output
+        const bool cap = act && !code && (at > F.out_cap || F.out_cap - at < n);
+        const bool zero = act && !code && !cap && n == 0;
+        const uint64_t stops = __ballot(act && (code || cap || zero));
+        const uint32_t first = stops ? (uint32_t)__builtin_ctzll(stops) : 64u;
+#if !LZF_DELIVER_COUNT_ONLY
+        if (!linked && act) {
+            const bool give = lane < first;
+            r_src[F.blk0 + i] = src; r_dst[F.blk0 + i] = F.dst + (give ? at : 0ull); r_len[F.blk0 + i] = give ? n : 0ull;
+        }
+#endif
+        if (stops) {
+            const int c = __shfl(code, (int)first, 64);
+            const int cp = __shfl((int)cap, (int)first, 64);
+            w = __shfl(at, (int)first, 64);
+            consumed = __shfl(end_off, (int)first, 64);
+            st = c ? c : cp ? LZF_OUT_CAPACITY : LZF_OK;
+            stopped = true;
+            break;
+        }
+        w += __shfl(incl, 63, 64);
+    }
+    if (lane != 0) return;
+#if !LZF_DELIVER_COUNT_ONLY
+    if (linked && F.nb) { l_src[F.link_idx] = F.stream; l_dst[F.link_idx] = F.dst; l_len[F.link_idx] = w; }
+#endif
+    d_out_len[F.frame] = w;
+    if (stopped) { d_status[F.frame] = st; d_consumed[F.frame] = consumed; }
+    else { d_status[F.frame] = F.scan_err; d_consumed[F.frame] = F.scan_consumed; }
+#if !LZF_DELIVER_COUNT_ONLY
+    if (F.hash_idx != kNone) {
+        const bool check = !stopped && (F.flags & kCheckContent);
+        h_len[F.hash_idx] = check ? w : 0ull; h_check[F.hash_idx] = check ? 1u : 0u;
+    }
+#endif

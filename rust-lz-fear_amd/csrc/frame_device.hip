@@ -24,6 +24,7 @@
 #include "lzf_frame_scan.h"
 #include "frame_jobs.h"
 #include "lzf_frame_layout.h"
+#include "lzf_chain_step.h"
 
 namespace {
 
@@ -125,63 +126,23 @@ __global__ __launch_bounds__(64) void lzf_frame_deliver_kernel(const DFrameDesc*
                                                                const uint8_t** __restrict__ l_src, uint8_t** __restrict__ l_dst, uint64_t* __restrict__ l_len,
                                                                uint64_t* __restrict__ h_len, uint32_t* __restrict__ h_check,
                                                                int32_t* __restrict__ d_status, uint64_t* __restrict__ d_out_len, uint64_t* __restrict__ d_consumed) {
-    const DFrameDesc F = frames[blockIdx.x];
-    const uint32_t lane = threadIdx.x;
-    const bool linked = (F.flags & kLinked) != 0;
-    uint64_t w = 0, consumed = F.scan_consumed;
-    int st = LZF_OK;
-    bool stopped = false;
-    for (uint32_t base = 0; base < F.nb; base += 64u) {
-        const uint32_t i = base + lane;
-        const bool act = i < F.nb;
-        uint64_t n = 0, end_off = 0;
-        int code = 0;
-        const uint8_t* src = nullptr;
-        if (act) {
-            const DBlkDesc b = blks[F.blk0 + i];
-            end_off = b.end_off; src = b.src;
-            if (b.sum_idx != kNone && sums[b.sum_idx] != b.want_sum) code = LZF_F_BLOCK_CHECKSUM_FAIL;
-            else if (b.job != kNone) {
-                const lzf_job_result r = res[b.job];
-                if (r.status != LZF_OK) code = r.status;
-                else n = r.out_len - (linked ? jobs[b.job].out_existing_len : 0ull);   // linked: the chain step set the stream's length before the job
-            } else n = b.len;
-            if (!code && n > F.bmax) code = LZF_F_BLOCK_SIZE_OVERFLOW;
-        }
-        uint64_t incl = n;                                      // inclusive scan of n over the wave
-        for (uint32_t d = 1; d < 64u; d <<= 1) {
-            const uint64_t v = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += v;
-        }
-        const uint64_t at = w + (incl - n);                     // where the block goes in the caller's output
-        const bool cap = act && !code && (at > F.out_cap || F.out_cap - at < n);
-        const bool zero = act && !code && !cap && n == 0;
-        const uint64_t stops = __ballot(act && (code || cap || zero));
-        const uint32_t first = stops ? (uint32_t)__builtin_ctzll(stops) : 64u;
-        if (!linked && act) {
-            const bool give = lane < first;
-            r_src[F.blk0 + i] = src; r_dst[F.blk0 + i] = F.dst + (give ? at : 0ull); r_len[F.blk0 + i] = give ? n : 0ull;
-        }
-        if (stops) {
-            const int c = __shfl(code, (int)first, 64);
-            const int cp = __shfl((int)cap, (int)first, 64);
-            w = __shfl(at, (int)first, 64);
-            consumed = __shfl(end_off, (int)first, 64);
-            st = c ? c : cp ? LZF_OUT_CAPACITY : LZF_OK;
-            stopped = true;
-            break;
-        }
-        w += __shfl(incl, 63, 64);
-    }
-    if (lane != 0) return;
-    if (linked && F.nb) { l_src[F.link_idx] = F.stream; l_dst[F.link_idx] = F.dst; l_len[F.link_idx] = w; }
-    d_out_len[F.frame] = w;
-    if (stopped) { d_status[F.frame] = st; d_consumed[F.frame] = consumed; }
-    else { d_status[F.frame] = F.scan_err; d_consumed[F.frame] = F.scan_consumed; }
-    if (F.hash_idx != kNone) {
-        const bool check = !stopped && (F.flags & kCheckContent);
-        h_len[F.hash_idx] = check ? w : 0ull; h_check[F.hash_idx] = check ? 1u : 0u;
-    }
+#define LZF_DELIVER_COUNT_ONLY 0
+#include "frame_deliver_body.inc"
+#undef LZF_DELIVER_COUNT_ONLY
+}
+// The size query's twins: delivery without the lists, and the chain step that carries the history as a length (lzf_chain_step.h).
+__global__ __launch_bounds__(64) void lzf_frame_size_deliver_kernel(const DFrameDesc* __restrict__ frames, const DBlkDesc* __restrict__ blks,
+                                                                    const lzf_decompress_job* __restrict__ jobs, const lzf_job_result* __restrict__ res,
+                                                                    const uint32_t* __restrict__ sums,
+                                                                    int32_t* __restrict__ d_status, uint64_t* __restrict__ d_out_len, uint64_t* __restrict__ d_consumed) {
+#define LZF_DELIVER_COUNT_ONLY 1
+#include "frame_deliver_body.inc"
+#undef LZF_DELIVER_COUNT_ONLY
+}
+__global__ __launch_bounds__(256) void lzf_chain_size_step_kernel(const lzf_chain_step* __restrict__ steps, lzf_chain_state* __restrict__ state,
+                                                                  uint32_t n, lzf_decompress_job* __restrict__ jobs,
+                                                                  const lzf_job_result* __restrict__ results) {
+    lzf::chain_step<true>(steps, state, n, jobs, results);
 }
 
 // decompress.rs:207-211: FrameChecksumFail where the EndMark was read, nothing stopped the frame and the hash differs
@@ -311,6 +272,28 @@ int scan_summaries(uint32_t n, const uint8_t* const* d_in, const size_t* in_len,
     return LZF_OK;
 }
 
+// Scan pass 2: the block table of every frame whose header parses, back on the host (the call's second wait).
+int scan_table(uint32_t n, hipStream_t st, PoolAlloc& args, const std::vector<FSum>& sum, std::vector<uint64_t>& blk0, std::vector<uint64_t>& cnt,
+               std::vector<TBlk>& table) {
+    blk0.assign(n, ~0ull); cnt.assign(n, 0);
+    uint64_t n_table = 0;
+    for (uint32_t f = 0; f < n; ++f) if (sum[f].flags & kLive) { blk0[f] = n_table; cnt[f] = sum[f].n_blocks; n_table += sum[f].n_blocks; }
+    if (n_table > 0x7FFFFFFFull) { (void)hipStreamSynchronize(st); return LZF_E_INVALID; }
+    table.resize((size_t)n_table);
+    if (n_table) {
+        std::vector<uint64_t> h(2 * (size_t)n);
+        memcpy(h.data(), blk0.data(), 8 * (size_t)n); memcpy(h.data() + n, cnt.data(), 8 * (size_t)n);
+        DEV_TRY(hipMemcpyAsync(args.at<uint64_t>(16 * (size_t)n), h.data(), 16 * (size_t)n, hipMemcpyHostToDevice, st));
+        PoolAlloc tab(st);
+        if (!tab.get(sizeof(TBlk) * (size_t)n_table)) { (void)hipStreamSynchronize(st); return LZF_E_HIP; }
+        KERNEL(lzf_frame_table_kernel, dim3((n + 63u) / 64u), dim3(64), 0, st, args.at<const uint8_t* const>(0), args.at<const uint64_t>(8 * (size_t)n),
+               args.at<const uint64_t>(16 * (size_t)n), args.at<const uint64_t>(24 * (size_t)n), n, tab.at<TBlk>(0));
+        DEV_TRY(hipMemcpyAsync(table.data(), tab.p, sizeof(TBlk) * (size_t)n_table, hipMemcpyDeviceToHost, st));
+        DEV_TRY(hipStreamSynchronize(st));
+    }
+    return LZF_OK;
+}
+
 // host image of the small arrays of every pass: one upload
 struct Image {
     std::vector<uint8_t> h;
@@ -366,22 +349,9 @@ int lzf_frame_decompress_device_many(uint32_t n_frames, const uint8_t* const* d_
     std::vector<FSum> sum;
     RC_TRY(scan_summaries(n, d_in, in_len, st, args, sum, d_status, d_out_len, d_consumed));
     // ---- scan pass 2: the block table of every frame whose header parses (wait 2)
-    std::vector<uint64_t> blk0(n, ~0ull), cnt(n, 0);
-    uint64_t n_table = 0;
-    for (uint32_t f = 0; f < n; ++f) if (sum[f].flags & kLive) { blk0[f] = n_table; cnt[f] = sum[f].n_blocks; n_table += sum[f].n_blocks; }
-    if (n_table > 0x7FFFFFFFull) { (void)hipStreamSynchronize(st); return LZF_E_INVALID; }
-    std::vector<TBlk> table((size_t)n_table);
-    if (n_table) {
-        std::vector<uint64_t> h(2 * (size_t)n);
-        memcpy(h.data(), blk0.data(), 8 * (size_t)n); memcpy(h.data() + n, cnt.data(), 8 * (size_t)n);
-        DEV_TRY(hipMemcpyAsync(args.at<uint64_t>(16 * (size_t)n), h.data(), 16 * (size_t)n, hipMemcpyHostToDevice, st));
-        PoolAlloc tab(st);
-        if (!tab.get(sizeof(TBlk) * (size_t)n_table)) { (void)hipStreamSynchronize(st); return LZF_E_HIP; }
-        KERNEL(lzf_frame_table_kernel, dim3((n + 63u) / 64u), dim3(64), 0, st, args.at<const uint8_t* const>(0), args.at<const uint64_t>(8 * (size_t)n),
-               args.at<const uint64_t>(16 * (size_t)n), args.at<const uint64_t>(24 * (size_t)n), n, tab.at<TBlk>(0));
-        DEV_TRY(hipMemcpyAsync(table.data(), tab.p, sizeof(TBlk) * (size_t)n_table, hipMemcpyDeviceToHost, st));
-        DEV_TRY(hipStreamSynchronize(st));
-    }
+    std::vector<uint64_t> blk0, cnt;
+    std::vector<TBlk> table;
+    RC_TRY(scan_table(n, st, args, sum, blk0, cnt, table));
     // ---- passes: as many frames as the memory budget holds, with the host driver's accounting (frame.cpp); a frame that does
     //      not fit alone gets LZF_E_NO_MEMORY
     std::vector<size_t> need(n, 0);
@@ -524,6 +494,102 @@ int lzf_frame_decompress_device_many(uint32_t n_frames, const uint8_t* const* d_
     }
     // the image left host memory long ago (it was first in the stream behind the table read-back); the kernels run on
     DEV_TRY(hipEventSynchronize(uploaded));
+    return LZF_OK;
+}
+
+// The decode call's scan, jobs and stop rules with lengths in the place of bytes: block checksums (they decide where delivery
+// stops), lzf_decompressed_size_batch for the decode (linked streams in lock-step, lzf_chain_size_step_kernel between the
+// steps), lzf_frame_size_deliver_kernel for the delivery.  No output slots, hence one pass whatever the memory budget is.
+int lzf_frame_decompressed_size_device(uint32_t n_frames, const uint8_t* const* d_in, const size_t* in_len, size_t dict_len,
+                                       uint64_t* d_out_len, uint64_t* d_consumed, int32_t* d_status, void* hip_stream) {
+    if (n_frames && (!d_in || !in_len || !d_out_len || !d_status)) return LZF_E_INVALID;
+    if (n_frames == 0) return LZF_OK;
+    if (usable_device() != LZF_OK) return LZF_E_NO_DEVICE;
+    const uint32_t n = n_frames;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    PoolAlloc own_consumed(st);                      // the kernels write `consumed` of every frame; a caller who passes NULL does not get it
+    if (!d_consumed) { if (!own_consumed.get(8 * (size_t)n)) return LZF_E_HIP; d_consumed = own_consumed.at<uint64_t>(0); }
+    // ---- scan: summaries (wait 1), block table (wait 2)
+    PoolAlloc args(st);
+    std::vector<FSum> sum;
+    RC_TRY(scan_summaries(n, d_in, in_len, st, args, sum, d_status, d_out_len, d_consumed));
+    std::vector<uint64_t> blk0, cnt;
+    std::vector<TBlk> table;
+    RC_TRY(scan_table(n, st, args, sum, blk0, cnt, table));
+    // ---- jobs (frame_jobs.h with sizes_only: the decode's lengths, no addresses) and descriptors
+    std::vector<lzf_frame_jobs::Frame> jf;
+    std::vector<uint32_t> jf_frame;
+    for (uint32_t f = 0; f < n; ++f) {
+        if (!(sum[f].flags & kLive)) continue;
+        jf.emplace_back();
+        lzf_frame_jobs::Frame& J = jf.back();
+        J.linked = !(sum[f].flags & lzf_scan::FL_INDEP); J.bmax = (size_t)sum[f].block_maxsize; J.consumed = (size_t)sum[f].consumed;
+        for (uint64_t k = 0; k < cnt[f]; ++k) {
+            const TBlk& t = table[blk0[f] + k];
+            J.blocks.push_back({d_in[f] + t.off, t.len & ~lzf_scan::INCOMPRESSIBLE, (t.len & lzf_scan::INCOMPRESSIBLE) == 0});
+        }
+        jf_frame.push_back(f);
+    }
+    if (jf.empty()) return LZF_OK;                   // every header failed: the scan kernel wrote the results
+    std::vector<lzf_frame_jobs::Frame*> jfl;
+    for (auto& J : jf) jfl.push_back(&J);
+    lzf_frame_jobs::Plan pl;
+    lzf_frame_jobs::layout(jfl, pl);
+    lzf_frame_jobs::build(jfl, pl, nullptr, nullptr, dict_len, true);
+    if (pl.jobs.size() > 0x7FFFFFFFull) { (void)hipStreamSynchronize(st); return LZF_E_INVALID; }
+    std::vector<DFrameDesc> fd; std::vector<DBlkDesc> bd;
+    std::vector<const uint8_t*> sptr; std::vector<uint64_t> slen;
+    for (size_t q = 0; q < jf.size(); ++q) {
+        const lzf_frame_jobs::Frame& J = jf[q];
+        const uint32_t f = jf_frame[q];
+        const FSum& S = sum[f];
+        DFrameDesc d;
+        memset(&d, 0, sizeof d);
+        d.out_cap = ~0ull; d.scan_consumed = S.consumed; d.bmax = J.bmax;              // unlimited room: never LZF_OUT_CAPACITY
+        d.blk0 = (uint32_t)bd.size(); d.nb = (uint32_t)J.blocks.size(); d.scan_err = S.status;
+        d.flags = (J.linked ? kLinked : 0u);
+        d.frame = f; d.hash_idx = kNone; d.link_idx = kNone;                          // the content checksum needs the content: not verified
+        const bool bsum = (S.flags & lzf_scan::FL_BLOCKSUM) != 0;
+        for (size_t i = 0; i < J.blocks.size(); ++i) {
+            const TBlk& t = table[blk0[f] + i];
+            DBlkDesc b;
+            b.src = nullptr;
+            b.end_off = t.end_off; b.job = J.job[i] == SIZE_MAX ? kNone : (uint32_t)J.job[i];
+            b.sum_idx = kNone; b.want_sum = t.want_sum; b.len = J.blocks[i].len;
+            if (bsum) { b.sum_idx = (uint32_t)sptr.size(); sptr.push_back(J.blocks[i].src); slen.push_back(J.blocks[i].len); }
+            bd.push_back(b);
+        }
+        fd.push_back(d);
+    }
+    Image img; Scratch scr;
+    const size_t i_jobs = img.add(pl.jobs.data(), sizeof(lzf_decompress_job) * pl.jobs.size());
+    const size_t i_steps = img.add(pl.csteps.data(), sizeof(lzf_chain_step) * pl.csteps.size());
+    const size_t i_sptr = img.add(sptr.data(), sizeof(void*) * sptr.size()), i_slen = img.add(slen.data(), 8 * slen.size());
+    const size_t i_frames = img.add(fd.data(), sizeof(DFrameDesc) * fd.size()), i_blks = img.add(bd.data(), sizeof(DBlkDesc) * bd.size());
+    const size_t s_res = scr.add(sizeof(lzf_job_result) * pl.jobs.size()), s_state = scr.add(sizeof(lzf_chain_state) * pl.n_chain);
+    const size_t s_sums = scr.add(4 * sptr.size());
+    const size_t img_bytes = img.h.size();
+    PoolAlloc meta(st);
+    if (!meta.get(img_bytes + scr.total)) { (void)hipStreamSynchronize(st); return LZF_E_HIP; }
+    hipEvent_t uploaded = nullptr;
+    DEV_TRY(hipEventCreateWithFlags(&uploaded, hipEventDisableTiming));
+    struct EventOwner { hipEvent_t e; ~EventOwner() { if (e) (void)hipEventDestroy(e); } } owner{uploaded};
+    if (img_bytes) DEV_TRY(hipMemcpyAsync(meta.p, img.h.data(), img_bytes, hipMemcpyHostToDevice, st));
+    DEV_TRY(hipEventRecord(uploaded, st));
+    if (scr.total) DEV_TRY(hipMemsetAsync(meta.at<uint8_t>(img_bytes), 0, scr.total, st));       // the chain states start at 0
+    lzf_decompress_job* const d_jobs = meta.at<lzf_decompress_job>(i_jobs);
+    lzf_job_result* const d_res = meta.at<lzf_job_result>(img_bytes + s_res);
+    uint32_t* const d_sums = meta.at<uint32_t>(img_bytes + s_sums);
+    if (!sptr.empty()) RC_TRY(lzf_xxh32_batch(meta.at<const uint8_t* const>(i_sptr), meta.at<const uint64_t>(i_slen), d_sums, (uint32_t)sptr.size(), st));
+    for (size_t k = 0; k < pl.n_steps; ++k) {
+        if (pl.n_chain) KERNEL(lzf_chain_size_step_kernel, dim3(pl.n_chain), dim3(256), 0, st, meta.at<const lzf_chain_step>(i_steps) + k * pl.n_chain,
+                               meta.at<lzf_chain_state>(img_bytes + s_state), pl.n_chain, d_jobs, (const lzf_job_result*)d_res);
+        const size_t a = pl.step_off[k], c = pl.step_off[k + 1] - a;
+        if (c) RC_TRY(lzf_decompressed_size_batch(d_jobs + a, d_res + a, (uint32_t)c, lzf_frame_jobs::step_max_input(pl, k), st));
+    }
+    KERNEL(lzf_frame_size_deliver_kernel, dim3((uint32_t)fd.size()), dim3(64), 0, st, meta.at<const DFrameDesc>(i_frames), meta.at<const DBlkDesc>(i_blks),
+           (const lzf_decompress_job*)d_jobs, (const lzf_job_result*)d_res, (const uint32_t*)d_sums, d_status, d_out_len, d_consumed);
+    DEV_TRY(hipEventSynchronize(uploaded));          // the image has left host memory; the kernels run on
     return LZF_OK;
 }
 

@@ -57,8 +57,10 @@ inline void layout(const std::vector<Frame*>& fs, Plan& p) {
     p.n_steps = max_steps > 1 ? max_steps : 1;
 }
 
-// Jobs and chain steps against the output allocation `dout` (p.out_total bytes) and the device dictionary.
-inline void build(const std::vector<Frame*>& fs, Plan& p, uint8_t* dout, const uint8_t* d_dict, size_t dict_len) {
+// Jobs and chain steps against the output allocation `dout` (p.out_total bytes) and the device dictionary.  With `sizes_only`
+// (lzf_frame_decompressed_size_device) there is neither: every length is set as for the decode, every output and dictionary
+// address stays NULL.
+inline void build(const std::vector<Frame*>& fs, Plan& p, uint8_t* dout, const uint8_t* d_dict, size_t dict_len, bool sizes_only = false) {
     p.jobs.clear(); p.step_off.clear();
     p.csteps.assign((size_t)p.n_chain * p.n_steps, lzf_chain_step{});
     for (size_t k = 0; k < p.n_steps; ++k) {
@@ -70,10 +72,10 @@ inline void build(const std::vector<Frame*>& fs, Plan& p, uint8_t* dout, const u
                 lzf_decompress_job j;
                 memset(&j, 0, sizeof j);
                 j.input = F.blocks[i].src; j.input_len = F.blocks[i].len;
-                j.prefix = d_dict; j.prefix_len = dict_len;                                       // :239-245
+                j.prefix = sizes_only ? nullptr : d_dict; j.prefix_len = dict_len;                // :239-245
                 const size_t lim = bmax;                                                          // :248
-                if (F.linked) { j.out = dout + F.out_off; j.out_cap = lim + F.blocks[i].len; j.output_limit = lim; }   // (patched per step)
-                else { j.out = dout + F.slot[i]; j.out_cap = block_out_bound(bmax, F.blocks[i].len) + F.blocks[i].len; j.output_limit = lim; }
+                if (F.linked) { j.out = sizes_only ? nullptr : dout + F.out_off; j.out_cap = lim + F.blocks[i].len; j.output_limit = lim; }   // (patched per step)
+                else { j.out = sizes_only ? nullptr : dout + F.slot[i]; j.out_cap = block_out_bound(bmax, F.blocks[i].len) + F.blocks[i].len; j.output_limit = lim; }
                 F.job[i] = p.jobs.size(); p.jobs.push_back(j);
             };
             if (!F.linked) { if (k == 0) for (size_t i = 0; i < nb; ++i) if (F.blocks[i].compressed) add_job(i); continue; }
@@ -81,7 +83,7 @@ inline void build(const std::vector<Frame*>& fs, Plan& p, uint8_t* dout, const u
             lzf_chain_step& st = p.csteps[k * p.n_chain + F.chain];
             memset(&st, 0, sizeof st);
             st.prev_job = (k > 0 && k - 1 < nb && F.blocks[k - 1].compressed) ? (uint32_t)F.job[k - 1] : UINT32_MAX;
-            st.job = UINT32_MAX; st.out = dout + F.out_off; st.block_maxsize = bmax;
+            st.job = UINT32_MAX; st.out = sizes_only ? nullptr : dout + F.out_off; st.block_maxsize = bmax;
             if (k < nb) {
                 if (F.blocks[k].compressed) { add_job(k); st.job = (uint32_t)F.job[k]; }
                 else { st.stored_len = F.blocks[k].len; st.stored_src = F.blocks[k].src; }

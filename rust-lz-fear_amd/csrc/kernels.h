@@ -33,6 +33,13 @@ LZF_DECOMPRESS_VARIANTS(LZF_EXT)
 // Producer / consumer pairs (lz4_decompress_paired.hip): X(name, ring bytes, region bytes, token-list entries).
 // (The launch bounds are repeated on the template DECLARATIONS of this header since round 4: hipcc takes a template kernel's
 //  attributes from its first declaration, and without them the instantiations were compiled for 1 024-thread workgroups.)
+// lz4_decoded_size.hip: decompress_raw's status and output.len() per job without decoding (one wavefront per job, jobs drawn from
+// *ticket, which starts at 0, in the order of perm when given); S = region bytes, TOKCAP = token-list entries of the shared parse
+// (48-byte regions, 3 KiB per parse: 71 / 52 / 49 ms for 16 / 32 / 48 on the bench's 11 769 blocks, profiles/decoded_size.txt)
+template <int S, int TOKCAP>
+__global__ __launch_bounds__(64) void lzf_decoded_size_kernel(const lzf_decompress_job* __restrict__ jobs, lzf_job_result* __restrict__ results,
+                                                              uint32_t n_jobs, uint32_t* __restrict__ ticket, const uint32_t* __restrict__ perm);
+extern template __global__ void lzf_decoded_size_kernel<48, 768>(const lzf_decompress_job*, lzf_job_result*, uint32_t, uint32_t*, const uint32_t*);
 struct seg_job;
 // done (optional): state array of the segmented pipeline; a job it finished (done[jid].done != 0) is skipped
 template <int RING, int S, int TOKCAP>

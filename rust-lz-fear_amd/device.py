@@ -46,6 +46,13 @@ def decompress_batch(d_jobs, d_res, n, stream=None, max_input_len=None):
         ffi.check(ffi.lib().lzf_decompress_batch_sized(d_jobs.data_ptr(), d_res.data_ptr(), n, int(max_input_len), _stream_ptr(stream)))
 
 
+def decompressed_size_batch(d_jobs, d_res, n, stream=None, max_input_len=None):
+    """lzf_decompressed_size_batch: status and output.len() of every decode job without decoding it.  The same job array as
+    decompress_batch; prefix, out and out_cap of the jobs are not looked at."""
+    bound = (1 << 64) - 1 if max_input_len is None else int(max_input_len)
+    ffi.check(ffi.lib().lzf_decompressed_size_batch(d_jobs.data_ptr(), d_res.data_ptr(), n, bound, _stream_ptr(stream)))
+
+
 def xxh32_batch(d_ptrs, d_lens, d_out, n, stream=None):
     ffi.check(ffi.lib().lzf_xxh32_batch(d_ptrs.data_ptr(), d_lens.data_ptr(), d_out.data_ptr(), n, _stream_ptr(stream)))
 
@@ -128,6 +135,25 @@ def frame_decompress_many(frames, outs, dictionary=None, stream=None):
         t.record_stream(s)
     ffi.check(ffi.lib().lzf_frame_decompress_device_many(n, ptrs, lens, dptr, dlen, optr, caps, out_len.data_ptr(), consumed.data_ptr(),
                                                          status.data_ptr(), s.cuda_stream))
+    return status, out_len, consumed
+
+
+def frame_decompressed_size(frames, dictionary_len=0, stream=None):
+    """lzf_frame_decompressed_size_device: per frame what frame_decompress_many would report with unlimited outputs and a
+    dictionary of `dictionary_len` bytes, found without decoding.  Returns (status int32, out_len int64, consumed int64) as CUDA
+    tensors, written in order on `stream`.  The content checksum is not verified (LZF_OK where the decode says FrameChecksumFail)."""
+    n, ptrs, lens = _frame_args(frames)
+    dev = frames[0].device if n else torch.device("cuda", torch.cuda.current_device())
+    status = torch.empty(n, dtype=torch.int32, device=dev)         # (empty: the call writes every entry)
+    out_len = torch.empty(n, dtype=torch.int64, device=dev)
+    consumed = torch.empty(n, dtype=torch.int64, device=dev)
+    if n == 0:
+        return status, out_len, consumed
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    for t in (status, out_len, consumed):
+        t.record_stream(s)
+    ffi.check(ffi.lib().lzf_frame_decompressed_size_device(n, ptrs, lens, int(dictionary_len), out_len.data_ptr(), consumed.data_ptr(),
+                                                           status.data_ptr(), s.cuda_stream))
     return status, out_len, consumed
 
 

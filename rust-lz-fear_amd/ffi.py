@@ -67,7 +67,7 @@ class FrameInfo(C.Structure):
 
 EXPORTS = [
     "lzf_abi_version", "lzf_last_error", "lzf_device_count", "lzf_compress_batch",
-    "lzf_decompress_batch", "lzf_decompress_batch_sized", "lzf_last_decompress_launch", "lzf_last_compress_launch", "lzf_table_replace_host", "lzf_table_offset_host", "lzf_compress2_host_writer", "lzf_table_seed_from_dictionary", "lzf_table_offset", "lzf_table_offset_batch",
+    "lzf_decompress_batch", "lzf_decompress_batch_sized", "lzf_decompressed_size_batch", "lzf_decompressed_size_batch_host", "lzf_last_decompress_launch", "lzf_last_compress_launch", "lzf_table_replace_host", "lzf_table_offset_host", "lzf_compress2_host_writer", "lzf_table_seed_from_dictionary", "lzf_table_offset", "lzf_table_offset_batch",
     "lzf_chain_decompress_step",
     "lzf_xxh32_batch", "lzf_copy_ranges", "lzf_compress_batch_host", "lzf_decompress_batch_host", "lzf_xxh32_batch_host",
 ]
@@ -80,7 +80,7 @@ FRAME_EXPORTS = [
     "lzf_frame_writer_new", "lzf_frame_writer_write", "lzf_frame_writer_finish", "lzf_frame_writer_sink_error", "lzf_frame_writer_free",
     "lzf_frame_get_stats", "lzf_frame_release_scratch", "lzf_frame_set_host_threads", "lzf_frame_set_memory_budget",
     "lzf_frame_set_pinned_limit", "lzf_frame_decompress_bound_device", "lzf_frame_decompress_device_many",
-    "lzf_frame_compress_device_many",
+    "lzf_frame_compress_device_many", "lzf_frame_decompressed_size_device",
 ]
 
 
@@ -122,6 +122,8 @@ def lib():
         L.lzf_compress_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         L.lzf_decompress_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.lzf_decompress_batch_sized.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p]
+        L.lzf_decompressed_size_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p]
+        L.lzf_decompressed_size_batch_host.argtypes = [C.POINTER(DecompressJob), C.POINTER(JobResult), C.c_uint32]
         L.lzf_table_seed_from_dictionary.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
         L.lzf_table_offset.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p]
         L.lzf_xxh32_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
@@ -176,6 +178,8 @@ def lib():
                                                        C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.lzf_frame_compress_device_many.argtypes = [C.POINTER(Settings), C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p,
                                                      C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.lzf_frame_decompressed_size_device.argtypes = [C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t,
+                                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -285,3 +289,25 @@ def decompress_blocks_host(items):
         out.append((res[i].status, C.string_at(keep[i][2], ln)))
         keep[i] = None                           # a block's staging buffer goes as soon as its bytes are out (streaming readers: memory = blocks in flight)
     return out
+
+
+def decompressed_sizes_host(items):
+    """items: list of dict(input=bytes, prefix_len=int, existing_len=int, limit=int).  Returns [(status, out_len)]: what
+    decompress_raw would return and its output.len(), found on the device without decoding (lzf_decompressed_size_batch_host)."""
+    n = len(items)
+    if n == 0:
+        return []
+    jobs = (DecompressJob * n)()
+    res = (JobResult * n)()
+    keep = []
+    for i, it in enumerate(items):
+        data = bytes(it["input"])
+        keep.append(data)
+        limit = it.get("limit")
+        jobs[i].input = _bytes_address(data)
+        jobs[i].input_len = len(data)
+        jobs[i].prefix_len = it.get("prefix_len", 0)
+        jobs[i].out_existing_len = it.get("existing_len", 0)
+        jobs[i].output_limit = (1 << 63) - 1 if limit is None else limit
+    check(lib().lzf_decompressed_size_batch_host(jobs, res, n))
+    return [(res[i].status, res[i].out_len) for i in range(n)]

@@ -265,9 +265,28 @@ def decompress_frames(frames, dictionary=b"", caps=None, with_consumed=False):
     return [(st[f], C.string_at(outs[f], olen[f])) for f in range(n)]
 
 
-def decompress_frames_device(frames, dictionary=None, caps=None, stream=None):
+def decompressed_sizes_device(frames, dictionary_len=0, stream=None):
+    """Per frame (1-D uint8 CUDA tensors) what `decompress_frames_device` would report, without decoding and without output memory
+    (lzf_frame_decompressed_size_device): [(status, size, consumed)] once `stream` has finished the call.  `dictionary_len`: the
+    length of the dictionary the frames will be decoded with.  The content checksum is not verified: a frame that would fail it
+    reports status 0."""
+    import torch
+    from . import device
+    frames = list(frames)
+    if not frames:
+        return []
+    s = stream if stream is not None else torch.cuda.current_stream(frames[0].device)
+    with torch.cuda.stream(s):
+        status, out_len, consumed = device.frame_decompressed_size(frames, dictionary_len=dictionary_len, stream=s)
+    s.synchronize()
+    return list(zip(status.cpu().tolist(), out_len.cpu().tolist(), consumed.cpu().tolist()))
+
+
+def decompress_frames_device(frames, dictionary=None, caps=None, stream=None, exact=False):
     """`decompress_frames` for frames that live on the device (1-D uint8 CUDA tensors), decoded on the device
-    (lzf_frame_decompress_device_many).  Outputs are sized from lzf_frame_decompress_bound_device when `caps` is None.
+    (lzf_frame_decompress_device_many).  Outputs are sized from lzf_frame_decompress_bound_device when `caps` is None — or, with
+    `exact=True`, from lzf_frame_decompressed_size_device: each output is as long as its frame decodes to, not as long as its
+    blocks could at worst.
     Returns [(status, out_tensor[:out_len], consumed)] once `stream` (default: the current stream) has finished the call."""
     import torch
     from . import device
@@ -276,7 +295,10 @@ def decompress_frames_device(frames, dictionary=None, caps=None, stream=None):
         return []
     dev = frames[0].device
     s = stream if stream is not None else torch.cuda.current_stream(dev)
-    if caps is None:
+    if caps is None and exact:
+        dlen = dictionary.numel() if dictionary is not None else 0
+        caps = [size for _, size, _ in decompressed_sizes_device(frames, dictionary_len=dlen, stream=s)]
+    elif caps is None:
         caps = device.frame_decompress_bound(frames, stream=s)
     outs = [torch.empty(int(c), dtype=torch.uint8, device=dev) for c in caps]
     with torch.cuda.stream(s):
