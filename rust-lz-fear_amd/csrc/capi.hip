@@ -404,9 +404,13 @@ inline uint64_t fed_min_hint() {
 constexpr uint64_t kFedMaxScratch = 24ull << 30;                     // bit maps of a call: 1 bit per compressed byte of the largest job x jobs (16 / 14 with the chunks' overlap)
 constexpr uint32_t kFedMaxJobs = 65535u;                             // (the chunk stage's grid has one row per job)
 // Workgroups of the kernel the current device holds at once, COUNTED (lz4_decompress_fed.hip, census mode): the occupancy query
-// does not know the LDS allocation granule (6 912 bytes take 7 680: 21 per CU, the query says 23), and a schedule with more slots
-// than residents runs its surplus slots after the others.  Once per device and process: one launch of ~0.1 ms and a 4-byte copy
-// (the one place a batch call waits for the device).
+// does not know the LDS allocation granule (an earlier build's 6 912 bytes took 7 680: 21 per CU where the query said 23; today's
+// 5 952 take 6 400: 25 per CU counted with the registers bounded to seven waves per SIMD), and a schedule with more slots than
+// residents runs its surplus slots after the others.  As built the REGISTERS limit the kernel: LZF_FED_WAVES (kernels.h) waves on
+// each of a CU's four SIMDs, 24 per CU counted.  Once per device and process: one launch of ~0.1 ms and a 4-byte copy (the one
+// place a batch call waits for the device).
+constexpr uint32_t kFedLdsAlloc = 6400u;                             // what the kernel's 5 952 bytes of LDS take
+constexpr uint32_t kFedWavesPerCu = 4u * (LZF_FED_WAVES > 0 ? (uint32_t)LZF_FED_WAVES : 5u);   // (no bound: 82 VGPRs, five per SIMD)
 struct FedGeometry { uint32_t slots, xcc_mask; };
 FedGeometry fed_geometry(hipStream_t st) {
     constexpr int kMaxDev = 64;
@@ -430,7 +434,10 @@ FedGeometry fed_geometry(hipStream_t st) {
         (void)hipFree(d);
     }
     (void)hipGetLastError();
-    if (!answer.slots) answer.slots = per_cu(7680u) * cu_count();    // (the census failed: the LDS granule's answer for 6 912 bytes; no XCD mask: jobs stay whole)
+    if (!answer.slots) {             // (the census failed: the smaller of the LDS's and the registers' answer; no XCD mask: jobs stay whole)
+        const uint32_t by_lds = per_cu(kFedLdsAlloc);
+        answer.slots = (by_lds < kFedWavesPerCu ? by_lds : kFedWavesPerCu) * cu_count();
+    }
 #ifdef LZF_ANALYSIS
     if (getenv("LZF_FED_VERBOSE")) fprintf(stderr, "[lzf] bitmap-fed kernel: %u workgroups resident at once (%u compute units), XCD mask 0x%x\n", answer.slots, cu_count(), answer.xcc_mask);
 #endif

@@ -139,8 +139,23 @@ struct fed_args {
 __global__ void lzf_fed_reset_kernel(fed_args a);
 // X(name, ring bytes, bit-map words per round, token-list entries)
 #define LZF_FED_VARIANTS(X) X(fed32, 4096, 32, 352)
+// The register allocation is held to six wavefronts per SIMD (80 VGPRs; unbounded the compiler takes 82, which the hardware rounds to
+// 88: five): the kernel waits on latency, and 24 resident wavefronts per CU instead of 20 took the call of bench.py from 93.3 to
+// 89.3 ms (profiles/fed_residency_prefetch.txt; seven per SIMD = the 25 per CU the LDS admits: 90.3).  The bound has to stand on
+// this declaration AND on the definition: written on the definition alone it is dropped without a word.
+// Analysis: -DLZF_DBG_FED_WAVES=n holds it to n instead (0: no bound, the kernel as it was before).
+#ifdef LZF_DBG_FED_WAVES
+#define LZF_FED_WAVES LZF_DBG_FED_WAVES
+#else
+#define LZF_FED_WAVES 6
+#endif
+#if LZF_FED_WAVES > 0
+#define LZF_FED_BOUNDS __launch_bounds__(64, LZF_FED_WAVES)
+#else
+#define LZF_FED_BOUNDS __launch_bounds__(64)
+#endif
 template <int RING, int W, int TOKCAP>
-__global__ __launch_bounds__(64) void lzf_decompress_fed_kernel(fed_args a);
+__global__ LZF_FED_BOUNDS void lzf_decompress_fed_kernel(fed_args a);
 #define LZF_EXTF(NAME, RG, W_, T) extern template __global__ void lzf_decompress_fed_kernel<RG, W_, T>(fed_args);
 LZF_FED_VARIANTS(LZF_EXTF)
 #undef LZF_EXTF

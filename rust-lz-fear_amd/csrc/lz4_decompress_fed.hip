@@ -7,7 +7,6 @@
 // link by link before a batch writes anything).
 //
 //   lzf_decompress_fed_kernel<RING, W, TOKCAP>        one wavefront per block: feed a round of 32 * W compressed bytes, copy it
-//   lzf_decompress_fed_pair_kernel<RING, W, TOKCAP>   two per block: wave 0 feeds round k + 1 while wave 1 copies round k
 //
 // Contract with the dispatch (capi.hip): a job is taken only when the plan stage found it eligible (sizes inside the bit map's
 // window) and the seam stage did not fail on it; a job is FINISHED here (results written, seg_job::done set) only when it decodes
@@ -41,7 +40,7 @@ __device__ __forceinline__ uint32_t xcc_id() {
 // writer's whole L2 (buffer_wbl2: measured ~150 us of the wave per hand-over, 98 -> 115 ms per call at 64 pieces per job).
 // ---------------------------------------------------------------------------------------------------------------------
 template <int RING, int W, int TOKCAP>
-__global__ __launch_bounds__(64) void lzf_decompress_fed_kernel(fed_args a) {
+__global__ LZF_FED_BOUNDS void lzf_decompress_fed_kernel(fed_args a) {      // (kernels.h: six waves per SIMD, bound on the declaration too)
     constexpr bool STAGE = true;
     constexpr uint32_t kMask = RING - 1;
     constexpr uint32_t kSpanMax = RING / 3;            // output bytes one batch may produce

@@ -29,6 +29,9 @@
             };
             if (expect < cstart + kRound) {
                 // ---- F0. stage in[cstart, cstart + kCB) (zeros beyond the input) and fetch the round's words of the bit map
+                // (Asking for the next round one round ahead — held in registers, or one load per 64 bytes to bring its lines into
+                // L2 — changed nothing at five or at six waves per SIMD: the other wavefronts already cover this round trip,
+                // profiles/fed_residency_prefetch.txt section 3.)
                 {
                     const uint32_t avail = len - cstart < kCB ? len - cstart : kCB;
                     cgu8* g = in + cstart;
