@@ -125,6 +125,16 @@ extern "C" {
     // d_in / in_len are host arrays of device addresses, the results device arrays written in stream order (d_consumed may be null)
     pub fn lzf_frame_decompressed_size_device(n_frames: u32, d_in: *const *const u8, in_len: *const usize, dict_len: usize,
                                               d_out_len: *mut u64, d_consumed: *mut u64, d_status: *mut i32, hip_stream: *mut c_void) -> c_int;
+    // streams of back-to-back frames in device memory (one contiguous output per stream; the pieces of an input packed back to back)
+    pub fn lzf_frame_stream_bound_device(n_streams: u32, d_in: *const *const u8, in_len: *const usize, out_bound: *mut usize,
+                                         hip_stream: *mut c_void) -> c_int;
+    pub fn lzf_frame_decompress_stream_device(n_streams: u32, d_in: *const *const u8, in_len: *const usize, d_dict: *const u8, dict_len: usize,
+                                              d_out: *const *mut u8, out_cap: *const usize, d_out_len: *mut u64, d_consumed: *mut u64,
+                                              d_status: *mut i32, d_n_frames: *mut u64, hip_stream: *mut c_void) -> c_int;
+    pub fn lzf_frame_compress_stream_bound(s: *const lzf_settings, frame_bytes: usize, in_len: usize) -> usize;
+    pub fn lzf_frame_compress_stream_device(s: *const lzf_settings, frame_bytes: usize, n_streams: u32, d_in: *const *const u8,
+                                            in_len: *const usize, d_dict: *const u8, dict_len: usize, d_out: *const *mut u8,
+                                            out_cap: *const usize, d_out_len: *mut u64, d_status: *mut i32, hip_stream: *mut c_void) -> c_int;
     pub fn lzf_frame_release_scratch();
     pub fn lzf_frame_set_host_threads(n: u32);
     pub fn lzf_frame_set_memory_budget(bytes: usize);

@@ -259,6 +259,65 @@ int lzf_frame_compress_device_many(const lzf_settings* s, uint32_t n_frames,
                                    uint8_t* const* d_out, const size_t* out_cap,
                                    uint64_t* d_out_len, int32_t* d_status, void* hip_stream);
 
+/* ---- streams of back-to-back frames in device memory ------------------------------------------------------------------
+ * "This also allows LZ4 frames to be concatenated back to back" (src/framed/mod.rs:6).  A content checksum is one serial XXH32
+ * chain per frame, so a payload written as one frame per few MiB has one short chain per frame, and the chains run in
+ * parallel.  A stream is in[0, len) holding zero or more frames back to back.  The rule is the loop a caller of
+ * lzf_frame_decompress writes with `consumed`:
+ *     pos = 0; out = 0; frames = 0; status = LZF_OK
+ *     while pos < len:
+ *         (st, n, c) = lzf_frame_decompress of in[pos, len) with the dictionary and the capacity out_cap - out
+ *         out += n; pos += c
+ *         if st != LZF_OK: status = st; break
+ *         if the frame did not end at its EndMark: break         (the Read adapter's stop at an empty block: LZF_OK)
+ *         frames += 1
+ * Hence: an empty stream is LZF_OK, 0, 0, 0; 1-3 trailing bytes are LZF_F_INPUT_ERROR with consumed = len; 4 or more trailing
+ * bytes that are not the magic (skippable and legacy frames too: the reference knows neither) are LZF_F_WRONG_MAGIC with
+ * consumed = pos + 4; a truncated last frame is LZF_F_INPUT_ERROR with the output of its complete blocks; LZF_OUT_CAPACITY
+ * comes at the block where the per-frame call with the remaining capacity reports it.
+ *
+ * lzf_frame_decompress_stream_device: conventions of lzf_frame_decompress_device_many.  d_in, in_len, d_out, out_cap are HOST
+ * arrays of n_streams entries holding DEVICE addresses; streams may alias each other, outputs must not overlap each other or
+ * any input.  d_out_len, d_consumed, d_status and d_n_frames (may be NULL; the frames that ended at their EndMark with LZF_OK)
+ * are DEVICE arrays of n_streams entries, written in stream order on `hip_stream`.  One dictionary per call.  A frame that does
+ * not fit the memory budget alone ends its stream with LZF_E_NO_MEMORY, the output of the frames before it stands.
+ * Nothing outside d_out[s][0, out_cap[s]) is ever written, and nothing beyond out_len[s] — with one exception: when a stream
+ * ends in LZF_F_FRAME_CHECKSUM_FAIL, the frames behind the failing one may have been placed already (the checksum is computed
+ * from the delivered bytes), and [out_len, out_cap) is unspecified.
+ * The host waits four times on the stream: for the frame count of every stream and for the frames' start offsets (the stream
+ * scan, one lane per stream, run twice), then, as lzf_frame_decompress_device_many, for the per-frame scan summary and the
+ * block table.  Where a frame goes is decided on the device: behind the decode a count-only delivery finds every frame's
+ * length, one wavefront per stream prefixes them and applies the rule above, then the delivery, the copy and the content
+ * checksums run as for single frames and a last kernel folds the frames' results into the streams'.  Frames go through in
+ * passes of the memory budget; a stream may span passes.  Not graph-capturable.
+ * lzf_frame_stream_bound_device: per stream the sum over the frames the walk finds of lzf_frame_decompress_bound_device's
+ * bound; with out_cap[s] at least that no stream ends in LZF_OUT_CAPACITY.  Synchronous (three waits). */
+int lzf_frame_stream_bound_device(uint32_t n_streams, const uint8_t* const* d_in, const size_t* in_len,
+                                  size_t* out_bound, void* hip_stream);
+int lzf_frame_decompress_stream_device(uint32_t n_streams, const uint8_t* const* d_in, const size_t* in_len,
+                                       const uint8_t* d_dict, size_t dict_len,
+                                       uint8_t* const* d_out, const size_t* out_cap,
+                                       uint64_t* d_out_len, uint64_t* d_consumed, int32_t* d_status, uint64_t* d_n_frames,
+                                       void* hip_stream);
+/* lzf_frame_compress_stream_device: input s becomes max(1, ceil(in_len[s] / frame_bytes)) frames, written back to back into
+ * d_out[s]: the bytes are the concatenation of lzf_frame_compress_many's output for each piece of frame_bytes bytes (the last
+ * one shorter) with the same settings and dictionary.  With s->has_content_size every frame's header carries its own piece's
+ * length; s->content_size is ignored.  frame_bytes == 0 or a non-NULL s->dictionary is LZF_E_INVALID.
+ * Conventions of lzf_frame_compress_device_many; d_out_len, d_status: DEVICE arrays of n_streams entries.  out_cap[s] below
+ * lzf_frame_compress_stream_bound (the sum of lzf_frame_compress_bound over the pieces; 0 for frame_bytes == 0) gives
+ * LZF_OUT_CAPACITY and no writes; a block status other than LZF_OK / LZF_OUTPUT_FULL (stored raw) fails the whole stream with
+ * the first such status in stream order, out_len 0 and no writes; otherwise nothing outside d_out[s][0, out_len) is written.
+ * The host plans everything from in_len[] and reads nothing back: between the compression and the assembly one kernel, one
+ * wavefront per stream, computes every frame's exact length from the job results, prefixes the lengths and sets every
+ * frame's destination and the stream's out_len and status.  A pass of the memory budget holds whole streams (a stream that
+ * is over the budget alone is a pass of its own), so that a failing stream has no byte written. */
+size_t lzf_frame_compress_stream_bound(const lzf_settings* s, size_t frame_bytes, size_t in_len);
+int lzf_frame_compress_stream_device(const lzf_settings* s, size_t frame_bytes, uint32_t n_streams,
+                                     const uint8_t* const* d_in, const size_t* in_len,
+                                     const uint8_t* d_dict, size_t dict_len,
+                                     uint8_t* const* d_out, const size_t* out_cap,
+                                     uint64_t* d_out_len, int32_t* d_status, void* hip_stream);
+
 /* Frame assembly from already-compressed blocks (what rank 0 does after the RCCL all-gather of a
  * block-sharded compression): writes header, then for every block
  * [u32 len | stored-bit][bytes][xxh32]?, then EndMark and content checksum.

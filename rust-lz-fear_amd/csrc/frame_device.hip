@@ -17,11 +17,20 @@
 // lzf_table_offset_batch between the steps), assembly (lzf_frame_assemble_kernel: header, length words, EndMark, status and
 // out_len, and the lists of the steps behind it, by lzf_frame_layout.h's rule), the payload copy (lzf_copy_ranges), block and
 // content checksums (lzf_xxh32_batch) and the checksum words (lzf_frame_patch_kernel).
+//
+// lzf_frame_decompress_stream_device / lzf_frame_compress_stream_device: streams of back-to-back frames.  Decode: the stream scan
+// (lzf_stream_scan_kernel, lzf_stream_walk.h, one lane per stream, two launches and two waits) lists the frames, which then go
+// through the decode above (decode_frames); per pass, behind the decode launches, the count-only delivery finds every frame's
+// length, lzf_stream_place_kernel gives every frame its place and the room left in its stream's output, and at the end
+// lzf_stream_fold_kernel folds the frames' results into the streams'.  Compress: the pieces of every input are frames of the
+// compress call above (compress_frames); lzf_stream_pack_kernel, in front of the assembly, puts each frame behind the one before.
 #include <hip/hip_runtime.h>
 #include <cstring>
+#include <map>
 #include <vector>
 #include "../../include/lzfear_frame.h"
 #include "lzf_frame_scan.h"
+#include "lzf_stream_walk.h"
 #include "frame_jobs.h"
 #include "lzf_frame_layout.h"
 #include "lzf_chain_step.h"
@@ -158,13 +167,121 @@ __global__ void lzf_frame_no_memory_kernel(uint32_t f, int32_t* d_status, uint64
     if (threadIdx.x == 0) { d_status[f] = LZF_E_NO_MEMORY; d_out_len[f] = 0; d_consumed[f] = 0; }
 }
 
+// ---- streams of back-to-back frames (lzf_stream_walk.h): the frames of a stream are consecutive frames of the call
+// Stream scan, one lane per stream.  Launch one counts the frames of every stream (the failing last one included); launch two,
+// with `starts`, lists where they begin: frame k of stream s at starts[first[s] + k].
+__global__ __launch_bounds__(64) void lzf_stream_scan_kernel(const uint8_t* const* __restrict__ in, const uint64_t* __restrict__ in_len, uint32_t n,
+                                                             uint64_t* __restrict__ counts, const uint64_t* __restrict__ first,
+                                                             uint64_t* __restrict__ starts) {
+    const uint32_t s = blockIdx.x * 64u + threadIdx.x;
+    if (s >= n) return;
+    if (!starts) { counts[s] = lzf_scan::walk_frames(in[s], in_len[s], [](uint64_t) {}).n_frames; return; }
+    uint64_t* const t = starts + first[s];
+    const uint64_t room = counts[s];    // what launch one found: never more entries than the host allocated
+    uint64_t k = 0;
+    lzf_scan::walk_frames(in[s], in_len[s], [&](uint64_t at) { if (k < room) t[k] = at; ++k; });
+}
+
+// the frames of one stream in one pass that have blocks to deliver: DFrameDesc [fd0, fd0 + nf) of the pass, in stream order
+struct SSeg { uint32_t stream, fd0, nf, pad; };
+// what a stream carries from pass to pass: the bytes placed so far, and whether a frame has ended it
+struct SState { uint64_t run; uint32_t stopped, pad; };
+
+__device__ inline uint64_t wave_sum(uint64_t v) {
+    for (int d = 32; d > 0; d >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, d, 64);
+    return v;
+}
+
+// Placement, one wavefront per stream and pass, 64 frames per round.  f_status / f_len / f_consumed hold what the count-only
+// delivery found for every frame with unlimited room.  The exclusive prefix of the lengths, behind the stream's running
+// length, is where each frame goes; the stream goes on behind a frame only if that frame ended at its EndMark with LZF_OK and
+// fits what is left of the stream's capacity.  The frame that ends the stream still gets its place and the room left — the
+// delivery behind this kernel stops it at the right block — every frame behind it gets no blocks at all.
+__global__ __launch_bounds__(64) void lzf_stream_place_kernel(const SSeg* __restrict__ segs, DFrameDesc* __restrict__ frames,
+                                                              const uint8_t** __restrict__ hptr,
+                                                              uint8_t* const* __restrict__ s_out, const uint64_t* __restrict__ s_cap,
+                                                              SState* __restrict__ sstate, const int32_t* __restrict__ f_status,
+                                                              const uint64_t* __restrict__ f_len, const uint64_t* __restrict__ f_consumed) {
+    const SSeg G = segs[blockIdx.x];
+    const uint32_t lane = threadIdx.x;
+    uint8_t* const out = s_out[G.stream];
+    const uint64_t cap = s_cap[G.stream];
+    uint64_t run = sstate[G.stream].run;
+    bool stopped = sstate[G.stream].stopped != 0;
+    for (uint32_t base = 0; base < G.nf; base += 64u) {
+        const uint32_t i = base + lane;
+        const bool act = i < G.nf;
+        DFrameDesc* const F = frames + G.fd0 + (act ? i : 0u);
+        uint64_t n = 0;
+        bool complete = false;
+        if (act) {
+            const uint32_t f = F->frame;
+            n = f_len[f];
+            complete = f_status[f] == LZF_OK && F->scan_err == LZF_OK && f_consumed[f] == F->scan_consumed;
+        }
+        uint64_t incl = n;                                      // inclusive scan of n over the wave
+        for (uint32_t d = 1; d < 64u; d <<= 1) {
+            const uint64_t v = __shfl_up(incl, d, 64);
+            if (lane >= d) incl += v;
+        }
+        const uint64_t at = run + (incl - n);                   // (at <= cap up to the first stop: every frame before it fits)
+        const bool fits = at <= cap && cap - at >= n;
+        const uint64_t stops = __ballot(act && !(complete && fits));
+        const uint32_t first = stops ? (uint32_t)__builtin_ctzll(stops) : 64u;
+        if (act) {
+            const bool live = !stopped && lane <= first;
+            uint8_t* const dst = live ? out + at : out;
+            F->dst = dst; F->out_cap = live ? cap - at : 0ull;
+            if (!live) { F->nb = 0u; F->flags &= ~kCheckContent; }
+            if (F->hash_idx != kNone) hptr[F->hash_idx] = dst;
+        }
+        if (stops) stopped = true;
+        else run += __shfl(incl, 63, 64);
+    }
+    if (lane == 0) { sstate[G.stream].run = run; sstate[G.stream].stopped = stopped ? 1u : 0u; }
+}
+
+// a frame that does not fit the memory budget alone ends its stream
+__global__ void lzf_stream_no_memory_kernel(uint32_t f, uint32_t stream, SState* sstate, int32_t* f_status, uint64_t* f_len, uint64_t* f_consumed) {
+    if (threadIdx.x == 0) { f_status[f] = LZF_E_NO_MEMORY; f_len[f] = 0; f_consumed[f] = 0; sstate[stream].stopped = 1u; }
+}
+
+// The stream rule over the frames' final results, one wavefront per stream: stream s is frames [first[s], first[s + 1]).  Every
+// frame up to and including the first one that does not end at its EndMark with LZF_OK (f_full: the frame's length up to
+// there, ~0 where the scan already failed) adds its output and its consumed bytes; the frames before it are the stream's frames.
+__global__ __launch_bounds__(64) void lzf_stream_fold_kernel(const uint64_t* __restrict__ first, const int32_t* __restrict__ f_status,
+                                                             const uint64_t* __restrict__ f_len, const uint64_t* __restrict__ f_consumed,
+                                                             const uint64_t* __restrict__ f_full,
+                                                             int32_t* __restrict__ d_status, uint64_t* __restrict__ d_out_len,
+                                                             uint64_t* __restrict__ d_consumed, uint64_t* __restrict__ d_n_frames) {
+    const uint32_t s = blockIdx.x, lane = threadIdx.x;
+    const uint64_t a = first[s], b = first[s + 1];
+    uint64_t out = 0, pos = 0, good = 0;
+    int st = LZF_OK;
+    for (uint64_t base = a; base < b; base += 64u) {
+        const uint64_t f = base + lane;
+        const bool act = f < b;
+        const uint64_t n = act ? f_len[f] : 0ull, c = act ? f_consumed[f] : 0ull;
+        const int code = act ? f_status[f] : LZF_OK;
+        const uint64_t stops = __ballot(act && (code != LZF_OK || c != f_full[f]));
+        const uint32_t stop_at = stops ? (uint32_t)__builtin_ctzll(stops) : 64u;
+        const bool take = act && lane <= stop_at;
+        out += wave_sum(take ? n : 0ull); pos += wave_sum(take ? c : 0ull);
+        good += (uint64_t)__popcll(__ballot(act && lane < stop_at));
+        if (stops) { st = __shfl(code, (int)stop_at, 64); break; }
+    }
+    if (lane != 0) return;
+    d_status[s] = st; d_out_len[s] = out; d_consumed[s] = pos;
+    if (d_n_frames) d_n_frames[s] = good;
+}
+
 // ---- compress: per frame and per block of a pass, for the assembly kernel
 struct CFrameDesc {
     uint8_t* dst;               // the caller's output
     uint32_t blk0, nb;          // the frame's blocks: CBlkDesc [blk0, blk0 + nb) of the pass, in block order
     int32_t status0;            // what the host decided: LZF_OK, LZF_OUT_CAPACITY or the block size's error (then nb = 0)
     uint32_t frame, hash_idx;   // hash_idx: the frame's content checksum in the pass, kNone: none
-    uint32_t pad;
+    uint32_t hdr_idx;           // the frame's header image (streams with a content size: one per piece length), 0: the call's one
 };
 static_assert(sizeof(CFrameDesc) == 32, "compress frame descriptor");
 struct CBlkDesc {
@@ -222,12 +339,61 @@ __global__ __launch_bounds__(64) void lzf_frame_assemble_kernel(const CFrameDesc
         }
         w += __shfl(incl, 63, 64);
     }
-    if (ok && lane < hdr_len) F.dst[lane] = hdr[lane];
+    if (ok && lane < hdr_len) F.dst[lane] = hdr[F.hdr_idx * lzf_layout::kMaxHeader + lane];
     if (ok && lane < 4u) F.dst[w + lane] = 0;                   // EndMark (:277)
     if (lane != 0) return;
     d_status[F.frame] = st;
     d_out_len[F.frame] = ok ? w + lzf_layout::tail_len(csum) : 0ull;
     if (F.hash_idx != kNone) c_at[F.hash_idx] = ok ? F.dst + w + 4 : nullptr;     // (:279-281)
+}
+
+// Streams of frames (lzf_frame_compress_stream_device): the frames of one stream, CFrameDesc [fd0, fd0 + nf) of the pass, go
+// back to back into the stream's output.  One wavefront per stream, a lane per frame, 64 frames per round: every frame's exact
+// length from its blocks' job results (lzf_frame_layout.h's rule, the assembly kernel's), a wave-wide exclusive scan of the
+// lengths for its place.  The first block status, in stream order, that is neither LZF_OK nor LZF_OUTPUT_FULL fails the whole
+// stream: every frame gets it as status0, and the assembly kernel behind writes no byte of them.
+struct CSeg { uint8_t* out; uint32_t fd0, nf, stream; int32_t status0; };
+__global__ __launch_bounds__(64) void lzf_stream_pack_kernel(const CSeg* __restrict__ segs, CFrameDesc* __restrict__ frames,
+                                                             const CBlkDesc* __restrict__ blks, const lzf_job_result* __restrict__ res,
+                                                             uint32_t hdr_len, uint32_t flags,
+                                                             int32_t* __restrict__ d_status, uint64_t* __restrict__ d_out_len) {
+    const CSeg G = segs[blockIdx.x];
+    const uint32_t lane = threadIdx.x;
+    const bool bsum = (flags & kBlockSums) != 0, csum = (flags & kContentSum) != 0;
+    int st = G.status0;
+    uint64_t w = 0;
+    if (st == LZF_OK) {
+        for (uint32_t base = 0; base < G.nf; base += 64u) {
+            const uint32_t i = base + lane;
+            const bool act = i < G.nf;
+            uint64_t len = 0;
+            int bad = LZF_OK;
+            if (act) {
+                const CFrameDesc F = frames[G.fd0 + i];
+                len = hdr_len + lzf_layout::tail_len(csum);
+                for (uint32_t k = 0; k < F.nb; ++k) {
+                    const CBlkDesc c = blks[F.blk0 + k];
+                    const lzf_job_result r = res[c.job];
+                    const lzf_layout::Block b = lzf_layout::block_of(r.status, r.out_len, c.raw_len);
+                    if (b.bad && bad == LZF_OK) bad = b.status;
+                    len += lzf_layout::block_span(b.len, bsum);
+                }
+            }
+            uint64_t incl = len;                                // inclusive scan of the frames' lengths over the wave
+            for (uint32_t d = 1; d < 64u; d <<= 1) {
+                const uint64_t v = __shfl_up(incl, d, 64);
+                if (lane >= d) incl += v;
+            }
+            if (act) frames[G.fd0 + i].dst = G.out + (w + incl - len);
+            const uint64_t bads = __ballot(act && bad != LZF_OK);
+            if (bads && st == LZF_OK) st = __shfl(bad, (int)__builtin_ctzll(bads), 64);
+            w += __shfl(incl, 63, 64);
+        }
+        if (st != LZF_OK) for (uint32_t i = lane; i < G.nf; i += 64u) frames[G.fd0 + i].status0 = st;
+    }
+    if (lane != 0) return;
+    d_status[G.stream] = st;
+    d_out_len[G.stream] = st == LZF_OK ? w : 0ull;
 }
 
 // the checksum words at their unaligned places (NULL: the frame failed)
@@ -313,37 +479,30 @@ struct Pass {
     uint32_t n_frames = 0, n_blks = 0, n_sums = 0, n_hash = 0, n_link = 0;
     uint64_t ind_max = 0, link_max = 0;
     // image offsets
-    size_t i_jobs = 0, i_steps = 0, i_sptr = 0, i_slen = 0, i_frames = 0, i_blks = 0, i_hptr = 0, i_hwant = 0, i_hframe = 0;
+    size_t i_jobs = 0, i_steps = 0, i_sptr = 0, i_slen = 0, i_frames = 0, i_blks = 0, i_hptr = 0, i_hwant = 0, i_hframe = 0, i_segs = 0;
+    uint32_t n_segs = 0;                // streams: the pass's SSeg list
     // scratch offsets
     size_t s_res = 0, s_state = 0, s_sums = 0, s_rsrc = 0, s_rdst = 0, s_rlen = 0, s_lsrc = 0, s_ldst = 0, s_llen = 0, s_hlen = 0, s_hcheck = 0, s_hout = 0;
 };
 
-}  // namespace
+// What makes the frames of a decode call the frames of streams (lzf_frame_decompress_stream_device): stream s is frames
+// [first[s], first[s + 1]) of the call and owns one output.  d_out / out_cap of decode_frames then hold, per frame, its stream's
+// output and capacity; d_status / d_out_len / d_consumed are per-frame scratch, the s_* arrays get the streams' results.
+struct StreamCtx {
+    uint32_t n_streams;
+    const uint64_t* first;              // host, n_streams + 1 entries
+    uint8_t* const* s_out;              // host, per stream: device address of its output
+    const size_t* s_cap;
+    SState* d_sstate;                   // device, zeroed: carried from pass to pass
+    int32_t* s_status; uint64_t* s_out_len; uint64_t* s_consumed; uint64_t* s_n_frames;    // device, per stream
+};
 
-extern "C" {
-
-int lzf_frame_decompress_bound_device(uint32_t n_frames, const uint8_t* const* d_in, const size_t* in_len, size_t* out_bound, void* hip_stream) {
-    if (n_frames && (!d_in || !in_len || !out_bound)) return LZF_E_INVALID;
-    if (usable_device() != LZF_OK) return LZF_E_NO_DEVICE;
-    if (n_frames == 0) return LZF_OK;
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    PoolAlloc args(st);
-    std::vector<FSum> sums;
-    RC_TRY(scan_summaries(n_frames, d_in, in_len, st, args, sums, nullptr, nullptr, nullptr));
-    for (uint32_t f = 0; f < n_frames; ++f) out_bound[f] = (sums[f].flags & kLive) ? (size_t)sums[f].out_bound : 0;
-    return LZF_OK;
-}
-
-int lzf_frame_decompress_device_many(uint32_t n_frames, const uint8_t* const* d_in, const size_t* in_len,
-                                     const uint8_t* d_dict, size_t dict_len,
-                                     uint8_t* const* d_out, const size_t* out_cap,
-                                     uint64_t* d_out_len, uint64_t* d_consumed, int32_t* d_status, void* hip_stream) {
-    if (n_frames && (!d_in || !in_len || !d_out || !out_cap || !d_out_len || !d_consumed || !d_status)) return LZF_E_INVALID;
-    if (!d_dict) dict_len = 0;
-    if (usable_device() != LZF_OK) return LZF_E_NO_DEVICE;
-    if (n_frames == 0) return LZF_OK;
-    const uint32_t n = n_frames;
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+// lzf_frame_decompress_device_many's work for n >= 1 frames on a usable device; with `sx` the frames are placed behind each
+// other in their streams' outputs on the device (count-only delivery, lzf_stream_place_kernel) and folded into per-stream
+// results at the end (lzf_stream_fold_kernel).
+int decode_frames(const uint32_t n, const uint8_t* const* d_in, const size_t* in_len, const uint8_t* d_dict, size_t dict_len,
+                  uint8_t* const* d_out, const size_t* out_cap, uint64_t* d_out_len, uint64_t* d_consumed, int32_t* d_status,
+                  hipStream_t st, const StreamCtx* sx) {
     // ---- scan pass 1: summaries (wait 1)
     PoolAlloc args(st);
     std::vector<FSum> sum;
@@ -358,6 +517,8 @@ int lzf_frame_decompress_device_many(uint32_t n_frames, const uint8_t* const* d_
     for (uint32_t f = 0; f < n; ++f) if (sum[f].flags & kLive) need[f] = (size_t)sum[f].consumed + 2 * (size_t)sum[f].need + 4096;
     size_t budget = lzf_frame_jobs::memory_budget();
     if (!budget) { size_t free_b = 0, total_b = 0; DEV_TRY(hipMemGetInfo(&free_b, &total_b)); budget = free_b / 2; }
+    std::vector<uint32_t> stream_of;                 // streams: the stream of every frame
+    if (sx) { stream_of.resize(n); for (uint32_t s = 0; s < sx->n_streams; ++s) for (uint64_t f = sx->first[s]; f < sx->first[s + 1]; ++f) stream_of[(size_t)f] = s; }
     std::vector<Pass> passes;
     for (uint32_t f0 = 0; f0 < n;) {
         size_t s = 0; uint32_t f1 = f0;
@@ -402,6 +563,7 @@ int lzf_frame_decompress_device_many(uint32_t n_frames, const uint8_t* const* d_
         std::vector<DFrameDesc> fd; std::vector<DBlkDesc> bd;
         std::vector<const uint8_t*> sptr; std::vector<uint64_t> slen;
         std::vector<const uint8_t*> hptr; std::vector<uint32_t> hwant, hframe;
+        std::vector<SSeg> segs;
         for (size_t q = 0; q < P.jf.size(); ++q) {
             const lzf_frame_jobs::Frame& J = P.jf[q];
             const uint32_t f = P.jf_frame[q];
@@ -409,7 +571,7 @@ int lzf_frame_decompress_device_many(uint32_t n_frames, const uint8_t* const* d_
             DFrameDesc d;
             memset(&d, 0, sizeof d);
             d.dst = d_out[f]; d.stream = J.linked && !J.blocks.empty() ? dslots + J.out_off : nullptr;
-            d.out_cap = out_cap[f]; d.scan_consumed = S.consumed; d.bmax = J.bmax;
+            d.out_cap = sx ? ~0ull : out_cap[f]; d.scan_consumed = S.consumed; d.bmax = J.bmax;
             d.blk0 = (uint32_t)bd.size(); d.nb = (uint32_t)J.blocks.size(); d.scan_err = S.status;
             d.flags = (J.linked ? kLinked : 0u);
             d.frame = f; d.hash_idx = kNone; d.link_idx = kNone;
@@ -432,8 +594,13 @@ int lzf_frame_decompress_device_many(uint32_t n_frames, const uint8_t* const* d_
                 if (bsum) { b.sum_idx = (uint32_t)sptr.size(); sptr.push_back(J.blocks[i].src); slen.push_back(J.blocks[i].len); }
                 bd.push_back(b);
             }
+            if (sx) {                       // (unlimited room above: for the count; lzf_stream_place_kernel sets dst and out_cap)
+                if (segs.empty() || segs.back().stream != stream_of[f]) segs.push_back(SSeg{stream_of[f], (uint32_t)fd.size(), 0u, 0u});
+                ++segs.back().nf;
+            }
             fd.push_back(d);
         }
+        P.n_segs = (uint32_t)segs.size(); P.i_segs = img.add(segs.data(), sizeof(SSeg) * segs.size());
         P.n_frames = (uint32_t)fd.size(); P.n_blks = (uint32_t)bd.size(); P.n_sums = (uint32_t)sptr.size(); P.n_hash = (uint32_t)hptr.size();
         P.i_jobs = img.add(P.plan.jobs.data(), sizeof(lzf_decompress_job) * P.plan.jobs.size());
         P.i_steps = img.add(P.plan.csteps.data(), sizeof(lzf_chain_step) * P.plan.csteps.size());
@@ -445,6 +612,13 @@ int lzf_frame_decompress_device_many(uint32_t n_frames, const uint8_t* const* d_
         P.s_rsrc = scr.add(8 * (size_t)P.n_blks); P.s_rdst = scr.add(8 * (size_t)P.n_blks); P.s_rlen = scr.add(8 * (size_t)P.n_blks);
         P.s_lsrc = scr.add(8 * (size_t)P.n_link); P.s_ldst = scr.add(8 * (size_t)P.n_link); P.s_llen = scr.add(8 * (size_t)P.n_link);
         P.s_hlen = scr.add(8 * (size_t)P.n_hash); P.s_hcheck = scr.add(4 * (size_t)P.n_hash); P.s_hout = scr.add(4 * (size_t)P.n_hash);
+    }
+    size_t i_sout = 0, i_scap = 0, i_first = 0, i_full = 0;
+    if (sx) {
+        std::vector<uint64_t> cap(sx->s_cap, sx->s_cap + sx->n_streams), full(n);
+        for (uint32_t f = 0; f < n; ++f) full[f] = (sum[f].flags & kLive) && sum[f].status == LZF_OK ? sum[f].consumed : ~0ull;
+        i_sout = img.add(sx->s_out, sizeof(void*) * sx->n_streams); i_scap = img.add(cap.data(), 8 * cap.size());
+        i_first = img.add(sx->first, 8 * ((size_t)sx->n_streams + 1)); i_full = img.add(full.data(), 8 * full.size());
     }
     // ---- one upload, then the kernels of every pass
     const size_t img_bytes = img.h.size();
@@ -459,6 +633,7 @@ int lzf_frame_decompress_device_many(uint32_t n_frames, const uint8_t* const* d_
     auto I = [&](size_t off) { return meta.at<uint8_t>(off); };
     auto S = [&](size_t off) { return meta.at<uint8_t>(img_bytes + off); };
     for (Pass& P : passes) {
+        if (P.no_memory && sx) { KERNEL(lzf_stream_no_memory_kernel, dim3(1), dim3(64), 0, st, P.f0, stream_of[P.f0], sx->d_sstate, d_status, d_out_len, d_consumed); continue; }
         if (P.no_memory) { KERNEL(lzf_frame_no_memory_kernel, dim3(1), dim3(64), 0, st, P.f0, d_status, d_out_len, d_consumed); continue; }
         if (!P.n_frames) continue;
         lzf_decompress_job* const d_jobs = reinterpret_cast<lzf_decompress_job*>(I(P.i_jobs));
@@ -471,6 +646,15 @@ int lzf_frame_decompress_device_many(uint32_t n_frames, const uint8_t* const* d_
                                                              reinterpret_cast<lzf_chain_state*>(S(P.s_state)), pl.n_chain, d_jobs, d_res, st));
             const size_t a = pl.step_off[k], c = pl.step_off[k + 1] - a;
             if (c) RC_TRY(lzf_decompress_batch_sized(d_jobs + a, d_res + a, (uint32_t)c, lzf_frame_jobs::step_max_input(pl, k), st));
+        }
+        if (sx) {                           // where every frame goes is known only now: count, then place
+            KERNEL(lzf_frame_size_deliver_kernel, dim3(P.n_frames), dim3(64), 0, st,
+                   reinterpret_cast<const DFrameDesc*>(I(P.i_frames)), reinterpret_cast<const DBlkDesc*>(I(P.i_blks)), (const lzf_decompress_job*)d_jobs,
+                   (const lzf_job_result*)d_res, (const uint32_t*)d_sums, d_status, d_out_len, d_consumed);
+            KERNEL(lzf_stream_place_kernel, dim3(P.n_segs), dim3(64), 0, st, reinterpret_cast<const SSeg*>(I(P.i_segs)),
+                   reinterpret_cast<DFrameDesc*>(I(P.i_frames)), reinterpret_cast<const uint8_t**>(I(P.i_hptr)),
+                   reinterpret_cast<uint8_t* const*>(I(i_sout)), reinterpret_cast<const uint64_t*>(I(i_scap)), sx->d_sstate,
+                   (const int32_t*)d_status, (const uint64_t*)d_out_len, (const uint64_t*)d_consumed);
         }
         KERNEL(lzf_frame_deliver_kernel, dim3(P.n_frames), dim3(64), 0, st,
                reinterpret_cast<const DFrameDesc*>(I(P.i_frames)), reinterpret_cast<const DBlkDesc*>(I(P.i_blks)), (const lzf_decompress_job*)d_jobs,
@@ -492,9 +676,138 @@ int lzf_frame_decompress_device_many(uint32_t n_frames, const uint8_t* const* d_
                    reinterpret_cast<const uint32_t*>(S(P.s_hcheck)), reinterpret_cast<const uint32_t*>(I(P.i_hframe)), P.n_hash, d_status);
         }
     }
+    if (sx)
+        KERNEL(lzf_stream_fold_kernel, dim3(sx->n_streams), dim3(64), 0, st, reinterpret_cast<const uint64_t*>(I(i_first)), (const int32_t*)d_status,
+               (const uint64_t*)d_out_len, (const uint64_t*)d_consumed, reinterpret_cast<const uint64_t*>(I(i_full)),
+               sx->s_status, sx->s_out_len, sx->s_consumed, sx->s_n_frames);
     // the image left host memory long ago (it was first in the stream behind the table read-back); the kernels run on
     DEV_TRY(hipEventSynchronize(uploaded));
     return LZF_OK;
+}
+
+// The stream scan of n streams: the frames of every stream back on the host (two waits: the counts, then the starts).  Stream s
+// is frames [first[s], first[s + 1]); frame f is f_in[f][0, f_len[f]): everything from its start to the end of its stream, as the
+// reader of the frame sees it.
+int scan_streams(uint32_t n, const uint8_t* const* d_in, const size_t* in_len, hipStream_t st, std::vector<uint64_t>& first,
+                 std::vector<const uint8_t*>& f_in, std::vector<size_t>& f_len) {
+    PoolAlloc args(st);
+    if (!args.get(32 * (size_t)n)) return LZF_E_HIP;             // [ptrs | lens | counts | first]
+    std::vector<uint64_t> h(2 * (size_t)n), counts(n);
+    for (uint32_t s = 0; s < n; ++s) { h[s] = reinterpret_cast<uintptr_t>(d_in[s]); h[n + s] = in_len[s]; }
+    DEV_TRY(hipMemcpyAsync(args.p, h.data(), 16 * (size_t)n, hipMemcpyHostToDevice, st));
+    KERNEL(lzf_stream_scan_kernel, dim3((n + 63u) / 64u), dim3(64), 0, st, args.at<const uint8_t* const>(0), args.at<const uint64_t>(8 * (size_t)n), n,
+           args.at<uint64_t>(16 * (size_t)n), (const uint64_t*)nullptr, (uint64_t*)nullptr);
+    DEV_TRY(hipMemcpyAsync(counts.data(), args.at<uint64_t>(16 * (size_t)n), 8 * (size_t)n, hipMemcpyDeviceToHost, st));
+    DEV_TRY(hipStreamSynchronize(st));
+    first.assign((size_t)n + 1, 0);
+    for (uint32_t s = 0; s < n; ++s) first[s + 1] = first[s] + counts[s];
+    const uint64_t total = first[n];
+    if (total > 0x7FFFFFFFull) return LZF_E_INVALID;
+    f_in.resize((size_t)total); f_len.resize((size_t)total);
+    if (!total) return LZF_OK;
+    std::vector<uint64_t> starts((size_t)total);
+    PoolAlloc tab(st);
+    if (!tab.get(8 * (size_t)total)) return LZF_E_HIP;
+    DEV_TRY(hipMemcpyAsync(args.at<uint64_t>(24 * (size_t)n), first.data(), 8 * (size_t)n, hipMemcpyHostToDevice, st));
+    KERNEL(lzf_stream_scan_kernel, dim3((n + 63u) / 64u), dim3(64), 0, st, args.at<const uint8_t* const>(0), args.at<const uint64_t>(8 * (size_t)n), n,
+           args.at<uint64_t>(16 * (size_t)n), args.at<const uint64_t>(24 * (size_t)n), tab.at<uint64_t>(0));
+    DEV_TRY(hipMemcpyAsync(starts.data(), tab.p, 8 * (size_t)total, hipMemcpyDeviceToHost, st));
+    DEV_TRY(hipStreamSynchronize(st));
+    for (uint32_t s = 0; s < n; ++s)
+        for (uint64_t f = first[s]; f < first[s + 1]; ++f) {
+            const uint64_t at = starts[(size_t)f] < in_len[s] ? starts[(size_t)f] : in_len[s];     // (never beyond the stream, whatever came back)
+            f_in[(size_t)f] = d_in[s] + at; f_len[(size_t)f] = in_len[s] - (size_t)at;
+        }
+    return LZF_OK;
+}
+
+// a call whose streams are all empty: LZF_OK, 0, 0, 0 for every stream
+__global__ __launch_bounds__(256) void lzf_stream_empty_kernel(uint32_t n, int32_t* d_status, uint64_t* d_out_len, uint64_t* d_consumed, uint64_t* d_n_frames) {
+    const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+    if (s >= n) return;
+    d_status[s] = LZF_OK; d_out_len[s] = 0; d_consumed[s] = 0;
+    if (d_n_frames) d_n_frames[s] = 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lzf_frame_decompress_bound_device(uint32_t n_frames, const uint8_t* const* d_in, const size_t* in_len, size_t* out_bound, void* hip_stream) {
+    if (n_frames && (!d_in || !in_len || !out_bound)) return LZF_E_INVALID;
+    if (usable_device() != LZF_OK) return LZF_E_NO_DEVICE;
+    if (n_frames == 0) return LZF_OK;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    PoolAlloc args(st);
+    std::vector<FSum> sums;
+    RC_TRY(scan_summaries(n_frames, d_in, in_len, st, args, sums, nullptr, nullptr, nullptr));
+    for (uint32_t f = 0; f < n_frames; ++f) out_bound[f] = (sums[f].flags & kLive) ? (size_t)sums[f].out_bound : 0;
+    return LZF_OK;
+}
+
+int lzf_frame_decompress_device_many(uint32_t n_frames, const uint8_t* const* d_in, const size_t* in_len,
+                                     const uint8_t* d_dict, size_t dict_len,
+                                     uint8_t* const* d_out, const size_t* out_cap,
+                                     uint64_t* d_out_len, uint64_t* d_consumed, int32_t* d_status, void* hip_stream) {
+    if (n_frames && (!d_in || !in_len || !d_out || !out_cap || !d_out_len || !d_consumed || !d_status)) return LZF_E_INVALID;
+    if (!d_dict) dict_len = 0;
+    if (usable_device() != LZF_OK) return LZF_E_NO_DEVICE;
+    if (n_frames == 0) return LZF_OK;
+    return decode_frames(n_frames, d_in, in_len, d_dict, dict_len, d_out, out_cap, d_out_len, d_consumed, d_status,
+                         static_cast<hipStream_t>(hip_stream), nullptr);
+}
+
+// Streams of back-to-back frames: the stream scan lists the frames (two waits), the frames then go through decode_frames (the
+// per-frame scan summary and the block table: two more waits) with their places found on the device.
+int lzf_frame_stream_bound_device(uint32_t n_streams, const uint8_t* const* d_in, const size_t* in_len, size_t* out_bound, void* hip_stream) {
+    if (n_streams && (!d_in || !in_len || !out_bound)) return LZF_E_INVALID;
+    if (usable_device() != LZF_OK) return LZF_E_NO_DEVICE;
+    if (n_streams == 0) return LZF_OK;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    std::vector<uint64_t> first;
+    std::vector<const uint8_t*> f_in; std::vector<size_t> f_len;
+    RC_TRY(scan_streams(n_streams, d_in, in_len, st, first, f_in, f_len));
+    std::vector<FSum> sums;
+    if (!f_in.empty()) {
+        PoolAlloc args(st);
+        RC_TRY(scan_summaries((uint32_t)f_in.size(), f_in.data(), f_len.data(), st, args, sums, nullptr, nullptr, nullptr));
+    }
+    for (uint32_t s = 0; s < n_streams; ++s) {
+        size_t b = 0;
+        for (uint64_t f = first[s]; f < first[s + 1]; ++f) if (sums[(size_t)f].flags & kLive) b += (size_t)sums[(size_t)f].out_bound;
+        out_bound[s] = b;
+    }
+    return LZF_OK;
+}
+
+int lzf_frame_decompress_stream_device(uint32_t n_streams, const uint8_t* const* d_in, const size_t* in_len,
+                                       const uint8_t* d_dict, size_t dict_len,
+                                       uint8_t* const* d_out, const size_t* out_cap,
+                                       uint64_t* d_out_len, uint64_t* d_consumed, int32_t* d_status, uint64_t* d_n_frames,
+                                       void* hip_stream) {
+    if (n_streams && (!d_in || !in_len || !d_out || !out_cap || !d_out_len || !d_consumed || !d_status)) return LZF_E_INVALID;
+    if (!d_dict) dict_len = 0;
+    if (usable_device() != LZF_OK) return LZF_E_NO_DEVICE;
+    if (n_streams == 0) return LZF_OK;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    std::vector<uint64_t> first;
+    std::vector<const uint8_t*> f_in; std::vector<size_t> f_len;
+    RC_TRY(scan_streams(n_streams, d_in, in_len, st, first, f_in, f_len));
+    const size_t n = f_in.size();
+    if (n == 0) {
+        KERNEL(lzf_stream_empty_kernel, dim3((n_streams + 255u) / 256u), dim3(256), 0, st, n_streams, d_status, d_out_len, d_consumed, d_n_frames);
+        return LZF_OK;
+    }
+    // per frame: its stream's output and capacity (the placement kernel cuts them up), and scratch for its own results
+    std::vector<uint8_t*> f_out(n); std::vector<size_t> f_cap(n);
+    for (uint32_t s = 0; s < n_streams; ++s) for (uint64_t f = first[s]; f < first[s + 1]; ++f) { f_out[(size_t)f] = d_out[s]; f_cap[(size_t)f] = out_cap[s]; }
+    const size_t o_len = up256(4 * n), o_cons = o_len + up256(8 * n), o_state = o_cons + up256(8 * n);
+    PoolAlloc per(st);
+    if (!per.get(o_state + sizeof(SState) * (size_t)n_streams)) return LZF_E_HIP;
+    DEV_TRY(hipMemsetAsync(per.at<uint8_t>(o_state), 0, sizeof(SState) * (size_t)n_streams, st));
+    const StreamCtx sx{n_streams, first.data(), d_out, out_cap, per.at<SState>(o_state), d_status, d_out_len, d_consumed, d_n_frames};
+    return decode_frames((uint32_t)n, f_in.data(), f_len.data(), d_dict, dict_len, f_out.data(), f_cap.data(),
+                         per.at<uint64_t>(o_len), per.at<uint64_t>(o_cons), per.at<int32_t>(0), st, &sx);
 }
 
 // The decode call's scan, jobs and stop rules with lengths in the place of bytes: block checksums (they decide where delivery
@@ -603,23 +916,27 @@ struct CPass {
     size_t slots = 0, copies = 0, tables = 0;                   // bytes of the pass's part of the work allocation
     std::vector<size_t> step_off;                               // linked: jobs of step k are [step_off[k], step_off[k + 1])
     size_t i_jobs = 0, i_tabptr = 0, i_adds = 0, i_cps = 0, i_cpd = 0, i_cpl = 0, i_tps = 0, i_tpd = 0, i_tpl = 0, i_frames = 0, i_blks = 0,
-           i_hptr = 0, i_hlen = 0;
+           i_hptr = 0, i_hlen = 0, i_segs = 0;
+    uint32_t n_segs = 0;                                        // streams: the pass's CSeg list
     size_t s_res = 0, s_rsrc = 0, s_rdst = 0, s_rlen = 0, s_at = 0, s_val = 0;
 };
 }  // namespace
 
-extern "C" {
+namespace {
+// What makes the frames of a compress call the pieces of streams (lzf_frame_compress_stream_device): stream q is frames
+// [first[q], first[q + 1]) of the call, written back to back.  d_out / out_cap of compress_frames then hold, per frame, its
+// stream's output and SIZE_MAX or 0 (the stream's capacity holds the bound, or not); d_status / d_out_len are per-frame scratch.
+struct CStreamCtx {
+    uint32_t n_streams;
+    const uint64_t* first;              // host, n_streams + 1 entries
+    int32_t* s_status; uint64_t* s_out_len;     // device, per stream
+};
 
-int lzf_frame_compress_device_many(const lzf_settings* s, uint32_t n_frames, const uint8_t* const* d_in, const size_t* in_len,
-                                   const uint8_t* d_dict, size_t dict_len, uint8_t* const* d_out, const size_t* out_cap,
-                                   uint64_t* d_out_len, int32_t* d_status, void* hip_stream) {
-    if (!s || (n_frames && (!d_in || !in_len || !d_out || !out_cap || !d_out_len || !d_status))) return LZF_E_INVALID;
-    if (s->dictionary) return LZF_E_INVALID;                    // the dictionary is d_dict: no host pointer may reach a kernel
-    if (!d_dict) dict_len = 0;
-    if (usable_device() != LZF_OK) return LZF_E_NO_DEVICE;
-    if (n_frames == 0) return LZF_OK;
-    const uint32_t n = n_frames;
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+// lzf_frame_compress_device_many's work for n >= 1 frames on a usable device; with `cx` the frames of a stream are packed
+// behind each other on the device (lzf_stream_pack_kernel in front of the assembly).
+int compress_frames(const lzf_settings* s, const uint32_t n, const uint8_t* const* d_in, const size_t* in_len,
+                    const uint8_t* d_dict, size_t dict_len, uint8_t* const* d_out, const size_t* out_cap,
+                    uint64_t* d_out_len, int32_t* d_status, hipStream_t st, const CStreamCtx* cx) {
     uint8_t bd = 0;
     const int bd_rc = lzf_layout::bd_new(s->block_size, &bd);  // compress.rs:183
     const size_t bs = bd_rc == LZF_OK ? (size_t)s->block_size : 1;
@@ -627,6 +944,22 @@ int lzf_frame_compress_device_many(const lzf_settings* s, uint32_t n_frames, con
     const bool per_block_prefix = indep && dict_len > 0;       // :218,:268 in_buffer = dict ++ block, for every block
     uint8_t hdr[lzf_layout::kMaxHeader] = {0};
     const uint32_t hdr_len = bd_rc == LZF_OK ? (uint32_t)lzf_layout::write_header(s, bd, hdr) : 0u;
+    // streams with a content size: every frame's header carries its own length, one header image per distinct length
+    std::vector<uint8_t> hdrs; std::vector<uint32_t> hdr_idx;
+    if (cx && s->has_content_size && bd_rc == LZF_OK) {
+        std::map<size_t, uint32_t> seen;
+        hdr_idx.resize(n);
+        for (uint32_t f = 0; f < n; ++f) {
+            auto it = seen.find(in_len[f]);
+            if (it == seen.end()) {
+                it = seen.emplace(in_len[f], (uint32_t)seen.size()).first;
+                lzf_settings own = *s; own.content_size = in_len[f];
+                hdrs.resize(hdrs.size() + lzf_layout::kMaxHeader, 0);
+                lzf_layout::write_header(&own, bd, hdrs.data() + (size_t)it->second * lzf_layout::kMaxHeader);
+            }
+            hdr_idx[f] = it->second;
+        }
+    }
     // ---- per frame: the host driver's status up front, the blocks and the scratch they need
     std::vector<int32_t> status0(n);
     std::vector<size_t> nb(n, 0), need(n, 0);
@@ -644,9 +977,17 @@ int lzf_frame_compress_device_many(const lzf_settings* s, uint32_t n_frames, con
     size_t budget = lzf_frame_jobs::memory_budget();
     if (!budget) { size_t free_b = 0, total_b = 0; DEV_TRY(hipMemGetInfo(&free_b, &total_b)); budget = free_b / 2; }
     std::vector<CPass> passes;
+    std::vector<uint32_t> stream_of;                            // streams: the stream of every frame; a pass holds whole streams
+    if (cx) { stream_of.resize(n); for (uint32_t q = 0; q < cx->n_streams; ++q) for (uint64_t f = cx->first[q]; f < cx->first[q + 1]; ++f) stream_of[(size_t)f] = q; }
     for (uint32_t f0 = 0; f0 < n;) {
         size_t sum = 0; uint32_t f1 = f0;
-        while (f1 < n && (f1 == f0 || sum + need[f1] <= budget)) { sum += need[f1]; ++f1; }
+        while (f1 < n) {
+            const uint32_t e = cx ? (uint32_t)cx->first[stream_of[f1] + 1] : f1 + 1;
+            size_t add = 0;
+            for (uint32_t f = f1; f < e; ++f) add += need[f];
+            if (f1 != f0 && sum + add > budget) break;
+            sum += add; f1 = e;
+        }
         CPass P; P.f0 = f0; P.f1 = f1;
         passes.push_back(std::move(P));
         f0 = f1;
@@ -674,7 +1015,7 @@ int lzf_frame_compress_device_many(const lzf_settings* s, uint32_t n_frames, con
     }
     // ---- jobs, copies and descriptors of every pass into one image
     Image img; Scratch scr;
-    const size_t i_hdr = img.add(hdr, sizeof hdr);
+    const size_t i_hdr = hdrs.empty() ? img.add(hdr, sizeof hdr) : img.add(hdrs.data(), hdrs.size());
     for (CPass& P : passes) {
         uint8_t* const dslots = work.at<uint8_t>(0);
         uint8_t* const dcopies = work.at<uint8_t>(up256(P.slots));
@@ -683,6 +1024,7 @@ int lzf_frame_compress_device_many(const lzf_settings* s, uint32_t n_frames, con
         std::vector<void*> tabptr; std::vector<uint64_t> adds;
         std::vector<const uint8_t*> cps, tps, hptr; std::vector<uint8_t*> cpd, tpd; std::vector<uint64_t> cpl, tpl, hlen;
         std::vector<CFrameDesc> fd; std::vector<CBlkDesc> bdesc(P.n_jobs);
+        std::vector<CSeg> segs;
         std::vector<std::vector<uint32_t>> frame_job(P.f1 - P.f0);
         size_t slot = 0, copy = 0;
         uint32_t linked = 0;
@@ -737,8 +1079,14 @@ int lzf_frame_compress_device_many(const lzf_settings* s, uint32_t n_frames, con
             if (csum && status0[f] == LZF_OK) {                 // (an empty input: no bytes to read, any valid address)
                 d.hash_idx = (uint32_t)hptr.size(); hptr.push_back(in_len[f] ? d_in[f] : d_out[f]); hlen.push_back(in_len[f]);
             }
+            if (cx) {                                           // (dst: lzf_stream_pack_kernel puts the frame behind the one before it)
+                if (!hdr_idx.empty()) d.hdr_idx = hdr_idx[f];
+                if (segs.empty() || segs.back().stream != stream_of[f]) segs.push_back(CSeg{d_out[f], (uint32_t)fd.size(), 0u, stream_of[f], status0[f]});
+                ++segs.back().nf;
+            }
             fd.push_back(d);
         }
+        P.n_segs = (uint32_t)segs.size(); P.i_segs = img.add(segs.data(), sizeof(CSeg) * segs.size());
         P.n_copies = (uint32_t)cps.size(); P.n_hash = (uint32_t)hptr.size(); P.n_frames = (uint32_t)fd.size();
         P.i_jobs = img.add(jobs.data(), sizeof(lzf_compress_job) * jobs.size());
         P.i_tabptr = img.add(tabptr.data(), sizeof(void*) * tabptr.size()); P.i_adds = img.add(adds.data(), 8 * adds.size());
@@ -787,6 +1135,10 @@ int lzf_frame_compress_device_many(const lzf_settings* s, uint32_t n_frames, con
         const size_t n_sums = bsum ? (size_t)P.n_jobs : 0;
         uint8_t** const at = reinterpret_cast<uint8_t**>(S(P.s_at));
         uint32_t* const val = reinterpret_cast<uint32_t*>(S(P.s_val));
+        if (cx)
+            KERNEL(lzf_stream_pack_kernel, dim3(P.n_segs), dim3(64), 0, st, reinterpret_cast<const CSeg*>(I(P.i_segs)),
+                   reinterpret_cast<CFrameDesc*>(I(P.i_frames)), reinterpret_cast<const CBlkDesc*>(I(P.i_blks)), (const lzf_job_result*)res,
+                   hdr_len, flags, cx->s_status, cx->s_out_len);
         KERNEL(lzf_frame_assemble_kernel, dim3(P.n_frames), dim3(64), 0, st,
                reinterpret_cast<const CFrameDesc*>(I(P.i_frames)), reinterpret_cast<const CBlkDesc*>(I(P.i_blks)), (const lzf_job_result*)res,
                (const uint8_t*)I(i_hdr), hdr_len, flags,
@@ -804,6 +1156,58 @@ int lzf_frame_compress_device_many(const lzf_settings* s, uint32_t n_frames, con
     }
     DEV_TRY(hipEventSynchronize(uploaded));                     // the image has left host memory; the launches run on
     return LZF_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int lzf_frame_compress_device_many(const lzf_settings* s, uint32_t n_frames, const uint8_t* const* d_in, const size_t* in_len,
+                                   const uint8_t* d_dict, size_t dict_len, uint8_t* const* d_out, const size_t* out_cap,
+                                   uint64_t* d_out_len, int32_t* d_status, void* hip_stream) {
+    if (!s || (n_frames && (!d_in || !in_len || !d_out || !out_cap || !d_out_len || !d_status))) return LZF_E_INVALID;
+    if (s->dictionary) return LZF_E_INVALID;                    // the dictionary is d_dict: no host pointer may reach a kernel
+    if (!d_dict) dict_len = 0;
+    if (usable_device() != LZF_OK) return LZF_E_NO_DEVICE;
+    if (n_frames == 0) return LZF_OK;
+    return compress_frames(s, n_frames, d_in, in_len, d_dict, dict_len, d_out, out_cap, d_out_len, d_status, static_cast<hipStream_t>(hip_stream), nullptr);
+}
+
+size_t lzf_frame_compress_stream_bound(const lzf_settings* s, size_t frame_bytes, size_t in_len) {
+    if (!s || !frame_bytes) return 0;
+    const size_t whole = in_len / frame_bytes, rest = in_len % frame_bytes;
+    return whole * lzf_frame_compress_bound(s, frame_bytes) + (rest || !whole ? lzf_frame_compress_bound(s, rest) : 0);
+}
+
+int lzf_frame_compress_stream_device(const lzf_settings* s, size_t frame_bytes, uint32_t n_streams,
+                                     const uint8_t* const* d_in, const size_t* in_len,
+                                     const uint8_t* d_dict, size_t dict_len, uint8_t* const* d_out, const size_t* out_cap,
+                                     uint64_t* d_out_len, int32_t* d_status, void* hip_stream) {
+    if (!s || !frame_bytes || (n_streams && (!d_in || !in_len || !d_out || !out_cap || !d_out_len || !d_status))) return LZF_E_INVALID;
+    if (s->dictionary) return LZF_E_INVALID;
+    if (!d_dict) dict_len = 0;
+    if (usable_device() != LZF_OK) return LZF_E_NO_DEVICE;
+    if (n_streams == 0) return LZF_OK;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    // the pieces: stream q is max(1, ceil(in_len[q] / frame_bytes)) frames of the call
+    std::vector<uint64_t> first((size_t)n_streams + 1, 0);
+    for (uint32_t q = 0; q < n_streams; ++q) { const uint64_t k = (in_len[q] + frame_bytes - 1) / frame_bytes; first[q + 1] = first[q] + (k ? k : 1); }
+    const size_t n = (size_t)first[n_streams];
+    if (n > 0x7FFFFFFFull) return LZF_E_INVALID;
+    std::vector<const uint8_t*> f_in(n); std::vector<size_t> f_len(n), f_cap(n); std::vector<uint8_t*> f_out(n);
+    for (uint32_t q = 0; q < n_streams; ++q) {
+        const size_t cap = out_cap[q] >= lzf_frame_compress_stream_bound(s, frame_bytes, in_len[q]) ? SIZE_MAX : 0;
+        for (uint64_t f = first[q]; f < first[q + 1]; ++f) {
+            const size_t off = (size_t)(f - first[q]) * frame_bytes;
+            f_in[(size_t)f] = d_in[q] + off; f_len[(size_t)f] = in_len[q] - off < frame_bytes ? in_len[q] - off : frame_bytes;
+            f_out[(size_t)f] = d_out[q]; f_cap[(size_t)f] = cap;
+        }
+    }
+    const size_t o_len = up256(4 * n);
+    PoolAlloc per(st);                                          // the frames' own status and length: scratch
+    if (!per.get(o_len + 8 * n)) return LZF_E_HIP;
+    const CStreamCtx cx{n_streams, first.data(), d_status, d_out_len};
+    return compress_frames(s, (uint32_t)n, f_in.data(), f_len.data(), d_dict, dict_len, f_out.data(), f_cap.data(),
+                           per.at<uint64_t>(o_len), per.at<int32_t>(0), st, &cx);
 }
 
 }  // extern "C"

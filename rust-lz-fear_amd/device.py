@@ -183,3 +183,71 @@ def frame_compress_many(settings, frames, outs, dictionary=None, stream=None):
     ffi.check(ffi.lib().lzf_frame_compress_device_many(C.byref(settings), n, ptrs, lens, dptr, dlen, optr, caps, out_len.data_ptr(),
                                                        status.data_ptr(), s.cuda_stream))
     return status, out_len
+
+
+# ---- streams of back-to-back frames in device memory (include/lzfear_frame.h) ---------------------------------------------
+
+def stream_decompress_bound(streams, stream=None):
+    """lzf_frame_stream_bound_device: per stream the sum of its frames' bounds.  Synchronous."""
+    n, ptrs, lens = _frame_args(streams)
+    if n == 0:
+        return []
+    bound = (C.c_size_t * n)()
+    ffi.check(ffi.lib().lzf_frame_stream_bound_device(n, ptrs, lens, bound, _stream_ptr(stream)))
+    return list(bound)
+
+
+def stream_decompress(streams, outs, dictionary=None, stream=None):
+    """lzf_frame_decompress_stream_device: every stream of back-to-back frames (1-D uint8 CUDA tensors) decoded into its tensor
+    of `outs` (their lengths are the capacities), frame behind frame.  Returns (status int32, out_len int64, consumed int64,
+    n_frames int64) as CUDA tensors, written in order on `stream`; nothing is synchronised beyond the call's own scans."""
+    n, ptrs, lens = _frame_args(streams)
+    assert len(outs) == n
+    dev = streams[0].device if n else torch.device("cuda", torch.cuda.current_device())
+    status = torch.empty(n, dtype=torch.int32, device=dev)         # (empty: the call writes every entry)
+    out_len = torch.empty(n, dtype=torch.int64, device=dev)
+    consumed = torch.empty(n, dtype=torch.int64, device=dev)
+    n_frames = torch.empty(n, dtype=torch.int64, device=dev)
+    if n == 0:
+        return status, out_len, consumed, n_frames
+    for t in outs:
+        assert t.dtype == torch.uint8 and t.is_cuda and t.dim() == 1 and t.is_contiguous(), "outs: 1-D contiguous uint8 CUDA tensors"
+    optr = (C.c_void_p * n)(*[t.data_ptr() for t in outs])
+    caps = (C.c_size_t * n)(*[t.numel() for t in outs])
+    dptr, dlen = None, 0
+    if dictionary is not None and dictionary.numel():
+        assert dictionary.dtype == torch.uint8 and dictionary.is_cuda and dictionary.is_contiguous()
+        dptr, dlen = dictionary.data_ptr(), dictionary.numel()
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    for t in (status, out_len, consumed, n_frames):
+        t.record_stream(s)
+    ffi.check(ffi.lib().lzf_frame_decompress_stream_device(n, ptrs, lens, dptr, dlen, optr, caps, out_len.data_ptr(), consumed.data_ptr(),
+                                                           status.data_ptr(), n_frames.data_ptr(), s.cuda_stream))
+    return status, out_len, consumed, n_frames
+
+
+def stream_compress(settings, frame_bytes, tensors, outs, dictionary=None, stream=None):
+    """lzf_frame_compress_stream_device: every input of `tensors` written as frames of `frame_bytes` input bytes each, back to
+    back, into its tensor of `outs`.  Returns (status int32, out_len int64) as CUDA tensors, written in order on `stream`;
+    nothing is synchronised."""
+    n, ptrs, lens = _frame_args(tensors)
+    assert len(outs) == n
+    dev = tensors[0].device if n else torch.device("cuda", torch.cuda.current_device())
+    status = torch.empty(n, dtype=torch.int32, device=dev)         # (empty: the call writes every entry)
+    out_len = torch.empty(n, dtype=torch.int64, device=dev)
+    if n == 0:
+        return status, out_len
+    for t in outs:
+        assert t.dtype == torch.uint8 and t.is_cuda and t.dim() == 1 and t.is_contiguous(), "outs: 1-D contiguous uint8 CUDA tensors"
+    optr = (C.c_void_p * n)(*[t.data_ptr() for t in outs])
+    caps = (C.c_size_t * n)(*[t.numel() for t in outs])
+    dptr, dlen = None, 0
+    if dictionary is not None and dictionary.numel():
+        assert dictionary.dtype == torch.uint8 and dictionary.is_cuda and dictionary.is_contiguous()
+        dptr, dlen = dictionary.data_ptr(), dictionary.numel()
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    for t in (status, out_len):
+        t.record_stream(s)
+    ffi.check(ffi.lib().lzf_frame_compress_stream_device(C.byref(settings), int(frame_bytes), n, ptrs, lens, dptr, dlen, optr, caps,
+                                                         out_len.data_ptr(), status.data_ptr(), s.cuda_stream))
+    return status, out_len

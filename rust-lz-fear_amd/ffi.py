@@ -81,6 +81,7 @@ FRAME_EXPORTS = [
     "lzf_frame_get_stats", "lzf_frame_release_scratch", "lzf_frame_set_host_threads", "lzf_frame_set_memory_budget",
     "lzf_frame_set_pinned_limit", "lzf_frame_decompress_bound_device", "lzf_frame_decompress_device_many",
     "lzf_frame_compress_device_many", "lzf_frame_decompressed_size_device",
+    "lzf_frame_stream_bound_device", "lzf_frame_decompress_stream_device", "lzf_frame_compress_stream_bound", "lzf_frame_compress_stream_device",
 ]
 
 
@@ -180,6 +181,15 @@ def lib():
                                                      C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p]
         L.lzf_frame_decompressed_size_device.argtypes = [C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t,
                                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.lzf_frame_stream_bound_device.argtypes = [C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_void_p]
+        L.lzf_frame_decompress_stream_device.argtypes = [C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t,
+                                                         C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                         C.c_void_p]
+        L.lzf_frame_compress_stream_bound.argtypes = [C.POINTER(Settings), C.c_size_t, C.c_size_t]
+        L.lzf_frame_compress_stream_bound.restype = C.c_size_t
+        L.lzf_frame_compress_stream_device.argtypes = [C.POINTER(Settings), C.c_size_t, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                                       C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p,
+                                                       C.c_void_p]
         _lib = L
     return _lib
 

@@ -207,6 +207,38 @@ class CompressionSettings:
                 raise FrameError(c)
         return [outs[f][:lens[f]] for f in range(len(tensors))]
 
+    def compress_streams_device(self, tensors, frame_bytes, with_size=False, stream=None):
+        """Every input of `tensors` (1-D uint8 CUDA tensors) written as a stream of back-to-back frames, one frame per
+        `frame_bytes` input bytes (lzf_frame_compress_stream_device): the bytes of `compress_many_device` over the pieces,
+        concatenated, packed on the device.  `with_size`: every frame's header carries its own piece's length.  Returns one
+        uint8 CUDA tensor per input once `stream` (default: the current stream) has finished the call; raises FrameError."""
+        import torch
+        from . import device
+        tensors = list(tensors)
+        if not tensors:
+            return []
+        dev = tensors[0].device
+        s = self._struct(0 if with_size else None)
+        s.dictionary = None                                 # (the device call takes the dictionary in device memory)
+        s.dictionary_len = 0
+        d_dict = None
+        if self._dictionary:
+            d_dict = torch.frombuffer(bytearray(self._dictionary), dtype=torch.uint8).to(dev)
+        L = ffi.lib()
+        outs = [torch.empty(L.lzf_frame_compress_stream_bound(C.byref(s), int(frame_bytes), t.numel()), dtype=torch.uint8, device=dev)
+                for t in tensors]
+        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        if d_dict is not None:
+            st.wait_stream(torch.cuda.current_stream(dev))   # (the upload ran on the current stream)
+        with torch.cuda.stream(st):
+            status, out_len = device.stream_compress(s, frame_bytes, tensors, outs, dictionary=d_dict, stream=st)
+        st.synchronize()
+        codes, lens = status.cpu().tolist(), out_len.cpu().tolist()
+        for c in codes:
+            if c != 0:
+                raise FrameError(c)
+        return [outs[f][:lens[f]] for f in range(len(tensors))]
+
     def compress_with_size(self, data):          # :147-157
         return self._run(data, len(data))
 
@@ -306,6 +338,29 @@ def decompress_frames_device(frames, dictionary=None, caps=None, stream=None, ex
     s.synchronize()
     st, ol, co = status.cpu().tolist(), out_len.cpu().tolist(), consumed.cpu().tolist()
     return [(st[f], outs[f][:ol[f]], co[f]) for f in range(len(frames))]
+
+
+def decompress_streams_device(streams, dictionary=None, caps=None, stream=None):
+    """Streams of back-to-back frames that live on the device (1-D uint8 CUDA tensors), every stream decoded on the device into
+    one contiguous tensor (lzf_frame_decompress_stream_device).  Outputs are sized from lzf_frame_stream_bound_device when `caps`
+    is None.  Returns [(status, out_tensor[:out_len], consumed, n_frames)] once `stream` (default: the current stream) has
+    finished the call: the status that ended the stream (0: every byte was read), the bytes of its frames up to there, the
+    input bytes read and the number of frames that ended at their EndMark."""
+    import torch
+    from . import device
+    streams = list(streams)
+    if not streams:
+        return []
+    dev = streams[0].device
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    if caps is None:
+        caps = device.stream_decompress_bound(streams, stream=s)
+    outs = [torch.empty(int(c), dtype=torch.uint8, device=dev) for c in caps]
+    with torch.cuda.stream(s):
+        status, out_len, consumed, n_frames = device.stream_decompress(streams, outs, dictionary=dictionary, stream=s)
+    s.synchronize()
+    st, ol, co, nf = status.cpu().tolist(), out_len.cpu().tolist(), consumed.cpu().tolist(), n_frames.cpu().tolist()
+    return [(st[f], outs[f][:ol[f]], co[f], nf[f]) for f in range(len(streams))]
 
 
 class FrameBlockReader:
