@@ -2,6 +2,8 @@
 //
 // Mirrors lz-fear's src/framed/{compress,decompress,header}.rs; every block goes through the HIP
 // kernels via lzf_compress_batch_host / lzf_decompress_batch_host — there is no CPU codec here.
+// The header parse and the block walk are lzf_frame_scan.h's (the device scan kernels run the same code), the frame layout is
+// lzf_frame_layout.h's, the passes of the memory budget are frame_jobs.h's split_passes.
 // All blocks of all frames of a call go into the same launches (independent-block frames: one launch; linked-block
 // frames — table and 64 KiB window carry, compress.rs:271-275, decompress.rs:253-269 — one launch per block index, every
 // stream of the call advancing together); the one-frame entry points are batches of one.
@@ -15,6 +17,7 @@
 #include <mutex>
 #include "../../include/lzfear_frame.h"
 #include "host_staging.h"
+#include "lzf_frame_scan.h"
 #include "frame_jobs.h"
 #include "lzf_frame_layout.h"
 
@@ -22,12 +25,18 @@ namespace {
 // a HIP failure inside a driver: nothing asynchronous may still read the caller's (or this call's) host arrays when it returns
 inline int fail_hip() { (void)hipDeviceSynchronize(); return LZF_E_HIP; }
 
-inline uint32_t rd32(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
-inline void wr32(uint8_t* p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); }
+// the frame format's constants, byte order and walk are those of lzf_frame_scan.h / lzf_frame_layout.h: the only copies
+using lzf_scan::rd32; using lzf_layout::wr32; using lzf_scan::rotl;
+using lzf_scan::FL_INDEP; using lzf_scan::FL_BLOCKSUM; using lzf_scan::FL_CSUM; using lzf_scan::INCOMPRESSIBLE;
+using lzf_frame_jobs::up256; using lzf_frame_jobs::block_out_bound;
+static_assert(lzf_scan::OK == LZF_OK && lzf_scan::INPUT_ERROR == LZF_F_INPUT_ERROR && lzf_scan::WRONG_MAGIC == LZF_F_WRONG_MAGIC &&
+              lzf_scan::HEADER_CHECKSUM_FAIL == LZF_F_HEADER_CHECKSUM_FAIL && lzf_scan::BLOCK_SIZE_OVERFLOW == LZF_F_BLOCK_SIZE_OVERFLOW &&
+              lzf_scan::UNIMPLEMENTED_BLOCKSIZE == LZF_F_UNIMPLEMENTED_BLOCKSIZE && lzf_scan::UNSUPPORTED_VERSION == LZF_F_UNSUPPORTED_VERSION &&
+              lzf_scan::RESERVED_FLAG_BITS == LZF_F_RESERVED_FLAG_BITS && lzf_scan::RESERVED_BD_BITS == LZF_F_RESERVED_BD_BITS &&
+              lzf_scan::MAGIC == LZF_MAGIC, "the walk reports the C ABI's statuses");
 
 // ---- XXH32 (streaming), as used by the frame format for header / block / content checksums
 constexpr uint32_t P1 = 2654435761u, P2 = 2246822519u, P3 = 3266489917u, P4 = 668265263u, P5 = 374761393u;
-inline uint32_t rotl(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
 struct Xxh32 {
     uint32_t v[4]; uint8_t buf[16]; uint32_t fill = 0; uint64_t total = 0; uint32_t seed;
     explicit Xxh32(uint32_t s = 0) : seed(s) { v[0] = s + P1 + P2; v[1] = s + P2; v[2] = s; v[3] = s - P1; }
@@ -54,10 +63,6 @@ struct Xxh32 {
     }
 };
 
-// header.rs:8-16
-constexpr uint8_t FL_INDEP = 0x20, FL_BLOCKSUM = 0x10, FL_CSIZE = 0x08, FL_CSUM = 0x04, FL_DICTID = 0x01;
-constexpr uint32_t INCOMPRESSIBLE = 0x80000000u;   // framed/mod.rs:18
-
 using lzf_layout::bd_new;          // header.rs:53-62 (lzf_frame_layout.h)
 using lzf_layout::write_header;    // compress.rs:163-200
 
@@ -81,40 +86,8 @@ int seeded_template(const uint8_t* dict, size_t dict_len, lzf_u32_table* host_ta
 std::atomic<uint64_t> g_host_block_hashes{0}, g_reader_device_hashes{0};
 size_t g_budget = 0;     // lzf_frame_set_memory_budget (0: half of the free device memory)
 
-// One block of a frame as the scan finds it (decompress.rs:217-235).
+// One block of a frame as the walk finds it (lzf_scan::Block), as a pointer into the caller's bytes.
 struct Blk { const uint8_t* data; uint32_t len; bool compressed; uint32_t want_sum; size_t end_off; };   // want_sum: the checksum behind it; end_off: input read once it is
-struct FrameScan {
-    size_t consumed = 0;          // bytes of the input read
-    int err = LZF_OK;             // structural error that ends the scan (reported in stream order)
-    bool endmark = false;
-    uint32_t want_content = 0;    // content checksum behind the EndMark
-};
-// The u32 length hops over a frame's blocks (decompress.rs:205-235).  Block checksums are only collected here: the
-// device hashes all blocks of a call in one launch and the delivery loop compares, in stream order.
-void scan_blocks(const uint8_t* in, size_t in_len, const lzf_frame_info& fi, std::vector<Blk>& blocks, FrameScan& sc) {
-    const size_t bmax = (size_t)fi.block_maxsize;
-    const bool bsum = fi.flags & FL_BLOCKSUM, csum = fi.flags & FL_CSUM;
-    size_t r = fi.header_len;
-    for (;;) {
-        if (in_len - r < 4) { sc.err = LZF_F_INPUT_ERROR; r = in_len; break; }
-        uint32_t bl = rd32(in + r); r += 4;
-        if (bl == 0) {                                                          // :206-215
-            if (csum) { if (in_len - r < 4) { sc.err = LZF_F_INPUT_ERROR; r = in_len; break; } sc.want_content = rd32(in + r); r += 4; }
-            sc.endmark = true; break;
-        }
-        const bool compressed = (bl & INCOMPRESSIBLE) == 0; bl &= ~INCOMPRESSIBLE;
-        if (bl > (uint32_t)bmax) { sc.err = LZF_F_BLOCK_SIZE_OVERFLOW; break; }               // :220-222
-        if (in_len - r < bl) { sc.err = LZF_F_INPUT_ERROR; r = in_len; break; }               // :226
-        const uint8_t* data = in + r; r += bl;
-        uint32_t c = 0;
-        if (bsum) {                                                                           // :228-230
-            if (in_len - r < 4) { sc.err = LZF_F_INPUT_ERROR; r = in_len; break; }
-            c = rd32(in + r); r += 4;
-        }
-        blocks.push_back({data, bl, compressed, c, r});
-    }
-    sc.consumed = r;
-}
 
 }  // namespace
 
@@ -183,37 +156,22 @@ int lzf_frame_compress(const lzf_settings* s, const uint8_t* in, size_t in_len, 
     return rc != LZF_OK ? rc : st;
 }
 
-// decompress.rs:102-161; *consumed = bytes the reference's reader has read when it returns
-static int read_header_ex(const uint8_t* in, size_t in_len, lzf_frame_info* info, size_t* consumed) {
+// decompress.rs:102-161 is lzf_scan::read_header: its status, and `consumed` = the bytes the reference's reader has read when it
+// returns.  Where the header parses, *info is filled from it; the content size and the dictionary id sit behind FLG and BD, in
+// that order, where the flags say so.  On any other status *info is all zero (until the walk became the only parse, a header that
+// failed at its checksum or its block size code still left FLG, BD and the two optional fields in *info; nothing read them).
+static lzf_scan::Header read_header_ex(const uint8_t* in, size_t in_len, lzf_frame_info* info) {
     memset(info, 0, sizeof *info);
-    size_t r = 0;
-    int rc = LZF_OK;
-#define NEED(n) do { if (in_len - r < (size_t)(n)) { r = in_len; rc = LZF_F_INPUT_ERROR; goto done; } } while (0)
-#define FAIL(c) do { rc = (c); goto done; } while (0)
-    {
-    NEED(4); r = 4; if (rd32(in) != LZF_MAGIC) FAIL(LZF_F_WRONG_MAGIC);       // :103-106
-    NEED(1); const uint8_t flg = in[r++];
-    if ((flg >> 6) != 1) FAIL(LZF_F_UNSUPPORTED_VERSION);                     // header.rs:33-36
-    if (flg & 0x02) FAIL(LZF_F_RESERVED_FLAG_BITS);                           // header.rs:37-39
-    NEED(1); const uint8_t bd = in[r++];
-    if (bd & 0x8F) FAIL(LZF_F_RESERVED_BD_BITS);                              // header.rs:66-68
-    info->flags = flg; info->bd = bd;
-    if (flg & FL_CSIZE) { NEED(8); info->has_content_size = 1; info->content_size = (uint64_t)rd32(in + r) | ((uint64_t)rd32(in + r + 4) << 32); r += 8; }
-    if (flg & FL_DICTID) { NEED(4); info->has_dictionary_id = 1; info->dictionary_id = rd32(in + r); r += 4; }
-    NEED(1); const uint8_t hc = in[r++];
-    if (hc != (uint8_t)(lzf_xxh32(in + 4, r - 5, 0) >> 8)) FAIL(LZF_F_HEADER_CHECKSUM_FAIL);   // :132-136
-    const unsigned size = (bd >> 4) & 7;
-    if (size < 4) FAIL(LZF_F_UNIMPLEMENTED_BLOCKSIZE);                        // :153, header.rs:73-80
-    info->block_maxsize = 1ull << (size * 2 + 8);
-    info->header_len = (uint16_t)r;
-    }
-done:
-    if (consumed) *consumed = r;
-    return rc;
-#undef NEED
-#undef FAIL
+    const lzf_scan::Header h = lzf_scan::read_header(in, in_len);
+    if (h.status != lzf_scan::OK) return h;
+    info->flags = h.flags; info->bd = h.bd;
+    info->block_maxsize = h.block_maxsize; info->header_len = (uint16_t)h.header_len;
+    const uint8_t* p = in + 6;
+    if (h.flags & lzf_scan::FL_CSIZE) { info->has_content_size = 1; info->content_size = (uint64_t)rd32(p) | ((uint64_t)rd32(p + 4) << 32); p += 8; }
+    if (h.flags & lzf_scan::FL_DICTID) { info->has_dictionary_id = 1; info->dictionary_id = rd32(p); }
+    return h;
 }
-int lzf_frame_read_header(const uint8_t* in, size_t in_len, lzf_frame_info* info) { return read_header_ex(in, in_len, info, nullptr); }
+int lzf_frame_read_header(const uint8_t* in, size_t in_len, lzf_frame_info* info) { return read_header_ex(in, in_len, info).status; }
 
 // decompress.rs:198-288 — one frame = a batch of one (lzf_frame_decompress_many below)
 int lzf_frame_decompress(const uint8_t* in, size_t in_len, const uint8_t* dict, size_t dict_len,
@@ -257,24 +215,28 @@ int lzf_frame_reader_decode_block(lzf_frame_reader* r, const uint8_t* dict, size
     *out_len = 0;
     if (!dict) dict_len = 0;
     if (r->finished) return LZF_OK;                                             // :202
-#define NEED(n) do { if (r->in_len - r->pos < (size_t)(n)) { r->pos = r->in_len; return LZF_F_INPUT_ERROR; } } while (0)
-    NEED(4); uint32_t bl = rd32(r->in + r->pos); r->pos += 4;                   // :205
-    if (bl == 0) {                                                              // :206-215
+    // the frame layer's walk from `pos`, stopped behind its first block (:205-230); the content checksum word is read only
+    // while the hasher is there (:207)
+    const bool bsum = (r->fi.flags & FL_BLOCKSUM) != 0;
+    const size_t bmax = (size_t)r->fi.block_maxsize;
+    const lzf_scan::Header from_pos{LZF_OK, 0, 0, (uint8_t)(r->has_hasher ? r->fi.flags : r->fi.flags & ~FL_CSUM), r->fi.bd, r->fi.block_maxsize};
+    const uint8_t* const at = r->in + r->pos;
+    lzf_scan::Block blk{0, 0, 0, 0, 0};
+    bool found = false;
+    const lzf_scan::Walk step = lzf_scan::walk_blocks(at, r->in_len - r->pos, from_pos, [&](const lzf_scan::Block& b) { blk = b; found = true; return false; });
+    r->pos += (size_t)step.consumed;
+    if (step.status != LZF_OK) return step.status;
+    if (!found) {                                                               // the EndMark (:206-215)
         if (r->has_hasher) {
             r->has_hasher = false;                                              // content_hasher.take()
-            NEED(4); const uint32_t c = rd32(r->in + r->pos); r->pos += 4;
-            if (c != r->hasher.digest()) return LZF_F_FRAME_CHECKSUM_FAIL;
+            if (step.want_content != r->hasher.digest()) return LZF_F_FRAME_CHECKSUM_FAIL;
         }
         r->finished = true;
         return LZF_OK;
     }
-    const bool compressed = (bl & INCOMPRESSIBLE) == 0; bl &= ~INCOMPRESSIBLE;  // :217-218
-    const size_t bmax = (size_t)r->fi.block_maxsize;
-    if (bl > (uint32_t)bmax) return LZF_F_BLOCK_SIZE_OVERFLOW;                  // :220-222
-    NEED(bl); const uint8_t* data = r->in + r->pos; r->pos += bl;               // :224-226
-    uint32_t want = 0; const bool bsum = (r->fi.flags & FL_BLOCKSUM) != 0;
-    if (bsum) { NEED(4); want = rd32(r->in + r->pos); r->pos += 4; }            // :229
-#undef NEED
+    const uint32_t bl = blk.len, want = blk.want_sum;
+    const bool compressed = blk.compressed != 0;                                // :217-218
+    const uint8_t* const data = at + blk.off;                                   // :224-226
     // the prefix (:238-245)
     const uint8_t* prefix = dict; size_t prefix_len = dict_len;
     if (r->linked) {
@@ -361,7 +323,6 @@ int lzf_frame_reader_decode_block(lzf_frame_reader* r, const uint8_t* dict, size
 namespace {
 using lzf_host::Seg;
 using lzf_host::Staging;
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 // (on failure: nothing asynchronous may still be reading the host arrays of the frame that returns)
 #define HIPOK(e) do { if ((e) != hipSuccess) { (void)hipDeviceSynchronize(); return LZF_E_HIP; } } while (0)
 #define RCOK(e) do { const int rc__ = (e); if (rc__ != LZF_OK) { (void)hipDeviceSynchronize(); return rc__; } } while (0)
@@ -461,12 +422,11 @@ int lzf_frame_compress_many(const lzf_settings* s, uint32_t n_frames, const uint
         else (void)hipGetLastError();
     }
     if (total <= limit) return compress_many_pass(s, n_frames, in, in_len, out, out_cap, out_len, status);
-    for (uint32_t f0 = 0; f0 < n_frames;) {
-        size_t sum = 0; uint32_t f1 = f0;
-        while (f1 < n_frames && (f1 == f0 || sum + in_len[f1] <= limit)) { sum += in_len[f1]; ++f1; }
+    std::vector<std::pair<uint32_t, uint32_t>> passes;
+    lzf_frame_jobs::split_passes(in_len, n_frames, limit, nullptr, passes);
+    for (const auto& [f0, f1] : passes) {
         const int rc = compress_many_pass(s, f1 - f0, in + f0, in_len + f0, out + f0, out_cap + f0, out_len + f0, status + f0);
         if (rc != LZF_OK) return rc;
-        f0 = f1;
     }
     return LZF_OK;
 }
@@ -768,11 +728,9 @@ static int compress_many_pass(const lzf_settings* s, uint32_t n_frames, const ui
 namespace {
 
 struct DFrame {
-    lzf_frame_info fi; std::vector<Blk> blocks; FrameScan sc; bool live = false, linked = false;
+    lzf_frame_info fi; std::vector<Blk> blocks; lzf_scan::Walk sc{}; bool live = false, linked = false;   // sc: how the walk ended
     size_t in_off = 0;                                   // device offset of the frame's bytes
-    size_t need = 0;                                     // device bytes this frame asks for (input + output room + packed result)
 };
-using lzf_frame_jobs::block_out_bound;
 
 // One pass over frames [f0, f1): everything on the device at once.
 int decompress_group(Staging& sg, std::vector<DFrame>& fr, uint32_t f0, uint32_t f1, const uint8_t* const* in, const size_t* in_len,
@@ -916,7 +874,7 @@ int decompress_group(Staging& sg, std::vector<DFrame>& fr, uint32_t f0, uint32_t
         if (st != LZF_OK) { status[f] = st; continue; }
         if (stopped) continue;
         if (consumed) consumed[f] = F.sc.consumed;
-        if (F.sc.err != LZF_OK) { status[f] = F.sc.err; continue; }
+        if (F.sc.status != LZF_OK) { status[f] = F.sc.status; continue; }
         if (F.sc.endmark && csum) { (w <= kDeviceHashMax ? dev_hash : host_hash).push_back({f, pk0, w}); }   // :207-211
     }
     if (!r_src.empty() || !dev_hash.empty()) {
@@ -963,21 +921,23 @@ int lzf_frame_decompress_many(uint32_t n_frames, const uint8_t* const* in, const
     if (n_frames && (!in || !in_len || !out || !out_cap || !out_len || !status)) return LZF_E_INVALID;
     if (!dict) dict_len = 0;
     std::vector<DFrame> fr(n_frames);
+    std::vector<size_t> need(n_frames, 0);               // device bytes every frame asks for (input + output room + packed result)
     for (uint32_t f = 0; f < n_frames; ++f) {
         DFrame& F = fr[f];
         out_len[f] = 0; if (consumed) consumed[f] = 0;
-        size_t hdr_read = 0;
-        const int rc = read_header_ex(in[f], in_len[f], &F.fi, &hdr_read);
-        if (rc != LZF_OK) { status[f] = rc; if (consumed) consumed[f] = hdr_read; continue; }
+        const lzf_scan::Header h = read_header_ex(in[f], in_len[f], &F.fi);
+        if (h.status != LZF_OK) { status[f] = h.status; if (consumed) consumed[f] = (size_t)h.consumed; continue; }
         status[f] = LZF_OK; F.live = true; F.linked = !(F.fi.flags & FL_INDEP);
-        scan_blocks(in[f], in_len[f], F.fi, F.blocks, F.sc);
+        F.sc = lzf_scan::walk_blocks(in[f], in_len[f], h, [&](const lzf_scan::Block& b) {
+            F.blocks.push_back({in[f] + b.off, b.len, b.compressed != 0, b.want_sum, (size_t)b.end_off});
+        });
         if (consumed) consumed[f] = F.sc.consumed;
         // device memory the frame asks for: its bytes, an output slot per block bounded by what the block can expand to
         // (a 5-byte block cannot claim block_maxsize), and the packed result
         const size_t bmax = (size_t)F.fi.block_maxsize;
         size_t bound = 0;
         for (const Blk& b : F.blocks) bound += (b.compressed ? block_out_bound(bmax, b.len) : 0) + b.len + 256;
-        F.need = F.sc.consumed + 2 * bound + 4096;
+        need[f] = F.sc.consumed + 2 * bound + 4096;
     }
     if (n_frames == 0) return LZF_OK;
     Staging& sg = Staging::get();
@@ -987,17 +947,11 @@ int lzf_frame_decompress_many(uint32_t n_frames, const uint8_t* const* in, const
     size_t free_b = 0, total_b = 0;
     HIPOK(hipMemGetInfo(&free_b, &total_b));
     size_t budget = g_budget ? g_budget : free_b / 2;
-    for (uint32_t f0 = 0; f0 < n_frames;) {
-        size_t sum = 0; uint32_t f1 = f0;
-        while (f1 < n_frames && (f1 == f0 || sum + fr[f1].need <= budget)) {
-            sum += fr[f1].live ? fr[f1].need : 0; ++f1;
-        }
-        if (f1 == f0 + 1 && fr[f0].live && fr[f0].need > budget) {
-            status[f0] = LZF_E_NO_MEMORY; out_len[f0] = 0; if (consumed) consumed[f0] = 0;
-            f0 = f1; continue;
-        }
+    std::vector<std::pair<uint32_t, uint32_t>> passes;
+    lzf_frame_jobs::split_passes(need.data(), n_frames, budget, nullptr, passes);
+    for (const auto& [f0, f1] : passes) {
+        if (f1 == f0 + 1 && need[f0] > budget) { status[f0] = LZF_E_NO_MEMORY; out_len[f0] = 0; if (consumed) consumed[f0] = 0; continue; }
         RCOK(decompress_group(sg, fr, f0, f1, in, in_len, dict, dict_len, out, out_cap, out_len, consumed, status));
-        f0 = f1;
     }
     ++g_stats.calls;
     return LZF_OK;

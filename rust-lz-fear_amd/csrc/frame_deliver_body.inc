@@ -27,11 +27,7 @@
             } else n = b.len;
             if (!code && n > F.bmax) code = LZF_F_BLOCK_SIZE_OVERFLOW;
         }
-        uint64_t incl = n;                                      // inclusive scan of n over the wave
-        for (uint32_t d = 1; d < 64u; d <<= 1) {
-            const uint64_t v = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += v;
-        }
+        const uint64_t incl = wave_incl_scan(n, lane);
         const uint64_t at = w + (incl - n);                     // where the block goes in the caller's output
         const bool cap = act && !code && (at > F.out_cap || F.out_cap - at < n);
         const bool zero = act && !code && !cap && n == 0;

@@ -24,6 +24,12 @@
 // length, lzf_stream_place_kernel gives every frame its place and the room left in its stream's output, and at the end
 // lzf_stream_fold_kernel folds the frames' results into the streams'.  Compress: the pieces of every input are frames of the
 // compress call above (compress_frames); lzf_stream_pack_kernel, in front of the assembly, puts each frame behind the one before.
+//
+// One copy of each rule.  The walk is lzf_frame_scan.h's (the host driver runs the same header).  The passes of the memory budget
+// are frame_jobs.h's split_passes, for all four *_many drivers.  The decode plan is plan_frames (the scan's summaries and table
+// as frame_jobs.h's frames) and plan_pass (jobs, descriptors, checksum lists): decode_frames runs them per pass, the size query
+// once with sizes_only.  The small arrays of a call travel in one Meta: one image, one upload, one event, typed accessors.  The
+// four one-wavefront-per-frame / per-stream kernels share wave_incl_scan.
 #include <hip/hip_runtime.h>
 #include <cstring>
 #include <map>
@@ -75,6 +81,21 @@ struct DBlkDesc {
     uint32_t sum_idx;           // block checksum of the pass, kNone: none
     uint32_t want_sum, len;     // len: a stored block's length
 };
+
+// ---- the wave-wide sums of the one-wavefront-per-frame / per-stream kernels below
+__device__ inline uint64_t wave_sum(uint64_t v) {
+    for (int d = 32; d > 0; d >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, d, 64);
+    return v;
+}
+// inclusive scan over the 64 lanes: lane l gets v of lanes 0..l (the exclusive one is the result minus the lane's own v; lane 63
+// holds the round's total, the carry into the next round of 64)
+__device__ inline uint64_t wave_incl_scan(uint64_t v, uint32_t lane) {
+    for (uint32_t d = 1; d < 64u; d <<= 1) {
+        const uint64_t u = __shfl_up(v, d, 64);
+        if (lane >= d) v += u;
+    }
+    return v;
+}
 
 __global__ __launch_bounds__(64) void lzf_frame_scan_kernel(const uint8_t* const* __restrict__ in, const uint64_t* __restrict__ in_len, uint32_t n,
                                                             FSum* __restrict__ sums, int32_t* __restrict__ d_status,
@@ -187,11 +208,6 @@ struct SSeg { uint32_t stream, fd0, nf, pad; };
 // what a stream carries from pass to pass: the bytes placed so far, and whether a frame has ended it
 struct SState { uint64_t run; uint32_t stopped, pad; };
 
-__device__ inline uint64_t wave_sum(uint64_t v) {
-    for (int d = 32; d > 0; d >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, d, 64);
-    return v;
-}
-
 // Placement, one wavefront per stream and pass, 64 frames per round.  f_status / f_len / f_consumed hold what the count-only
 // delivery found for every frame with unlimited room.  The exclusive prefix of the lengths, behind the stream's running
 // length, is where each frame goes; the stream goes on behind a frame only if that frame ended at its EndMark with LZF_OK and
@@ -219,11 +235,7 @@ __global__ __launch_bounds__(64) void lzf_stream_place_kernel(const SSeg* __rest
             n = f_len[f];
             complete = f_status[f] == LZF_OK && F->scan_err == LZF_OK && f_consumed[f] == F->scan_consumed;
         }
-        uint64_t incl = n;                                      // inclusive scan of n over the wave
-        for (uint32_t d = 1; d < 64u; d <<= 1) {
-            const uint64_t v = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += v;
-        }
+        const uint64_t incl = wave_incl_scan(n, lane);
         const uint64_t at = run + (incl - n);                   // (at <= cap up to the first stop: every frame before it fits)
         const bool fits = at <= cap && cap - at >= n;
         const uint64_t stops = __ballot(act && !(complete && fits));
@@ -323,11 +335,7 @@ __global__ __launch_bounds__(64) void lzf_frame_assemble_kernel(const CFrameDesc
         lzf_layout::Block b{0u, false, false, LZF_OK};
         if (act) { c = blks[F.blk0 + i]; const lzf_job_result r = res[c.job]; b = lzf_layout::block_of(r.status, r.out_len, c.raw_len); }
         const uint64_t span = act ? lzf_layout::block_span(b.len, bsum) : 0ull;
-        uint64_t incl = span;                                   // inclusive scan of the spans over the wave
-        for (uint32_t d = 1; d < 64u; d <<= 1) {
-            const uint64_t v = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += v;
-        }
+        const uint64_t incl = wave_incl_scan(span, lane);
         if (act) {
             const uint32_t g = F.blk0 + i;
             uint8_t* const at = F.dst + (w + incl - span);      // the block's length word
@@ -379,11 +387,7 @@ __global__ __launch_bounds__(64) void lzf_stream_pack_kernel(const CSeg* __restr
                     len += lzf_layout::block_span(b.len, bsum);
                 }
             }
-            uint64_t incl = len;                                // inclusive scan of the frames' lengths over the wave
-            for (uint32_t d = 1; d < 64u; d <<= 1) {
-                const uint64_t v = __shfl_up(incl, d, 64);
-                if (lane >= d) incl += v;
-            }
+            const uint64_t incl = wave_incl_scan(len, lane);
             if (act) frames[G.fd0 + i].dst = G.out + (w + incl - len);
             const uint64_t bads = __ballot(act && bad != LZF_OK);
             if (bads && st == LZF_OK) st = __shfl(bad, (int)__builtin_ctzll(bads), 64);
@@ -422,9 +426,59 @@ int usable_device() {
 }
 using lzf_frame_jobs::up256;
 
-// Scan pass 1 of n frames: summaries back on the host (the call's first wait).  `args` keeps [ptrs | lens | blk0 | cnt] for pass 2.
-int scan_summaries(uint32_t n, const uint8_t* const* d_in, const size_t* in_len, hipStream_t st, PoolAlloc& args, std::vector<FSum>& sums,
+// The small arrays of a call in one pool allocation: the host image (every list the host builds: one upload) and, behind it, the
+// scratch that only kernels write.  add / room hand out offsets while the call is planned; after upload(), img<T>(off) and
+// scr<T>(off) are their typed device addresses.  wait() returns once the image has left host memory (the kernels run on).
+struct Meta {
+    hipStream_t st;
+    std::vector<uint8_t> image; size_t scratch = 0;
+    PoolAlloc mem; hipEvent_t uploaded = nullptr;
+    explicit Meta(hipStream_t s) : st(s), mem(s) {}
+    ~Meta() { if (uploaded) (void)hipEventDestroy(uploaded); }
+    size_t add(const void* p, size_t bytes) { const size_t o = image.size(); image.resize(up256(o + bytes)); if (bytes && p) memcpy(image.data() + o, p, bytes); return o; }
+    template <class T> size_t add(const std::vector<T>& v) { return add(v.data(), sizeof(T) * v.size()); }
+    size_t room(size_t bytes) { const size_t o = scratch; scratch = up256(scratch + bytes); return o; }
+    template <class T> T* img(size_t off) const { return mem.at<T>(off); }
+    template <class T> T* scr(size_t off) const { return mem.at<T>(image.size() + off); }
+    int upload(bool zero_scratch) {         // zero_scratch: chain states, range and hash lengths start at 0
+        if (!mem.get(image.size() + scratch)) { (void)hipStreamSynchronize(st); return LZF_E_HIP; }
+        DEV_TRY(hipEventCreateWithFlags(&uploaded, hipEventDisableTiming));
+        if (!image.empty()) DEV_TRY(hipMemcpyAsync(mem.p, image.data(), image.size(), hipMemcpyHostToDevice, st));
+        DEV_TRY(hipEventRecord(uploaded, st));
+        if (zero_scratch && scratch) DEV_TRY(hipMemsetAsync(scr<uint8_t>(0), 0, scratch, st));
+        return LZF_OK;
+    }
+    int wait() { DEV_TRY(hipEventSynchronize(uploaded)); return LZF_OK; }
+};
+
+// lzf_frame_set_memory_budget's value, or half of the free device memory
+int pass_budget(hipStream_t st, size_t* budget) {
+    *budget = lzf_frame_jobs::memory_budget();
+    if (!*budget) { size_t free_b = 0, total_b = 0; DEV_TRY(hipMemGetInfo(&free_b, &total_b)); *budget = free_b / 2; }
+    return LZF_OK;
+}
+// frames [first[s], first[s + 1]) are stream s: the stream of every frame
+std::vector<uint32_t> streams_of(uint32_t n_streams, const uint64_t* first) {
+    std::vector<uint32_t> of((size_t)first[n_streams]);
+    for (uint32_t s = 0; s < n_streams; ++s) for (uint64_t f = first[s]; f < first[s + 1]; ++f) of[(size_t)f] = s;
+    return of;
+}
+
+// What the scan of n frames brings back to the host: the summaries (pass 1) and, with scan_table, the block table (pass 2):
+// frame f's blocks are table[blk0[f], blk0[f] + cnt[f]).  `args` keeps [ptrs | lens | blk0 | cnt] on the device between the two.
+struct Scan {
+    PoolAlloc args;
+    std::vector<FSum> sum;
+    std::vector<uint64_t> blk0, cnt;
+    std::vector<TBlk> table;
+    explicit Scan(hipStream_t st) : args(st) {}
+    bool live(uint32_t f) const { return (sum[f].flags & kLive) != 0; }
+};
+
+// Scan pass 1 of n frames: summaries back on the host (the call's first wait).
+int scan_summaries(uint32_t n, const uint8_t* const* d_in, const size_t* in_len, hipStream_t st, Scan& sc,
                    int32_t* d_status, uint64_t* d_out_len, uint64_t* d_consumed) {
+    PoolAlloc& args = sc.args;
     const size_t o_sum = up256(32 * (size_t)n);
     if (!args.get(o_sum + sizeof(FSum) * (size_t)n)) return LZF_E_HIP;
     std::vector<uint64_t> h(2 * (size_t)n);
@@ -432,48 +486,39 @@ int scan_summaries(uint32_t n, const uint8_t* const* d_in, const size_t* in_len,
     DEV_TRY(hipMemcpyAsync(args.p, h.data(), 16 * (size_t)n, hipMemcpyHostToDevice, st));
     KERNEL(lzf_frame_scan_kernel, dim3((n + 63u) / 64u), dim3(64), 0, st, args.at<const uint8_t* const>(0), args.at<const uint64_t>(8 * (size_t)n), n,
            args.at<FSum>(o_sum), d_status, d_out_len, d_consumed);
-    sums.resize(n);
-    DEV_TRY(hipMemcpyAsync(sums.data(), args.at<FSum>(o_sum), sizeof(FSum) * (size_t)n, hipMemcpyDeviceToHost, st));
+    sc.sum.resize(n);
+    DEV_TRY(hipMemcpyAsync(sc.sum.data(), args.at<FSum>(o_sum), sizeof(FSum) * (size_t)n, hipMemcpyDeviceToHost, st));
     DEV_TRY(hipStreamSynchronize(st));
     return LZF_OK;
 }
 
 // Scan pass 2: the block table of every frame whose header parses, back on the host (the call's second wait).
-int scan_table(uint32_t n, hipStream_t st, PoolAlloc& args, const std::vector<FSum>& sum, std::vector<uint64_t>& blk0, std::vector<uint64_t>& cnt,
-               std::vector<TBlk>& table) {
-    blk0.assign(n, ~0ull); cnt.assign(n, 0);
+int scan_table(uint32_t n, hipStream_t st, Scan& sc) {
+    sc.blk0.assign(n, ~0ull); sc.cnt.assign(n, 0);
     uint64_t n_table = 0;
-    for (uint32_t f = 0; f < n; ++f) if (sum[f].flags & kLive) { blk0[f] = n_table; cnt[f] = sum[f].n_blocks; n_table += sum[f].n_blocks; }
+    for (uint32_t f = 0; f < n; ++f) if (sc.live(f)) { sc.blk0[f] = n_table; sc.cnt[f] = sc.sum[f].n_blocks; n_table += sc.sum[f].n_blocks; }
     if (n_table > 0x7FFFFFFFull) { (void)hipStreamSynchronize(st); return LZF_E_INVALID; }
-    table.resize((size_t)n_table);
+    sc.table.resize((size_t)n_table);
     if (n_table) {
         std::vector<uint64_t> h(2 * (size_t)n);
-        memcpy(h.data(), blk0.data(), 8 * (size_t)n); memcpy(h.data() + n, cnt.data(), 8 * (size_t)n);
-        DEV_TRY(hipMemcpyAsync(args.at<uint64_t>(16 * (size_t)n), h.data(), 16 * (size_t)n, hipMemcpyHostToDevice, st));
+        memcpy(h.data(), sc.blk0.data(), 8 * (size_t)n); memcpy(h.data() + n, sc.cnt.data(), 8 * (size_t)n);
+        DEV_TRY(hipMemcpyAsync(sc.args.at<uint64_t>(16 * (size_t)n), h.data(), 16 * (size_t)n, hipMemcpyHostToDevice, st));
         PoolAlloc tab(st);
         if (!tab.get(sizeof(TBlk) * (size_t)n_table)) { (void)hipStreamSynchronize(st); return LZF_E_HIP; }
-        KERNEL(lzf_frame_table_kernel, dim3((n + 63u) / 64u), dim3(64), 0, st, args.at<const uint8_t* const>(0), args.at<const uint64_t>(8 * (size_t)n),
-               args.at<const uint64_t>(16 * (size_t)n), args.at<const uint64_t>(24 * (size_t)n), n, tab.at<TBlk>(0));
-        DEV_TRY(hipMemcpyAsync(table.data(), tab.p, sizeof(TBlk) * (size_t)n_table, hipMemcpyDeviceToHost, st));
+        KERNEL(lzf_frame_table_kernel, dim3((n + 63u) / 64u), dim3(64), 0, st, sc.args.at<const uint8_t* const>(0), sc.args.at<const uint64_t>(8 * (size_t)n),
+               sc.args.at<const uint64_t>(16 * (size_t)n), sc.args.at<const uint64_t>(24 * (size_t)n), n, tab.at<TBlk>(0));
+        DEV_TRY(hipMemcpyAsync(sc.table.data(), tab.p, sizeof(TBlk) * (size_t)n_table, hipMemcpyDeviceToHost, st));
         DEV_TRY(hipStreamSynchronize(st));
     }
     return LZF_OK;
 }
 
-// host image of the small arrays of every pass: one upload
-struct Image {
-    std::vector<uint8_t> h;
-    size_t add(const void* p, size_t bytes) { const size_t o = h.size(); h.resize(up256(o + bytes)); if (bytes && p) memcpy(h.data() + o, p, bytes); return o; }
-};
-struct Scratch {                         // device-only arrays (written by kernels), after the image
-    size_t total = 0;
-    size_t add(size_t bytes) { const size_t o = total; total = up256(total + bytes); return o; }
-};
-
+// One pass of the decode plan: frames [f0, f1) of the call, everything the kernels read in the call's image (i_*) and everything
+// they write in its scratch (s_*).
 struct Pass {
     uint32_t f0 = 0, f1 = 0;
     bool no_memory = false;
-    std::vector<lzf_frame_jobs::Frame> jf;
+    std::vector<lzf_frame_jobs::Frame> jf;          // the frames whose header parsed, jf_frame: which frame of the call each is
     std::vector<uint32_t> jf_frame;
     lzf_frame_jobs::Plan plan;
     uint32_t n_frames = 0, n_blks = 0, n_sums = 0, n_hash = 0, n_link = 0;
@@ -483,7 +528,99 @@ struct Pass {
     uint32_t n_segs = 0;                // streams: the pass's SSeg list
     // scratch offsets
     size_t s_res = 0, s_state = 0, s_sums = 0, s_rsrc = 0, s_rdst = 0, s_rlen = 0, s_lsrc = 0, s_ldst = 0, s_llen = 0, s_hlen = 0, s_hcheck = 0, s_hout = 0;
+    std::vector<lzf_frame_jobs::Frame*> frames() { std::vector<lzf_frame_jobs::Frame*> l; for (auto& J : jf) l.push_back(&J); return l; }
 };
+
+// The decode plan, step one: the pass's frames as frame_jobs.h's frames, from the scan summaries and the block table (the blocks
+// as device addresses in the caller's input), and their output layout.
+void plan_frames(Pass& P, const uint8_t* const* d_in, const Scan& sc) {
+    P.jf.reserve(P.f1 - P.f0);
+    for (uint32_t f = P.f0; f < P.f1; ++f) {
+        if (!sc.live(f)) continue;
+        const FSum& S = sc.sum[f];
+        P.jf.emplace_back();
+        lzf_frame_jobs::Frame& J = P.jf.back();
+        J.linked = !(S.flags & lzf_scan::FL_INDEP); J.bmax = (size_t)S.block_maxsize; J.consumed = (size_t)S.consumed;
+        for (uint64_t k = 0; k < sc.cnt[f]; ++k) {
+            const TBlk& t = sc.table[sc.blk0[f] + k];
+            J.blocks.push_back({d_in[f] + t.off, t.len & ~lzf_scan::INCOMPRESSIBLE, (t.len & lzf_scan::INCOMPRESSIBLE) == 0});
+        }
+        P.jf_frame.push_back(f);
+    }
+    lzf_frame_jobs::layout(P.frames(), P.plan);
+}
+
+// What the plan's step two is told about the call.  The size query (lzf_frame_decompressed_size_device) has neither outputs nor
+// slots: sizes_only, every address NULL, unlimited room, no copy lists and no content checksum.
+struct DecodeCall {
+    bool sizes_only;
+    uint8_t* dslots; const uint8_t* d_dict; size_t dict_len;
+    uint8_t* const* d_out; const size_t* out_cap;
+    const uint32_t* stream_of;          // streams: the stream of every frame (unlimited room for the count; the placement sets dst and out_cap)
+};
+
+// The decode plan, step two: jobs and chain steps (frame_jobs.h), the delivery kernel's descriptors and the checksum lists of the
+// pass, into the call's image; room for what the kernels write, in its scratch.
+int plan_pass(Pass& P, const Scan& sc, const DecodeCall& c, Meta& meta) {
+    lzf_frame_jobs::build(P.frames(), P.plan, c.dslots, c.d_dict, c.dict_len, c.sizes_only);
+    if (P.plan.jobs.size() > 0x7FFFFFFFull) return LZF_E_INVALID;
+    std::vector<DFrameDesc> fd; std::vector<DBlkDesc> bd;
+    std::vector<const uint8_t*> sptr; std::vector<uint64_t> slen;
+    std::vector<const uint8_t*> hptr; std::vector<uint32_t> hwant, hframe;
+    std::vector<SSeg> segs;
+    for (size_t q = 0; q < P.jf.size(); ++q) {
+        const lzf_frame_jobs::Frame& J = P.jf[q];
+        const uint32_t f = P.jf_frame[q];
+        const FSum& S = sc.sum[f];
+        const bool chained = J.linked && !J.blocks.empty();
+        DFrameDesc d;
+        memset(&d, 0, sizeof d);
+        d.out_cap = c.sizes_only || c.stream_of ? ~0ull : c.out_cap[f]; d.scan_consumed = S.consumed; d.bmax = J.bmax;
+        d.blk0 = (uint32_t)bd.size(); d.nb = (uint32_t)J.blocks.size(); d.scan_err = S.status;
+        d.flags = (J.linked ? kLinked : 0u);
+        d.frame = f; d.hash_idx = kNone; d.link_idx = kNone;
+        if (!c.sizes_only) {
+            d.dst = c.d_out[f]; d.stream = chained ? c.dslots + J.out_off : nullptr;
+            if ((S.flags & kEndmark) && (S.flags & lzf_scan::FL_CSUM) && S.status == LZF_OK) {
+                d.flags |= kCheckContent; d.hash_idx = (uint32_t)hptr.size();
+                hptr.push_back(c.d_out[f]); hwant.push_back(S.want_content); hframe.push_back(f);
+            }
+            if (chained) {
+                d.link_idx = P.n_link++;
+                const uint64_t m = (uint64_t)J.blocks.size() * J.bmax, cap = c.out_cap[f] < m ? c.out_cap[f] : m;
+                if (cap > P.link_max) P.link_max = cap;
+            } else if (!J.blocks.empty() && J.bmax > P.ind_max) P.ind_max = J.bmax;
+        }
+        const bool bsum = (S.flags & lzf_scan::FL_BLOCKSUM) != 0;
+        for (size_t i = 0; i < J.blocks.size(); ++i) {
+            const TBlk& t = sc.table[sc.blk0[f] + i];
+            DBlkDesc b;
+            b.src = c.sizes_only ? nullptr : J.blocks[i].compressed ? (J.linked ? nullptr : c.dslots + J.slot[i]) : J.blocks[i].src;
+            b.end_off = t.end_off; b.job = J.job[i] == SIZE_MAX ? kNone : (uint32_t)J.job[i];
+            b.sum_idx = kNone; b.want_sum = t.want_sum; b.len = J.blocks[i].len;
+            if (bsum) { b.sum_idx = (uint32_t)sptr.size(); sptr.push_back(J.blocks[i].src); slen.push_back(J.blocks[i].len); }
+            bd.push_back(b);
+        }
+        if (c.stream_of) {
+            if (segs.empty() || segs.back().stream != c.stream_of[f]) segs.push_back(SSeg{c.stream_of[f], (uint32_t)fd.size(), 0u, 0u});
+            ++segs.back().nf;
+        }
+        fd.push_back(d);
+    }
+    P.n_segs = (uint32_t)segs.size(); P.i_segs = meta.add(segs);
+    P.n_frames = (uint32_t)fd.size(); P.n_blks = (uint32_t)bd.size(); P.n_sums = (uint32_t)sptr.size(); P.n_hash = (uint32_t)hptr.size();
+    P.i_jobs = meta.add(P.plan.jobs); P.i_steps = meta.add(P.plan.csteps);
+    P.i_sptr = meta.add(sptr); P.i_slen = meta.add(slen);
+    P.i_frames = meta.add(fd); P.i_blks = meta.add(bd);
+    P.i_hptr = meta.add(hptr); P.i_hwant = meta.add(hwant); P.i_hframe = meta.add(hframe);
+    P.s_res = meta.room(sizeof(lzf_job_result) * P.plan.jobs.size()); P.s_state = meta.room(sizeof(lzf_chain_state) * P.plan.n_chain);
+    P.s_sums = meta.room(4 * (size_t)P.n_sums);
+    if (c.sizes_only) return LZF_OK;
+    P.s_rsrc = meta.room(8 * (size_t)P.n_blks); P.s_rdst = meta.room(8 * (size_t)P.n_blks); P.s_rlen = meta.room(8 * (size_t)P.n_blks);
+    P.s_lsrc = meta.room(8 * (size_t)P.n_link); P.s_ldst = meta.room(8 * (size_t)P.n_link); P.s_llen = meta.room(8 * (size_t)P.n_link);
+    P.s_hlen = meta.room(8 * (size_t)P.n_hash); P.s_hcheck = meta.room(4 * (size_t)P.n_hash); P.s_hout = meta.room(4 * (size_t)P.n_hash);
+    return LZF_OK;
+}
 
 // What makes the frames of a decode call the frames of streams (lzf_frame_decompress_stream_device): stream s is frames
 // [first[s], first[s + 1]) of the call and owns one output.  d_out / out_cap of decode_frames then hold, per frame, its stream's
@@ -503,186 +640,90 @@ struct StreamCtx {
 int decode_frames(const uint32_t n, const uint8_t* const* d_in, const size_t* in_len, const uint8_t* d_dict, size_t dict_len,
                   uint8_t* const* d_out, const size_t* out_cap, uint64_t* d_out_len, uint64_t* d_consumed, int32_t* d_status,
                   hipStream_t st, const StreamCtx* sx) {
-    // ---- scan pass 1: summaries (wait 1)
-    PoolAlloc args(st);
-    std::vector<FSum> sum;
-    RC_TRY(scan_summaries(n, d_in, in_len, st, args, sum, d_status, d_out_len, d_consumed));
-    // ---- scan pass 2: the block table of every frame whose header parses (wait 2)
-    std::vector<uint64_t> blk0, cnt;
-    std::vector<TBlk> table;
-    RC_TRY(scan_table(n, st, args, sum, blk0, cnt, table));
-    // ---- passes: as many frames as the memory budget holds, with the host driver's accounting (frame.cpp); a frame that does
-    //      not fit alone gets LZF_E_NO_MEMORY
+    // ---- scan: summaries (wait 1), the block table of every frame whose header parses (wait 2)
+    Scan sc(st);
+    RC_TRY(scan_summaries(n, d_in, in_len, st, sc, d_status, d_out_len, d_consumed));
+    RC_TRY(scan_table(n, st, sc));
+    // ---- passes: as many frames as the memory budget holds (frame_jobs.h's split_passes), with the host driver's accounting
+    //      (frame.cpp); a frame that does not fit alone gets LZF_E_NO_MEMORY
     std::vector<size_t> need(n, 0);
-    for (uint32_t f = 0; f < n; ++f) if (sum[f].flags & kLive) need[f] = (size_t)sum[f].consumed + 2 * (size_t)sum[f].need + 4096;
-    size_t budget = lzf_frame_jobs::memory_budget();
-    if (!budget) { size_t free_b = 0, total_b = 0; DEV_TRY(hipMemGetInfo(&free_b, &total_b)); budget = free_b / 2; }
-    std::vector<uint32_t> stream_of;                 // streams: the stream of every frame
-    if (sx) { stream_of.resize(n); for (uint32_t s = 0; s < sx->n_streams; ++s) for (uint64_t f = sx->first[s]; f < sx->first[s + 1]; ++f) stream_of[(size_t)f] = s; }
-    std::vector<Pass> passes;
-    for (uint32_t f0 = 0; f0 < n;) {
-        size_t s = 0; uint32_t f1 = f0;
-        while (f1 < n && (f1 == f0 || s + need[f1] <= budget)) { s += need[f1]; ++f1; }
-        Pass P; P.f0 = f0; P.f1 = f1;
-        P.no_memory = f1 == f0 + 1 && (sum[f0].flags & kLive) && need[f0] > budget;
-        passes.push_back(std::move(P));
-        f0 = f1;
-    }
+    for (uint32_t f = 0; f < n; ++f) if (sc.live(f)) need[f] = (size_t)sc.sum[f].consumed + 2 * (size_t)sc.sum[f].need + 4096;
+    size_t budget = 0;
+    RC_TRY(pass_budget(st, &budget));
+    std::vector<std::pair<uint32_t, uint32_t>> cuts;
+    lzf_frame_jobs::split_passes(need.data(), n, budget, nullptr, cuts);
+    std::vector<Pass> passes(cuts.size());
     // ---- output layout of every pass; the passes share one slot allocation (stream order: pass p + 1 decodes after pass p's copy)
     size_t slots_bytes = 0;
-    for (Pass& P : passes) {
+    for (size_t p = 0; p < cuts.size(); ++p) {
+        Pass& P = passes[p];
+        P.f0 = cuts[p].first; P.f1 = cuts[p].second;
+        P.no_memory = P.f1 == P.f0 + 1 && need[P.f0] > budget;
         if (P.no_memory) continue;
-        P.jf.reserve(P.f1 - P.f0);
-        for (uint32_t f = P.f0; f < P.f1; ++f) {
-            if (!(sum[f].flags & kLive)) continue;
-            P.jf.emplace_back();
-            lzf_frame_jobs::Frame& J = P.jf.back();
-            J.linked = !(sum[f].flags & lzf_scan::FL_INDEP); J.bmax = (size_t)sum[f].block_maxsize; J.consumed = (size_t)sum[f].consumed;
-            for (uint64_t k = 0; k < cnt[f]; ++k) {
-                const TBlk& t = table[blk0[f] + k];
-                J.blocks.push_back({d_in[f] + t.off, t.len & ~lzf_scan::INCOMPRESSIBLE, (t.len & lzf_scan::INCOMPRESSIBLE) == 0});
-            }
-            P.jf_frame.push_back(f);
-        }
-        std::vector<lzf_frame_jobs::Frame*> jfl;
-        for (auto& J : P.jf) jfl.push_back(&J);
-        lzf_frame_jobs::layout(jfl, P.plan);
+        plan_frames(P, d_in, sc);
         if (P.plan.out_total > slots_bytes) slots_bytes = P.plan.out_total;
     }
     PoolAlloc slots(st);
     if (slots_bytes && !slots.get(slots_bytes)) { (void)hipStreamSynchronize(st); return LZF_E_HIP; }
-    uint8_t* const dslots = static_cast<uint8_t*>(slots.p);
     // ---- jobs and descriptors of every pass into one image
-    Image img; Scratch scr;
-    for (Pass& P : passes) {
-        if (P.no_memory) continue;
-        std::vector<lzf_frame_jobs::Frame*> jfl;
-        for (auto& J : P.jf) jfl.push_back(&J);
-        lzf_frame_jobs::build(jfl, P.plan, dslots, d_dict, dict_len);
-        if (P.plan.jobs.size() > 0x7FFFFFFFull) { (void)hipStreamSynchronize(st); return LZF_E_INVALID; }
-        std::vector<DFrameDesc> fd; std::vector<DBlkDesc> bd;
-        std::vector<const uint8_t*> sptr; std::vector<uint64_t> slen;
-        std::vector<const uint8_t*> hptr; std::vector<uint32_t> hwant, hframe;
-        std::vector<SSeg> segs;
-        for (size_t q = 0; q < P.jf.size(); ++q) {
-            const lzf_frame_jobs::Frame& J = P.jf[q];
-            const uint32_t f = P.jf_frame[q];
-            const FSum& S = sum[f];
-            DFrameDesc d;
-            memset(&d, 0, sizeof d);
-            d.dst = d_out[f]; d.stream = J.linked && !J.blocks.empty() ? dslots + J.out_off : nullptr;
-            d.out_cap = sx ? ~0ull : out_cap[f]; d.scan_consumed = S.consumed; d.bmax = J.bmax;
-            d.blk0 = (uint32_t)bd.size(); d.nb = (uint32_t)J.blocks.size(); d.scan_err = S.status;
-            d.flags = (J.linked ? kLinked : 0u);
-            d.frame = f; d.hash_idx = kNone; d.link_idx = kNone;
-            if ((S.flags & kEndmark) && (S.flags & lzf_scan::FL_CSUM) && S.status == LZF_OK) {
-                d.flags |= kCheckContent; d.hash_idx = (uint32_t)hptr.size();
-                hptr.push_back(d_out[f]); hwant.push_back(S.want_content); hframe.push_back(f);
-            }
-            if (J.linked && !J.blocks.empty()) {
-                d.link_idx = P.n_link++;
-                const uint64_t m = (uint64_t)J.blocks.size() * J.bmax, c = out_cap[f] < m ? out_cap[f] : m;
-                if (c > P.link_max) P.link_max = c;
-            } else if (!J.blocks.empty() && J.bmax > P.ind_max) P.ind_max = J.bmax;
-            const bool bsum = (S.flags & lzf_scan::FL_BLOCKSUM) != 0;
-            for (size_t i = 0; i < J.blocks.size(); ++i) {
-                const TBlk& t = table[blk0[f] + i];
-                DBlkDesc b;
-                b.src = J.blocks[i].compressed ? (J.linked ? nullptr : dslots + J.slot[i]) : J.blocks[i].src;
-                b.end_off = t.end_off; b.job = J.job[i] == SIZE_MAX ? kNone : (uint32_t)J.job[i];
-                b.sum_idx = kNone; b.want_sum = t.want_sum; b.len = J.blocks[i].len;
-                if (bsum) { b.sum_idx = (uint32_t)sptr.size(); sptr.push_back(J.blocks[i].src); slen.push_back(J.blocks[i].len); }
-                bd.push_back(b);
-            }
-            if (sx) {                       // (unlimited room above: for the count; lzf_stream_place_kernel sets dst and out_cap)
-                if (segs.empty() || segs.back().stream != stream_of[f]) segs.push_back(SSeg{stream_of[f], (uint32_t)fd.size(), 0u, 0u});
-                ++segs.back().nf;
-            }
-            fd.push_back(d);
-        }
-        P.n_segs = (uint32_t)segs.size(); P.i_segs = img.add(segs.data(), sizeof(SSeg) * segs.size());
-        P.n_frames = (uint32_t)fd.size(); P.n_blks = (uint32_t)bd.size(); P.n_sums = (uint32_t)sptr.size(); P.n_hash = (uint32_t)hptr.size();
-        P.i_jobs = img.add(P.plan.jobs.data(), sizeof(lzf_decompress_job) * P.plan.jobs.size());
-        P.i_steps = img.add(P.plan.csteps.data(), sizeof(lzf_chain_step) * P.plan.csteps.size());
-        P.i_sptr = img.add(sptr.data(), sizeof(void*) * sptr.size()); P.i_slen = img.add(slen.data(), 8 * slen.size());
-        P.i_frames = img.add(fd.data(), sizeof(DFrameDesc) * fd.size()); P.i_blks = img.add(bd.data(), sizeof(DBlkDesc) * bd.size());
-        P.i_hptr = img.add(hptr.data(), sizeof(void*) * hptr.size()); P.i_hwant = img.add(hwant.data(), 4 * hwant.size()); P.i_hframe = img.add(hframe.data(), 4 * hframe.size());
-        P.s_res = scr.add(sizeof(lzf_job_result) * P.plan.jobs.size()); P.s_state = scr.add(sizeof(lzf_chain_state) * P.plan.n_chain);
-        P.s_sums = scr.add(4 * (size_t)P.n_sums);
-        P.s_rsrc = scr.add(8 * (size_t)P.n_blks); P.s_rdst = scr.add(8 * (size_t)P.n_blks); P.s_rlen = scr.add(8 * (size_t)P.n_blks);
-        P.s_lsrc = scr.add(8 * (size_t)P.n_link); P.s_ldst = scr.add(8 * (size_t)P.n_link); P.s_llen = scr.add(8 * (size_t)P.n_link);
-        P.s_hlen = scr.add(8 * (size_t)P.n_hash); P.s_hcheck = scr.add(4 * (size_t)P.n_hash); P.s_hout = scr.add(4 * (size_t)P.n_hash);
-    }
+    const std::vector<uint32_t> stream_of = sx ? streams_of(sx->n_streams, sx->first) : std::vector<uint32_t>();
+    const DecodeCall call{false, slots.at<uint8_t>(0), d_dict, dict_len, d_out, out_cap, sx ? stream_of.data() : nullptr};
+    Meta meta(st);
+    for (Pass& P : passes) if (!P.no_memory) RC_TRY(plan_pass(P, sc, call, meta));
     size_t i_sout = 0, i_scap = 0, i_first = 0, i_full = 0;
     if (sx) {
         std::vector<uint64_t> cap(sx->s_cap, sx->s_cap + sx->n_streams), full(n);
-        for (uint32_t f = 0; f < n; ++f) full[f] = (sum[f].flags & kLive) && sum[f].status == LZF_OK ? sum[f].consumed : ~0ull;
-        i_sout = img.add(sx->s_out, sizeof(void*) * sx->n_streams); i_scap = img.add(cap.data(), 8 * cap.size());
-        i_first = img.add(sx->first, 8 * ((size_t)sx->n_streams + 1)); i_full = img.add(full.data(), 8 * full.size());
+        for (uint32_t f = 0; f < n; ++f) full[f] = sc.live(f) && sc.sum[f].status == LZF_OK ? sc.sum[f].consumed : ~0ull;
+        i_sout = meta.add(sx->s_out, sizeof(void*) * sx->n_streams); i_scap = meta.add(cap);
+        i_first = meta.add(sx->first, 8 * ((size_t)sx->n_streams + 1)); i_full = meta.add(full);
     }
     // ---- one upload, then the kernels of every pass
-    const size_t img_bytes = img.h.size();
-    PoolAlloc meta(st);
-    if (!meta.get(img_bytes + scr.total)) { (void)hipStreamSynchronize(st); return LZF_E_HIP; }
-    hipEvent_t uploaded = nullptr;
-    DEV_TRY(hipEventCreateWithFlags(&uploaded, hipEventDisableTiming));
-    struct EventOwner { hipEvent_t e; ~EventOwner() { if (e) (void)hipEventDestroy(e); } } owner{uploaded};
-    if (img_bytes) DEV_TRY(hipMemcpyAsync(meta.p, img.h.data(), img_bytes, hipMemcpyHostToDevice, st));
-    DEV_TRY(hipEventRecord(uploaded, st));
-    if (scr.total) DEV_TRY(hipMemsetAsync(meta.at<uint8_t>(img_bytes), 0, scr.total, st));       // chain states, range and hash lengths start at 0
-    auto I = [&](size_t off) { return meta.at<uint8_t>(off); };
-    auto S = [&](size_t off) { return meta.at<uint8_t>(img_bytes + off); };
+    RC_TRY(meta.upload(true));
     for (Pass& P : passes) {
         if (P.no_memory && sx) { KERNEL(lzf_stream_no_memory_kernel, dim3(1), dim3(64), 0, st, P.f0, stream_of[P.f0], sx->d_sstate, d_status, d_out_len, d_consumed); continue; }
         if (P.no_memory) { KERNEL(lzf_frame_no_memory_kernel, dim3(1), dim3(64), 0, st, P.f0, d_status, d_out_len, d_consumed); continue; }
         if (!P.n_frames) continue;
-        lzf_decompress_job* const d_jobs = reinterpret_cast<lzf_decompress_job*>(I(P.i_jobs));
-        lzf_job_result* const d_res = reinterpret_cast<lzf_job_result*>(S(P.s_res));
-        uint32_t* const d_sums = reinterpret_cast<uint32_t*>(S(P.s_sums));
-        if (P.n_sums) RC_TRY(lzf_xxh32_batch(reinterpret_cast<const uint8_t* const*>(I(P.i_sptr)), reinterpret_cast<const uint64_t*>(I(P.i_slen)), d_sums, P.n_sums, st));
+        lzf_decompress_job* const d_jobs = meta.img<lzf_decompress_job>(P.i_jobs);
+        lzf_job_result* const d_res = meta.scr<lzf_job_result>(P.s_res);
+        uint32_t* const d_sums = meta.scr<uint32_t>(P.s_sums);
+        const DFrameDesc* const d_frames = meta.img<const DFrameDesc>(P.i_frames);
+        const DBlkDesc* const d_blks = meta.img<const DBlkDesc>(P.i_blks);
+        if (P.n_sums) RC_TRY(lzf_xxh32_batch(meta.img<const uint8_t* const>(P.i_sptr), meta.img<const uint64_t>(P.i_slen), d_sums, P.n_sums, st));
         const lzf_frame_jobs::Plan& pl = P.plan;
         for (size_t k = 0; k < pl.n_steps; ++k) {
-            if (pl.n_chain) RC_TRY(lzf_chain_decompress_step(reinterpret_cast<const lzf_chain_step*>(I(P.i_steps)) + k * pl.n_chain,
-                                                             reinterpret_cast<lzf_chain_state*>(S(P.s_state)), pl.n_chain, d_jobs, d_res, st));
+            if (pl.n_chain) RC_TRY(lzf_chain_decompress_step(meta.img<const lzf_chain_step>(P.i_steps) + k * pl.n_chain, meta.scr<lzf_chain_state>(P.s_state),
+                                                             pl.n_chain, d_jobs, d_res, st));
             const size_t a = pl.step_off[k], c = pl.step_off[k + 1] - a;
             if (c) RC_TRY(lzf_decompress_batch_sized(d_jobs + a, d_res + a, (uint32_t)c, lzf_frame_jobs::step_max_input(pl, k), st));
         }
         if (sx) {                           // where every frame goes is known only now: count, then place
-            KERNEL(lzf_frame_size_deliver_kernel, dim3(P.n_frames), dim3(64), 0, st,
-                   reinterpret_cast<const DFrameDesc*>(I(P.i_frames)), reinterpret_cast<const DBlkDesc*>(I(P.i_blks)), (const lzf_decompress_job*)d_jobs,
+            KERNEL(lzf_frame_size_deliver_kernel, dim3(P.n_frames), dim3(64), 0, st, d_frames, d_blks, (const lzf_decompress_job*)d_jobs,
                    (const lzf_job_result*)d_res, (const uint32_t*)d_sums, d_status, d_out_len, d_consumed);
-            KERNEL(lzf_stream_place_kernel, dim3(P.n_segs), dim3(64), 0, st, reinterpret_cast<const SSeg*>(I(P.i_segs)),
-                   reinterpret_cast<DFrameDesc*>(I(P.i_frames)), reinterpret_cast<const uint8_t**>(I(P.i_hptr)),
-                   reinterpret_cast<uint8_t* const*>(I(i_sout)), reinterpret_cast<const uint64_t*>(I(i_scap)), sx->d_sstate,
+            KERNEL(lzf_stream_place_kernel, dim3(P.n_segs), dim3(64), 0, st, meta.img<const SSeg>(P.i_segs), meta.img<DFrameDesc>(P.i_frames),
+                   meta.img<const uint8_t*>(P.i_hptr), meta.img<uint8_t* const>(i_sout), meta.img<const uint64_t>(i_scap), sx->d_sstate,
                    (const int32_t*)d_status, (const uint64_t*)d_out_len, (const uint64_t*)d_consumed);
         }
-        KERNEL(lzf_frame_deliver_kernel, dim3(P.n_frames), dim3(64), 0, st,
-               reinterpret_cast<const DFrameDesc*>(I(P.i_frames)), reinterpret_cast<const DBlkDesc*>(I(P.i_blks)), (const lzf_decompress_job*)d_jobs,
+        KERNEL(lzf_frame_deliver_kernel, dim3(P.n_frames), dim3(64), 0, st, d_frames, d_blks, (const lzf_decompress_job*)d_jobs,
                (const lzf_job_result*)d_res, (const uint32_t*)d_sums,
-               reinterpret_cast<const uint8_t**>(S(P.s_rsrc)), reinterpret_cast<uint8_t**>(S(P.s_rdst)), reinterpret_cast<uint64_t*>(S(P.s_rlen)),
-               reinterpret_cast<const uint8_t**>(S(P.s_lsrc)), reinterpret_cast<uint8_t**>(S(P.s_ldst)), reinterpret_cast<uint64_t*>(S(P.s_llen)),
-               reinterpret_cast<uint64_t*>(S(P.s_hlen)), reinterpret_cast<uint32_t*>(S(P.s_hcheck)), d_status, d_out_len, d_consumed);
+               meta.scr<const uint8_t*>(P.s_rsrc), meta.scr<uint8_t*>(P.s_rdst), meta.scr<uint64_t>(P.s_rlen),
+               meta.scr<const uint8_t*>(P.s_lsrc), meta.scr<uint8_t*>(P.s_ldst), meta.scr<uint64_t>(P.s_llen),
+               meta.scr<uint64_t>(P.s_hlen), meta.scr<uint32_t>(P.s_hcheck), d_status, d_out_len, d_consumed);
         if (P.n_blks && P.ind_max)
-            RC_TRY(lzf_copy_ranges(reinterpret_cast<const uint8_t* const*>(S(P.s_rsrc)), reinterpret_cast<uint8_t* const*>(S(P.s_rdst)),
-                                   reinterpret_cast<const uint64_t*>(S(P.s_rlen)), P.n_blks, P.ind_max, st));
+            RC_TRY(lzf_copy_ranges(meta.scr<const uint8_t* const>(P.s_rsrc), meta.scr<uint8_t* const>(P.s_rdst), meta.scr<const uint64_t>(P.s_rlen), P.n_blks, P.ind_max, st));
         if (P.n_link && P.link_max)
-            RC_TRY(lzf_copy_ranges(reinterpret_cast<const uint8_t* const*>(S(P.s_lsrc)), reinterpret_cast<uint8_t* const*>(S(P.s_ldst)),
-                                   reinterpret_cast<const uint64_t*>(S(P.s_llen)), P.n_link, P.link_max, st));
+            RC_TRY(lzf_copy_ranges(meta.scr<const uint8_t* const>(P.s_lsrc), meta.scr<uint8_t* const>(P.s_ldst), meta.scr<const uint64_t>(P.s_llen), P.n_link, P.link_max, st));
         if (P.n_hash) {
-            RC_TRY(lzf_xxh32_batch(reinterpret_cast<const uint8_t* const*>(I(P.i_hptr)), reinterpret_cast<const uint64_t*>(S(P.s_hlen)),
-                                   reinterpret_cast<uint32_t*>(S(P.s_hout)), P.n_hash, st));
-            KERNEL(lzf_frame_content_check_kernel, dim3((P.n_hash + 255u) / 256u), dim3(256), 0, st,
-                   reinterpret_cast<const uint32_t*>(S(P.s_hout)), reinterpret_cast<const uint32_t*>(I(P.i_hwant)),
-                   reinterpret_cast<const uint32_t*>(S(P.s_hcheck)), reinterpret_cast<const uint32_t*>(I(P.i_hframe)), P.n_hash, d_status);
+            RC_TRY(lzf_xxh32_batch(meta.img<const uint8_t* const>(P.i_hptr), meta.scr<const uint64_t>(P.s_hlen), meta.scr<uint32_t>(P.s_hout), P.n_hash, st));
+            KERNEL(lzf_frame_content_check_kernel, dim3((P.n_hash + 255u) / 256u), dim3(256), 0, st, meta.scr<const uint32_t>(P.s_hout),
+                   meta.img<const uint32_t>(P.i_hwant), meta.scr<const uint32_t>(P.s_hcheck), meta.img<const uint32_t>(P.i_hframe), P.n_hash, d_status);
         }
     }
     if (sx)
-        KERNEL(lzf_stream_fold_kernel, dim3(sx->n_streams), dim3(64), 0, st, reinterpret_cast<const uint64_t*>(I(i_first)), (const int32_t*)d_status,
-               (const uint64_t*)d_out_len, (const uint64_t*)d_consumed, reinterpret_cast<const uint64_t*>(I(i_full)),
+        KERNEL(lzf_stream_fold_kernel, dim3(sx->n_streams), dim3(64), 0, st, meta.img<const uint64_t>(i_first), (const int32_t*)d_status,
+               (const uint64_t*)d_out_len, (const uint64_t*)d_consumed, meta.img<const uint64_t>(i_full),
                sx->s_status, sx->s_out_len, sx->s_consumed, sx->s_n_frames);
     // the image left host memory long ago (it was first in the stream behind the table read-back); the kernels run on
-    DEV_TRY(hipEventSynchronize(uploaded));
-    return LZF_OK;
+    return meta.wait();
 }
 
 // The stream scan of n streams: the frames of every stream back on the host (two waits: the counts, then the starts).  Stream s
@@ -738,10 +779,9 @@ int lzf_frame_decompress_bound_device(uint32_t n_frames, const uint8_t* const* d
     if (usable_device() != LZF_OK) return LZF_E_NO_DEVICE;
     if (n_frames == 0) return LZF_OK;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    PoolAlloc args(st);
-    std::vector<FSum> sums;
-    RC_TRY(scan_summaries(n_frames, d_in, in_len, st, args, sums, nullptr, nullptr, nullptr));
-    for (uint32_t f = 0; f < n_frames; ++f) out_bound[f] = (sums[f].flags & kLive) ? (size_t)sums[f].out_bound : 0;
+    Scan sc(st);
+    RC_TRY(scan_summaries(n_frames, d_in, in_len, st, sc, nullptr, nullptr, nullptr));
+    for (uint32_t f = 0; f < n_frames; ++f) out_bound[f] = sc.live(f) ? (size_t)sc.sum[f].out_bound : 0;
     return LZF_OK;
 }
 
@@ -767,14 +807,11 @@ int lzf_frame_stream_bound_device(uint32_t n_streams, const uint8_t* const* d_in
     std::vector<uint64_t> first;
     std::vector<const uint8_t*> f_in; std::vector<size_t> f_len;
     RC_TRY(scan_streams(n_streams, d_in, in_len, st, first, f_in, f_len));
-    std::vector<FSum> sums;
-    if (!f_in.empty()) {
-        PoolAlloc args(st);
-        RC_TRY(scan_summaries((uint32_t)f_in.size(), f_in.data(), f_len.data(), st, args, sums, nullptr, nullptr, nullptr));
-    }
+    Scan sc(st);
+    if (!f_in.empty()) RC_TRY(scan_summaries((uint32_t)f_in.size(), f_in.data(), f_len.data(), st, sc, nullptr, nullptr, nullptr));
     for (uint32_t s = 0; s < n_streams; ++s) {
         size_t b = 0;
-        for (uint64_t f = first[s]; f < first[s + 1]; ++f) if (sums[(size_t)f].flags & kLive) b += (size_t)sums[(size_t)f].out_bound;
+        for (uint64_t f = first[s]; f < first[s + 1]; ++f) if (sc.live((uint32_t)f)) b += (size_t)sc.sum[(size_t)f].out_bound;
         out_bound[s] = b;
     }
     return LZF_OK;
@@ -823,87 +860,31 @@ int lzf_frame_decompressed_size_device(uint32_t n_frames, const uint8_t* const* 
     PoolAlloc own_consumed(st);                      // the kernels write `consumed` of every frame; a caller who passes NULL does not get it
     if (!d_consumed) { if (!own_consumed.get(8 * (size_t)n)) return LZF_E_HIP; d_consumed = own_consumed.at<uint64_t>(0); }
     // ---- scan: summaries (wait 1), block table (wait 2)
-    PoolAlloc args(st);
-    std::vector<FSum> sum;
-    RC_TRY(scan_summaries(n, d_in, in_len, st, args, sum, d_status, d_out_len, d_consumed));
-    std::vector<uint64_t> blk0, cnt;
-    std::vector<TBlk> table;
-    RC_TRY(scan_table(n, st, args, sum, blk0, cnt, table));
-    // ---- jobs (frame_jobs.h with sizes_only: the decode's lengths, no addresses) and descriptors
-    std::vector<lzf_frame_jobs::Frame> jf;
-    std::vector<uint32_t> jf_frame;
-    for (uint32_t f = 0; f < n; ++f) {
-        if (!(sum[f].flags & kLive)) continue;
-        jf.emplace_back();
-        lzf_frame_jobs::Frame& J = jf.back();
-        J.linked = !(sum[f].flags & lzf_scan::FL_INDEP); J.bmax = (size_t)sum[f].block_maxsize; J.consumed = (size_t)sum[f].consumed;
-        for (uint64_t k = 0; k < cnt[f]; ++k) {
-            const TBlk& t = table[blk0[f] + k];
-            J.blocks.push_back({d_in[f] + t.off, t.len & ~lzf_scan::INCOMPRESSIBLE, (t.len & lzf_scan::INCOMPRESSIBLE) == 0});
-        }
-        jf_frame.push_back(f);
-    }
-    if (jf.empty()) return LZF_OK;                   // every header failed: the scan kernel wrote the results
-    std::vector<lzf_frame_jobs::Frame*> jfl;
-    for (auto& J : jf) jfl.push_back(&J);
-    lzf_frame_jobs::Plan pl;
-    lzf_frame_jobs::layout(jfl, pl);
-    lzf_frame_jobs::build(jfl, pl, nullptr, nullptr, dict_len, true);
-    if (pl.jobs.size() > 0x7FFFFFFFull) { (void)hipStreamSynchronize(st); return LZF_E_INVALID; }
-    std::vector<DFrameDesc> fd; std::vector<DBlkDesc> bd;
-    std::vector<const uint8_t*> sptr; std::vector<uint64_t> slen;
-    for (size_t q = 0; q < jf.size(); ++q) {
-        const lzf_frame_jobs::Frame& J = jf[q];
-        const uint32_t f = jf_frame[q];
-        const FSum& S = sum[f];
-        DFrameDesc d;
-        memset(&d, 0, sizeof d);
-        d.out_cap = ~0ull; d.scan_consumed = S.consumed; d.bmax = J.bmax;              // unlimited room: never LZF_OUT_CAPACITY
-        d.blk0 = (uint32_t)bd.size(); d.nb = (uint32_t)J.blocks.size(); d.scan_err = S.status;
-        d.flags = (J.linked ? kLinked : 0u);
-        d.frame = f; d.hash_idx = kNone; d.link_idx = kNone;                          // the content checksum needs the content: not verified
-        const bool bsum = (S.flags & lzf_scan::FL_BLOCKSUM) != 0;
-        for (size_t i = 0; i < J.blocks.size(); ++i) {
-            const TBlk& t = table[blk0[f] + i];
-            DBlkDesc b;
-            b.src = nullptr;
-            b.end_off = t.end_off; b.job = J.job[i] == SIZE_MAX ? kNone : (uint32_t)J.job[i];
-            b.sum_idx = kNone; b.want_sum = t.want_sum; b.len = J.blocks[i].len;
-            if (bsum) { b.sum_idx = (uint32_t)sptr.size(); sptr.push_back(J.blocks[i].src); slen.push_back(J.blocks[i].len); }
-            bd.push_back(b);
-        }
-        fd.push_back(d);
-    }
-    Image img; Scratch scr;
-    const size_t i_jobs = img.add(pl.jobs.data(), sizeof(lzf_decompress_job) * pl.jobs.size());
-    const size_t i_steps = img.add(pl.csteps.data(), sizeof(lzf_chain_step) * pl.csteps.size());
-    const size_t i_sptr = img.add(sptr.data(), sizeof(void*) * sptr.size()), i_slen = img.add(slen.data(), 8 * slen.size());
-    const size_t i_frames = img.add(fd.data(), sizeof(DFrameDesc) * fd.size()), i_blks = img.add(bd.data(), sizeof(DBlkDesc) * bd.size());
-    const size_t s_res = scr.add(sizeof(lzf_job_result) * pl.jobs.size()), s_state = scr.add(sizeof(lzf_chain_state) * pl.n_chain);
-    const size_t s_sums = scr.add(4 * sptr.size());
-    const size_t img_bytes = img.h.size();
-    PoolAlloc meta(st);
-    if (!meta.get(img_bytes + scr.total)) { (void)hipStreamSynchronize(st); return LZF_E_HIP; }
-    hipEvent_t uploaded = nullptr;
-    DEV_TRY(hipEventCreateWithFlags(&uploaded, hipEventDisableTiming));
-    struct EventOwner { hipEvent_t e; ~EventOwner() { if (e) (void)hipEventDestroy(e); } } owner{uploaded};
-    if (img_bytes) DEV_TRY(hipMemcpyAsync(meta.p, img.h.data(), img_bytes, hipMemcpyHostToDevice, st));
-    DEV_TRY(hipEventRecord(uploaded, st));
-    if (scr.total) DEV_TRY(hipMemsetAsync(meta.at<uint8_t>(img_bytes), 0, scr.total, st));       // the chain states start at 0
-    lzf_decompress_job* const d_jobs = meta.at<lzf_decompress_job>(i_jobs);
-    lzf_job_result* const d_res = meta.at<lzf_job_result>(img_bytes + s_res);
-    uint32_t* const d_sums = meta.at<uint32_t>(img_bytes + s_sums);
-    if (!sptr.empty()) RC_TRY(lzf_xxh32_batch(meta.at<const uint8_t* const>(i_sptr), meta.at<const uint64_t>(i_slen), d_sums, (uint32_t)sptr.size(), st));
+    Scan sc(st);
+    RC_TRY(scan_summaries(n, d_in, in_len, st, sc, d_status, d_out_len, d_consumed));
+    RC_TRY(scan_table(n, st, sc));
+    // ---- the decode's plan with sizes_only: its jobs' lengths and its descriptors, no addresses; the content checksum needs the
+    //      content: not verified
+    Pass P; P.f0 = 0; P.f1 = n;
+    plan_frames(P, d_in, sc);
+    if (P.jf.empty()) return LZF_OK;                 // every header failed: the scan kernel wrote the results
+    Meta meta(st);
+    RC_TRY(plan_pass(P, sc, DecodeCall{true, nullptr, nullptr, dict_len, nullptr, nullptr, nullptr}, meta));
+    RC_TRY(meta.upload(true));
+    lzf_decompress_job* const d_jobs = meta.img<lzf_decompress_job>(P.i_jobs);
+    lzf_job_result* const d_res = meta.scr<lzf_job_result>(P.s_res);
+    uint32_t* const d_sums = meta.scr<uint32_t>(P.s_sums);
+    const lzf_frame_jobs::Plan& pl = P.plan;
+    if (P.n_sums) RC_TRY(lzf_xxh32_batch(meta.img<const uint8_t* const>(P.i_sptr), meta.img<const uint64_t>(P.i_slen), d_sums, P.n_sums, st));
     for (size_t k = 0; k < pl.n_steps; ++k) {
-        if (pl.n_chain) KERNEL(lzf_chain_size_step_kernel, dim3(pl.n_chain), dim3(256), 0, st, meta.at<const lzf_chain_step>(i_steps) + k * pl.n_chain,
-                               meta.at<lzf_chain_state>(img_bytes + s_state), pl.n_chain, d_jobs, (const lzf_job_result*)d_res);
+        if (pl.n_chain) KERNEL(lzf_chain_size_step_kernel, dim3(pl.n_chain), dim3(256), 0, st, meta.img<const lzf_chain_step>(P.i_steps) + k * pl.n_chain,
+                               meta.scr<lzf_chain_state>(P.s_state), pl.n_chain, d_jobs, (const lzf_job_result*)d_res);
         const size_t a = pl.step_off[k], c = pl.step_off[k + 1] - a;
         if (c) RC_TRY(lzf_decompressed_size_batch(d_jobs + a, d_res + a, (uint32_t)c, lzf_frame_jobs::step_max_input(pl, k), st));
     }
-    KERNEL(lzf_frame_size_deliver_kernel, dim3((uint32_t)fd.size()), dim3(64), 0, st, meta.at<const DFrameDesc>(i_frames), meta.at<const DBlkDesc>(i_blks),
+    KERNEL(lzf_frame_size_deliver_kernel, dim3(P.n_frames), dim3(64), 0, st, meta.img<const DFrameDesc>(P.i_frames), meta.img<const DBlkDesc>(P.i_blks),
            (const lzf_decompress_job*)d_jobs, (const lzf_job_result*)d_res, (const uint32_t*)d_sums, d_status, d_out_len, d_consumed);
-    DEV_TRY(hipEventSynchronize(uploaded));          // the image has left host memory; the kernels run on
-    return LZF_OK;
+    return meta.wait();                              // the image has left host memory; the kernels run on
 }
 
 }  // extern "C"
@@ -920,9 +901,7 @@ struct CPass {
     uint32_t n_segs = 0;                                        // streams: the pass's CSeg list
     size_t s_res = 0, s_rsrc = 0, s_rdst = 0, s_rlen = 0, s_at = 0, s_val = 0;
 };
-}  // namespace
 
-namespace {
 // What makes the frames of a compress call the pieces of streams (lzf_frame_compress_stream_device): stream q is frames
 // [first[q], first[q + 1]) of the call, written back to back.  d_out / out_cap of compress_frames then hold, per frame, its
 // stream's output and SIZE_MAX or 0 (the stream's capacity holds the bound, or not); d_status / d_out_len are per-frame scratch.
@@ -973,25 +952,17 @@ int compress_frames(const lzf_settings* s, const uint32_t n, const uint8_t* cons
         nb[f] = (in_len[f] + bs - 1) / bs;
         need[f] = in_len[f] + copies_of(f) + (indep ? 0 : sizeof(lzf_u32_table)) + 256 * nb[f] + 4096;   // output slots, copies, table, lists
     }
-    // ---- passes of the memory budget; a frame whose scratch alone is over it is a pass of its own
-    size_t budget = lzf_frame_jobs::memory_budget();
-    if (!budget) { size_t free_b = 0, total_b = 0; DEV_TRY(hipMemGetInfo(&free_b, &total_b)); budget = free_b / 2; }
-    std::vector<CPass> passes;
-    std::vector<uint32_t> stream_of;                            // streams: the stream of every frame; a pass holds whole streams
-    if (cx) { stream_of.resize(n); for (uint32_t q = 0; q < cx->n_streams; ++q) for (uint64_t f = cx->first[q]; f < cx->first[q + 1]; ++f) stream_of[(size_t)f] = q; }
-    for (uint32_t f0 = 0; f0 < n;) {
-        size_t sum = 0; uint32_t f1 = f0;
-        while (f1 < n) {
-            const uint32_t e = cx ? (uint32_t)cx->first[stream_of[f1] + 1] : f1 + 1;
-            size_t add = 0;
-            for (uint32_t f = f1; f < e; ++f) add += need[f];
-            if (f1 != f0 && sum + add > budget) break;
-            sum += add; f1 = e;
-        }
-        CPass P; P.f0 = f0; P.f1 = f1;
-        passes.push_back(std::move(P));
-        f0 = f1;
-    }
+    // ---- passes of the memory budget (frame_jobs.h's split_passes); a frame whose scratch alone is over it is a pass of its own;
+    //      streams: a pass holds whole streams
+    size_t budget = 0;
+    RC_TRY(pass_budget(st, &budget));
+    const std::vector<uint32_t> stream_of = cx ? streams_of(cx->n_streams, cx->first) : std::vector<uint32_t>();
+    std::vector<uint32_t> group_end(stream_of.size());
+    for (size_t f = 0; f < group_end.size(); ++f) group_end[f] = (uint32_t)cx->first[stream_of[f] + 1];
+    std::vector<std::pair<uint32_t, uint32_t>> cuts;
+    lzf_frame_jobs::split_passes(need.data(), n, budget, cx ? group_end.data() : nullptr, cuts);
+    std::vector<CPass> passes(cuts.size());
+    for (size_t p = 0; p < cuts.size(); ++p) { passes[p].f0 = cuts[p].first; passes[p].f1 = cuts[p].second; }
     // ---- work allocation (output slots | copies | linked tables), shared by the passes (stream order: pass p + 1 compresses
     //      after pass p's payload copy); the template table of a dictionary of >= 8 bytes
     size_t work_bytes = 0;
@@ -1014,8 +985,8 @@ int compress_frames(const lzf_settings* s, const uint32_t n, const uint8_t* cons
         RC_TRY(lzf_table_seed_from_dictionary(d_tmpl, d_dict, dict_len, st));
     }
     // ---- jobs, copies and descriptors of every pass into one image
-    Image img; Scratch scr;
-    const size_t i_hdr = hdrs.empty() ? img.add(hdr, sizeof hdr) : img.add(hdrs.data(), hdrs.size());
+    Meta meta(st);
+    const size_t i_hdr = hdrs.empty() ? meta.add(hdr, sizeof hdr) : meta.add(hdrs);
     for (CPass& P : passes) {
         uint8_t* const dslots = work.at<uint8_t>(0);
         uint8_t* const dcopies = work.at<uint8_t>(up256(P.slots));
@@ -1086,40 +1057,34 @@ int compress_frames(const lzf_settings* s, const uint32_t n, const uint8_t* cons
             }
             fd.push_back(d);
         }
-        P.n_segs = (uint32_t)segs.size(); P.i_segs = img.add(segs.data(), sizeof(CSeg) * segs.size());
+        P.n_segs = (uint32_t)segs.size(); P.i_segs = meta.add(segs);
         P.n_copies = (uint32_t)cps.size(); P.n_hash = (uint32_t)hptr.size(); P.n_frames = (uint32_t)fd.size();
-        P.i_jobs = img.add(jobs.data(), sizeof(lzf_compress_job) * jobs.size());
-        P.i_tabptr = img.add(tabptr.data(), sizeof(void*) * tabptr.size()); P.i_adds = img.add(adds.data(), 8 * adds.size());
-        P.i_cps = img.add(cps.data(), 8 * cps.size()); P.i_cpd = img.add(cpd.data(), 8 * cpd.size()); P.i_cpl = img.add(cpl.data(), 8 * cpl.size());
-        P.i_tps = img.add(tps.data(), 8 * tps.size()); P.i_tpd = img.add(tpd.data(), 8 * tpd.size()); P.i_tpl = img.add(tpl.data(), 8 * tpl.size());
-        P.i_frames = img.add(fd.data(), sizeof(CFrameDesc) * fd.size()); P.i_blks = img.add(blks.data(), sizeof(CBlkDesc) * blks.size());
-        P.i_hptr = img.add(hptr.data(), 8 * hptr.size()); P.i_hlen = img.add(hlen.data(), 8 * hlen.size());
+        P.i_jobs = meta.add(jobs);
+        P.i_tabptr = meta.add(tabptr); P.i_adds = meta.add(adds);
+        P.i_cps = meta.add(cps); P.i_cpd = meta.add(cpd); P.i_cpl = meta.add(cpl);
+        P.i_tps = meta.add(tps); P.i_tpd = meta.add(tpd); P.i_tpl = meta.add(tpl);
+        P.i_frames = meta.add(fd); P.i_blks = meta.add(blks);
+        P.i_hptr = meta.add(hptr); P.i_hlen = meta.add(hlen);
         const size_t n_at = (bsum ? (size_t)P.n_jobs : 0) + P.n_hash;
-        P.s_res = scr.add(sizeof(lzf_job_result) * (size_t)P.n_jobs);
-        P.s_rsrc = scr.add(8 * (size_t)P.n_jobs); P.s_rdst = scr.add(8 * (size_t)P.n_jobs); P.s_rlen = scr.add(8 * (size_t)P.n_jobs);
-        P.s_at = scr.add(8 * n_at); P.s_val = scr.add(4 * n_at);
+        P.s_res = meta.room(sizeof(lzf_job_result) * (size_t)P.n_jobs);
+        P.s_rsrc = meta.room(8 * (size_t)P.n_jobs); P.s_rdst = meta.room(8 * (size_t)P.n_jobs); P.s_rlen = meta.room(8 * (size_t)P.n_jobs);
+        P.s_at = meta.room(8 * n_at); P.s_val = meta.room(4 * n_at);
     }
-    // ---- one upload, then the launches of every pass
-    const size_t img_bytes = img.h.size();
-    PoolAlloc meta(st);
-    if (!meta.get(img_bytes + scr.total)) { (void)hipStreamSynchronize(st); return LZF_E_HIP; }
-    hipEvent_t uploaded = nullptr;
-    DEV_TRY(hipEventCreateWithFlags(&uploaded, hipEventDisableTiming));
-    struct EventOwner { hipEvent_t e; ~EventOwner() { if (e) (void)hipEventDestroy(e); } } owner{uploaded};
-    DEV_TRY(hipMemcpyAsync(meta.p, img.h.data(), img_bytes, hipMemcpyHostToDevice, st));
-    DEV_TRY(hipEventRecord(uploaded, st));
-    auto I = [&](size_t off) { return meta.at<uint8_t>(off); };
-    auto S = [&](size_t off) { return meta.at<uint8_t>(img_bytes + off); };
+    // ---- one upload, then the launches of every pass (the kernels write every scratch entry they read: no zeroing)
+    RC_TRY(meta.upload(false));
     const uint32_t flags = (bsum ? kBlockSums : 0u) | (csum ? kContentSum : 0u);
     for (CPass& P : passes) {
-        lzf_compress_job* const jobs = reinterpret_cast<lzf_compress_job*>(I(P.i_jobs));
-        lzf_job_result* const res = reinterpret_cast<lzf_job_result*>(S(P.s_res));
+        lzf_compress_job* const jobs = meta.img<lzf_compress_job>(P.i_jobs);
+        lzf_job_result* const res = meta.scr<lzf_job_result>(P.s_res);
+        const uint8_t* const* const r_src = meta.scr<const uint8_t* const>(P.s_rsrc);
+        uint8_t* const* const r_dst = meta.scr<uint8_t* const>(P.s_rdst);
+        const uint64_t* const r_len = meta.scr<const uint64_t>(P.s_rlen);
         if (P.n_copies)
-            RC_TRY(lzf_copy_ranges(reinterpret_cast<const uint8_t* const*>(I(P.i_cps)), reinterpret_cast<uint8_t* const*>(I(P.i_cpd)),
-                                   reinterpret_cast<const uint64_t*>(I(P.i_cpl)), P.n_copies, dict_len > bs ? dict_len : bs, st));
+            RC_TRY(lzf_copy_ranges(meta.img<const uint8_t* const>(P.i_cps), meta.img<uint8_t* const>(P.i_cpd), meta.img<const uint64_t>(P.i_cpl), P.n_copies,
+                                   dict_len > bs ? dict_len : bs, st));
         if (P.n_linked) {                                       // :213-214 table = template.clone() (U32Table::default() without one)
-            if (d_tmpl) RC_TRY(lzf_copy_ranges(reinterpret_cast<const uint8_t* const*>(I(P.i_tps)), reinterpret_cast<uint8_t* const*>(I(P.i_tpd)),
-                                               reinterpret_cast<const uint64_t*>(I(P.i_tpl)), P.n_linked, sizeof(lzf_u32_table), st));
+            if (d_tmpl) RC_TRY(lzf_copy_ranges(meta.img<const uint8_t* const>(P.i_tps), meta.img<uint8_t* const>(P.i_tpd), meta.img<const uint64_t>(P.i_tpl),
+                                               P.n_linked, sizeof(lzf_u32_table), st));
             else DEV_TRY(hipMemsetAsync(work.at<uint8_t>(up256(P.slots) + up256(P.copies)), 0, P.tables, st));
         }
         if (P.n_jobs && indep) RC_TRY(lzf_compress_batch(jobs, res, P.n_jobs, LZF_KINDS_U32 | LZF_KINDS_U32_FRESH_ONLY, st));
@@ -1127,35 +1092,27 @@ int compress_frames(const lzf_settings* s, const uint32_t n, const uint8_t* cons
             for (size_t k = 0; k + 1 < P.step_off.size(); ++k) {    // no host round trip between the steps
                 const size_t a = P.step_off[k], c = P.step_off[k + 1] - a;
                 if (!c) continue;
-                if (k > 0) RC_TRY(lzf_table_offset_batch(reinterpret_cast<void* const*>(I(P.i_tabptr)) + a, reinterpret_cast<const uint64_t*>(I(P.i_adds)) + a,
-                                                         (uint32_t)c, LZF_TABLE_U32, st));
+                if (k > 0) RC_TRY(lzf_table_offset_batch(meta.img<void* const>(P.i_tabptr) + a, meta.img<const uint64_t>(P.i_adds) + a, (uint32_t)c, LZF_TABLE_U32, st));
                 RC_TRY(lzf_compress_batch(jobs + a, res + a, (uint32_t)c, LZF_KINDS_U32, st));
             }
         }
         const size_t n_sums = bsum ? (size_t)P.n_jobs : 0;
-        uint8_t** const at = reinterpret_cast<uint8_t**>(S(P.s_at));
-        uint32_t* const val = reinterpret_cast<uint32_t*>(S(P.s_val));
+        uint8_t** const at = meta.scr<uint8_t*>(P.s_at);
+        uint32_t* const val = meta.scr<uint32_t>(P.s_val);
         if (cx)
-            KERNEL(lzf_stream_pack_kernel, dim3(P.n_segs), dim3(64), 0, st, reinterpret_cast<const CSeg*>(I(P.i_segs)),
-                   reinterpret_cast<CFrameDesc*>(I(P.i_frames)), reinterpret_cast<const CBlkDesc*>(I(P.i_blks)), (const lzf_job_result*)res,
-                   hdr_len, flags, cx->s_status, cx->s_out_len);
-        KERNEL(lzf_frame_assemble_kernel, dim3(P.n_frames), dim3(64), 0, st,
-               reinterpret_cast<const CFrameDesc*>(I(P.i_frames)), reinterpret_cast<const CBlkDesc*>(I(P.i_blks)), (const lzf_job_result*)res,
-               (const uint8_t*)I(i_hdr), hdr_len, flags,
-               reinterpret_cast<const uint8_t**>(S(P.s_rsrc)), reinterpret_cast<uint8_t**>(S(P.s_rdst)), reinterpret_cast<uint64_t*>(S(P.s_rlen)),
-               at, at + n_sums, d_status, d_out_len);
-        if (P.n_jobs)
-            RC_TRY(lzf_copy_ranges(reinterpret_cast<const uint8_t* const*>(S(P.s_rsrc)), reinterpret_cast<uint8_t* const*>(S(P.s_rdst)),
-                                   reinterpret_cast<const uint64_t*>(S(P.s_rlen)), P.n_jobs, bs, st));
-        if (n_sums)
-            RC_TRY(lzf_xxh32_batch(reinterpret_cast<const uint8_t* const*>(S(P.s_rsrc)), reinterpret_cast<const uint64_t*>(S(P.s_rlen)), val, (uint32_t)n_sums, st));
+            KERNEL(lzf_stream_pack_kernel, dim3(P.n_segs), dim3(64), 0, st, meta.img<const CSeg>(P.i_segs), meta.img<CFrameDesc>(P.i_frames),
+                   meta.img<const CBlkDesc>(P.i_blks), (const lzf_job_result*)res, hdr_len, flags, cx->s_status, cx->s_out_len);
+        KERNEL(lzf_frame_assemble_kernel, dim3(P.n_frames), dim3(64), 0, st, meta.img<const CFrameDesc>(P.i_frames), meta.img<const CBlkDesc>(P.i_blks),
+               (const lzf_job_result*)res, meta.img<const uint8_t>(i_hdr), hdr_len, flags,
+               meta.scr<const uint8_t*>(P.s_rsrc), meta.scr<uint8_t*>(P.s_rdst), meta.scr<uint64_t>(P.s_rlen), at, at + n_sums, d_status, d_out_len);
+        if (P.n_jobs) RC_TRY(lzf_copy_ranges(r_src, r_dst, r_len, P.n_jobs, bs, st));
+        if (n_sums) RC_TRY(lzf_xxh32_batch(r_src, r_len, val, (uint32_t)n_sums, st));
         if (P.n_hash)                                           // (on the caller's stream: a forked checksum stream did not pay)
-            RC_TRY(lzf_xxh32_batch(reinterpret_cast<const uint8_t* const*>(I(P.i_hptr)), reinterpret_cast<const uint64_t*>(I(P.i_hlen)), val + n_sums, P.n_hash, st));
+            RC_TRY(lzf_xxh32_batch(meta.img<const uint8_t* const>(P.i_hptr), meta.img<const uint64_t>(P.i_hlen), val + n_sums, P.n_hash, st));
         const size_t n_at = n_sums + P.n_hash;
         if (n_at) KERNEL(lzf_frame_patch_kernel, dim3((uint32_t)((n_at + 255u) / 256u)), dim3(256), 0, st, (uint8_t* const*)at, (const uint32_t*)val, (uint32_t)n_at);
     }
-    DEV_TRY(hipEventSynchronize(uploaded));                     // the image has left host memory; the launches run on
-    return LZF_OK;
+    return meta.wait();                                         // the image has left host memory; the launches run on
 }
 }  // namespace
 

@@ -6,19 +6,45 @@
 // block_out_bound + input length (the limit plus what the literals may overshoot); a linked frame is one stream
 // buffer that lzf_chain_decompress_step grows block after block, with the dictionary as every job's prefix (:239-245).
 // Stored blocks get no job: independent ones are read straight from the input, linked ones are appended by the chain step.
+//
+// split_passes is the one planner of the memory budget: the four *_many drivers cut their frames into passes with it.
 #ifndef LZF_FRAME_JOBS_H
 #define LZF_FRAME_JOBS_H
 
+#include <cassert>
 #include <cstdint>
 #include <cstring>
+#include <utility>
 #include <vector>
 #include "../../include/lzfear_frame.h"
+#include "lzf_frame_scan.h"
 
 namespace lzf_frame_jobs {
 
 inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-// the most a block of `len` compressed bytes can decode to: every byte a 255-run length byte (raw/decompress.rs:40-56)
-inline size_t block_out_bound(size_t bmax, size_t len) { const size_t e = 255 * len + 16; return e < bmax ? e : bmax; }
+using lzf_scan::block_out_bound;    // the most a block of `len` compressed bytes can decode to (lzf_frame_scan.h)
+
+// The passes of a call under a memory budget: frames [0, n), frame f asking for need[f] bytes, go through in passes [first, second)
+// of whole groups, in order.  Groups are taken greedily while the running sum stays within the budget; the first group of a pass
+// is always taken, so a group over the budget alone is a pass of its own (the caller sees that from the pass and `need`).
+// group_end[f] = one past the last frame of f's group, for every f; NULL: every frame is its own group.
+inline void split_passes(const size_t* need, uint32_t n, size_t budget, const uint32_t* group_end,
+                         std::vector<std::pair<uint32_t, uint32_t>>& passes) {
+    passes.clear();
+    for (uint32_t f0 = 0; f0 < n;) {
+        size_t sum = 0; uint32_t f1 = f0;
+        while (f1 < n) {
+            const uint32_t e = group_end ? group_end[f1] : f1 + 1;
+            assert(e > f1 && e <= n);                             // a group ends behind its frames and inside the call
+            size_t add = 0;
+            for (uint32_t f = f1; f < e; ++f) add += need[f];
+            if (f1 != f0 && (add > budget || sum > budget - add)) break;
+            sum += add; f1 = e;
+        }
+        passes.emplace_back(f0, f1);
+        f0 = f1;
+    }
+}
 
 struct BlockRef { const uint8_t* src; uint32_t len; bool compressed; };    // src: device address of the block's bytes
 struct Frame {

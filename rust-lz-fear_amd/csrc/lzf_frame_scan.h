@@ -3,14 +3,17 @@
 //   read_header   LZ4FrameReader::new, src/framed/decompress.rs:102-161 (header.rs:29-81 for FLG / BD)
 //   walk_blocks   the u32 length hops of decode_block, src/framed/decompress.rs:198-235
 //
-// The device frame layer (frame_device.hip) runs both in its scan kernel, one lane per frame; the CPU tests compile this header
-// with g++ (tests/emu/emu_frame_scan.cpp) and hold it to the reference's statuses and `consumed` on the decode corpus.  No
+// This is the frame layer's only walk.  The device frame layer (frame_device.hip) runs it in its scan kernels, one lane per
+// frame; the host driver (frame.cpp) runs it over the caller's bytes: lzf_frame_read_header and lzf_frame_decompress_many through
+// both, the block-by-block reader through a walk_blocks that stops behind its one block.  The CPU tests compile this header with g++
+// (tests/emu/emu_frame_scan.cpp) and hold it to the reference's statuses and `consumed` on the decode corpus.  No
 // alignment is assumed: frames start anywhere, every multi-byte field is read bytewise.  Status codes are those of
 // include/lzfear_frame.h.
 #ifndef LZF_FRAME_SCAN_H
 #define LZF_FRAME_SCAN_H
 
 #include <stdint.h>
+#include <type_traits>
 
 #if defined(__HIPCC__) || defined(__HIP__)
 #define LZF_SCAN_HD __host__ __device__
@@ -90,7 +93,10 @@ struct Walk {
 };
 
 // decompress.rs:205-235: length word (EndMark and content checksum word :206-215, stored bit :217-218, bl > block_maxsize
-// :220-222), payload (:224-226), block checksum word (:228-230).  on_block(const Block&) is called for every block found.
+// :220-222), payload (:224-226), block checksum word (:228-230).  on_block(const Block&) is called for every block found; one
+// that returns bool ends the walk behind the block for which it returns false (status OK, no EndMark, consumed = the block's
+// end_off): the block-by-block reader takes its one block so.  The walk starts at h.header_len and reads h.flags and
+// h.block_maxsize, nothing else of the header.
 template <class OnBlock>
 LZF_SCAN_HD inline Walk walk_blocks(const uint8_t* in, uint64_t in_len, const Header& h, OnBlock&& on_block) {
     Walk w{OK, 0, false, 0};
@@ -113,7 +119,8 @@ LZF_SCAN_HD inline Walk walk_blocks(const uint8_t* in, uint64_t in_len, const He
             b.want_sum = rd32(in + r); r += 4;
         }
         b.end_off = r;
-        on_block(b);
+        if constexpr (std::is_same<decltype(on_block(b)), bool>::value) { if (!on_block(b)) break; }
+        else on_block(b);
     }
     w.consumed = r;
     return w;

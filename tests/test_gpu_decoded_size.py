@@ -483,6 +483,20 @@ def test_frames_that_stop_early():
     assert [tuple(g) for g in frame_sizes([bytes(csum)])] == [(0, len(data), len(f))]
 
 
+def test_frames_of_65_blocks_cross_the_delivery_round():
+    """65 blocks of 64 KiB per frame, independent and linked, block checksums on: the count-only delivery takes 64 blocks per
+    round, block 64 is counted behind the first round's total.  Whole frames, and the last block's checksum damaged: the frame
+    stops in the second round with 64 blocks counted."""
+    data = synth.silesia_mix(9 << 20, (9 << 20) + 65 * 65536).tobytes()
+    frames = [o.frame_compress(data, o.make_settings(block_size=64 << 10, block_checksums=True, independent_blocks=ib))[1] for ib in (True, False)]
+    for f in list(frames):
+        b = bytearray(f); b[-9] ^= 1                      # (... block 64 | its checksum | EndMark | content checksum)
+        frames.append(bytes(b))
+    dec = check_frames(frames, label="65 blocks")
+    assert dec == [tuple(x if i != 1 else len(x) for i, x in enumerate(o.frame_decompress(f))) for f in frames]
+    assert [d[:2] for d in dec] == [(0, len(data))] * 2 + [(o.F_BLOCK_CHECKSUM_FAIL, 64 * 65536)] * 2
+
+
 def test_frames_decode_corpus():
     files = fuzz_corpus("decode")
     assert len(files) == 830

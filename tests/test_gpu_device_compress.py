@@ -123,6 +123,20 @@ def test_mixed_frames_one_call(bs, bsum):
         assert launch == "lzf_compress_team_kernel", launch
 
 
+@pytest.mark.parametrize("indep", [True, False])
+def test_frames_of_65_blocks_cross_the_assembly_round(indep):
+    """65 blocks of 64 KiB per frame, block checksums on: the assembly kernel places 64 blocks per round, so block 64's length
+    word goes behind the first round's total (the carry of the wave scan).  Text, and text with the last block stored (random
+    bytes: its span differs from its neighbours'), in one call."""
+    mix = synth.silesia_mix(9 << 20, (9 << 20) + 65 * 65536).tobytes()
+    datas = [mix, mix[:64 * 65536] + vectors.rng_bytes(65, 65536)]
+    kw = dict(block_size=64 << 10, block_checksums=True, independent_blocks=indep)
+    st, ol, outs = check_against_host(gsettings(**kw), datas, oracle=kw)
+    assert st == [0, 0]
+    for d, n, t in zip(datas, ol, outs):
+        assert framed.decompress_frame(t[:n].cpu().numpy().tobytes()) == d
+
+
 def test_dictionaries():
     """A 70 000-byte dictionary with an id for independent and linked blocks, linked streams of 1, 2 and 17 blocks in one call,
     and a 4-byte dictionary."""

@@ -125,6 +125,30 @@ def test_capacity_edges():
         assert run([f], caps=[b]) == [o.frame_decompress(f)]
 
 
+def test_frames_of_65_blocks_cross_the_delivery_round():
+    """65 blocks of 64 KiB per frame, independent and linked, block checksums on: the delivery kernel takes 64 blocks per round,
+    so block 64 goes behind the first round's total (the carry of the wave scan).  Whole frames; the last block's checksum
+    damaged, which stops the frame in the second round with the first round's 64 blocks delivered; and capacities that end
+    inside block 63, between the rounds, and inside block 64."""
+    data = synth.silesia_mix(9 << 20, (9 << 20) + 65 * 65536).tobytes()
+    frames = [o.frame_compress(data, o.make_settings(block_size=64 << 10, block_checksums=True, independent_blocks=ib))[1] for ib in (True, False)]
+    damaged = []
+    for f in frames:
+        b = bytearray(f); b[-9] ^= 1                      # (... block 64 | its checksum | EndMark | content checksum)
+        damaged.append(bytes(b))
+    got = run(frames + damaged)
+    for f, g in zip(frames + damaged, got):
+        assert g == o.frame_decompress(f)
+    assert [g[:2] for g in got[:2]] == [(0, data)] * 2
+    assert [(g[0], len(g[1])) for g in got[2:]] == [(19, 64 * 65536)] * 2
+    caps = [64 * 65536 - 1, 64 * 65536, 64 * 65536 + 1, 65 * 65536 - 1, 65 * 65536]
+    for f in frames:
+        capped = run([f] * len(caps), caps=caps)
+        assert capped == framed.decompress_frames([f] * len(caps), caps=caps, with_consumed=True)
+        assert [g[0] for g in capped] == [ffi.OUT_CAPACITY] * 4 + [0]
+        assert [len(g[1]) for g in capped] == [63 * 65536, 64 * 65536, 64 * 65536, 64 * 65536, 65 * 65536]
+
+
 @pytest.mark.parametrize("poison", [0xA5, 0x5A])
 def test_red_zones(poison):
     rng = np.random.default_rng(poison)

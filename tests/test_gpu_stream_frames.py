@@ -329,6 +329,22 @@ def test_compress_streams_are_the_host_frames_concatenated():
                 assert pos == len(b)
 
 
+@pytest.mark.parametrize("indep", [True, False])
+def test_compress_streams_of_65_frames_cross_the_packing_round(indep):
+    """65 frames of one 64 KiB block per stream, block checksums on: the packing kernel places 64 frames per round, so frame 64
+    goes behind the first round's total (the carry of the wave scan); the stream decode then places the same 65 frames.  A
+    second stream of 66 pieces, the last one short, in the same call."""
+    mix = synth.silesia_mix(80 << 20, (80 << 20) + 65 * 65536 + 1234).tobytes()
+    datas = [mix[:65 * 65536], mix]
+    fb = 64 << 10
+    cs = settings(64 << 10, indep, True)
+    got = cs.compress_streams_device([dev(d) for d in datas], fb)
+    for d, t, nf in zip(datas, got, (65, 66)):
+        b = bytes(t.cpu().numpy().tobytes())
+        assert b == host_stream(cs, d, fb, False)
+        assert run([b]) == [ref_stream(b, ocap=1 << 20)] == [(0, d, len(b), nf)]
+
+
 @pytest.mark.parametrize("in_poison", [0x00, 0xFF])
 def test_compress_capacity_edge_under_red_zones(in_poison):
     """out_cap one below lzf_frame_compress_stream_bound: LZF_OUT_CAPACITY and not a byte written; at the bound: the stream, and
