@@ -375,10 +375,11 @@ int seg_decompress(const lzf_decompress_job* d_jobs, lzf_job_result* d_results, 
 }
 
 // ---- the bitmap-fed kernel (lz4_decompress_fed.hip): batches beyond the segmented pipeline's ----------------------------------
-// plan + parse + seam of the segmented pipeline over the whole batch (the token bit map of every block: one bit per compressed
-// byte), then one wavefront per block that lists its tokens from the map and copies — the in-kernel parse of the pair kernel is
+// plan + parse of the segmented pipeline over the whole batch (the token bit map of every block: one bit per compressed byte;
+// no seam stage — the fed wavefront carries the true chain and masks or walks what a chunk's parse marked before it fell in step),
+// then one wavefront per block that lists its tokens from the map and copies — the in-kernel parse of the pair kernel is
 // 13.0 of its 27.8 wave-instructions per sequence, the hop parse 3.8 — then the pair kernel over whatever that left (errors,
-// sizes outside the map's window, a chain that did not verify).
+// sizes outside the map's window).  The launch order comes from the parse as well: it counts every job's tokens.
 constexpr auto k_fed32 = lzf::lzf_decompress_fed_kernel<4096, 32, 352>;
 constexpr uint32_t kFedMinInDefault = 65536u;                        // per job: smaller inputs are left to the pair kernel behind the fed kernel
 // per call: a caller that bounds its inputs (lzf_decompress_batch_sized, the frame layer) keeps batches of small blocks off this path
@@ -444,14 +445,17 @@ FedGeometry fed_geometry(hipStream_t st) {
     by_dev[dev] = answer;
     return answer;
 }
-// A call (or one half of it) in two steps: FRONT = scratch + plan, parse, seam (the bit maps); BACK = the copy stage fed from them and
-// the pair kernel over what is left, then the scratch goes back.  The two steps may run on different streams (the caller orders them).
+// A call (or one half of it) in two steps: FRONT = scratch + plan, parse (the bit maps) and, from the parse's token counts, the launch
+// order; BACK = the copy stage fed from them and the pair kernel over what is left, then the scratch goes back.  The two steps may run
+// on different streams (the caller orders them).
 struct FedCall {
     SegScratch s; const lzf_decompress_job* jobs = nullptr; lzf_job_result* res = nullptr; uint32_t n = 0; const uint32_t* perm = nullptr;
     size_t o_tick = 0, o_fst = 0; bool live = false;
 };
-// false: the pair kernel takes these jobs (no room for the bit maps)
-int fed_front(FedCall& f, const lzf_decompress_job* d_jobs, lzf_job_result* d_results, uint32_t n, const uint32_t* perm, hipStream_t st, uint64_t max_in_hint) {
+// !f.live afterwards: the pair kernel takes these jobs (no room for the bit maps), and nothing was launched.
+// perm + est (both or neither): the launch order is wanted and nobody has worked it out yet — est[] is filled here, by the plan stage
+// (the bytes' share) and the parse (the sequences: exact, where lzf_decompress_cost_kernel samples), and perm[] ordered by it.
+int fed_front(FedCall& f, const lzf_decompress_job* d_jobs, lzf_job_result* d_results, uint32_t n, uint32_t* perm, uint32_t* est, uint32_t len_shift, hipStream_t st, uint64_t max_in_hint) {
     f.jobs = d_jobs; f.res = d_results; f.n = n; f.perm = perm; f.live = false;
     lzf::seg_ctx& c = f.s.ctx;
     c = lzf::seg_ctx{};
@@ -462,13 +466,12 @@ int fed_front(FedCall& f, const lzf_decompress_job* d_jobs, lzf_job_result* d_re
     c.maxtile = (max_in + lzf::kSegTile - 1u) / lzf::kSegTile;
     c.n_cu = cu_count();
     c.g_off = 0u; c.g_n = n; c.fed = 1u;
+    c.est = perm ? est : nullptr; c.len_shift = len_shift;
     size_t off = 0;
     auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
     const size_t o_st = take(sizeof(lzf::seg_job) * (size_t)n);
     const size_t o_top = take(sizeof(unsigned long long));
-    const size_t o_x = take(sizeof(uint32_t) * (size_t)n * c.maxch);
-    const size_t o_vf = take(sizeof(uint32_t) * (size_t)n * c.maxch);
-    const size_t o_bits = take(sizeof(uint32_t) * (size_t)n * c.maxch * lzf::kSegChunkWords);
+    const size_t o_bits = take(sizeof(uint32_t) * (size_t)n * c.maxch * lzf::kSegChunkWords);      // (no xexit, no vfrom: there is no seam stage on this path)
     f.o_tick = take(sizeof(uint32_t) * 32u * lzf::kFedTicketStride);
     f.o_fst = take(sizeof(lzf::fed_state) * (size_t)n);
     if (off > kFedMaxScratch) return LZF_OK;                         // (the pair kernel takes the call)
@@ -476,11 +479,13 @@ int fed_front(FedCall& f, const lzf_decompress_job* d_jobs, lzf_job_result* d_re
     uint8_t* b = static_cast<uint8_t*>(f.s.base);
     c.st = reinterpret_cast<lzf::seg_job*>(b + o_st);
     c.rec_top = reinterpret_cast<unsigned long long*>(b + o_top);
-    c.xexit = reinterpret_cast<uint32_t*>(b + o_x);
-    c.vfrom = reinterpret_cast<uint32_t*>(b + o_vf);
     c.bits = reinterpret_cast<uint32_t*>(b + o_bits);
     f.live = true;
-    const int rc = seg_launch(c, 3u, st);                            // plan, parse, seam
+    int rc = seg_launch(c, 2u, st);                                  // plan, parse
+    if (rc == LZF_OK && c.est) {
+        hipLaunchKernelGGL(lzf::lzf_order_by_estimate_kernel, dim3(1), dim3(1024), 0, st, (const uint32_t*)est, perm, n);
+        if (hipGetLastError() != hipSuccess) rc = LZF_E_HIP;
+    }
     if (rc != LZF_OK) { (void)hipFreeAsync(f.s.base, st); f.s.base = nullptr; f.live = false; g_last_error = "bitmap-fed decompress: launch failed"; }
     return rc;
 }
@@ -506,7 +511,11 @@ int fed_back(FedCall& f, hipStream_t st, uint32_t slots_per_cu) {
     if ((uint64_t)n * pieces > 0xFFFFFFF0ull) pieces = 1u;
     if (!fg.xcc_mask) pieces = 1u;
     int rc = LZF_OK;
-    lzf::fed_args a{f.jobs, f.res, c.st, c.bits, c.vfrom, f.perm, reinterpret_cast<lzf::fed_state*>(b + f.o_fst), reinterpret_cast<uint32_t*>(b + f.o_tick), fg.xcc_mask ? fg.xcc_mask : 1u, n, c.maxch, pieces, nullptr};
+    uint32_t carry = (uint32_t)kFedwCarry;
+#ifdef LZF_ANALYSIS      // LZF_FED_CARRY = the longest last batch of a window that is left for the next window (0: never; A/B)
+    { static const long e = [] { const char* v = getenv("LZF_FED_CARRY"); return v ? atol(v) : -1L; }(); if (e >= 0 && e < 64) carry = (uint32_t)e; }
+#endif
+    lzf::fed_args a{f.jobs, f.res, c.st, c.bits, f.perm, reinterpret_cast<lzf::fed_state*>(b + f.o_fst), reinterpret_cast<uint32_t*>(b + f.o_tick), fg.xcc_mask ? fg.xcc_mask : 1u, n, c.maxch, pieces, carry, nullptr};
     hipLaunchKernelGGL(lzf::lzf_fed_reset_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, a);
     hipLaunchKernelGGL(k_fed32, dim3(slots < n ? slots : n), dim3(64), pad, st, a);
     if (hipGetLastError() != hipSuccess) rc = LZF_E_HIP;
@@ -519,11 +528,11 @@ int fed_back(FedCall& f, hipStream_t st, uint32_t slots_per_cu) {
     if (rc != LZF_OK) g_last_error = "bitmap-fed decompress: launch failed";
     return rc;
 }
-int fed_decompress(const lzf_decompress_job* d_jobs, lzf_job_result* d_results, uint32_t n, const uint32_t* perm, hipStream_t st, bool* used, uint64_t max_in_hint) {
+int fed_decompress(const lzf_decompress_job* d_jobs, lzf_job_result* d_results, uint32_t n, uint32_t* perm, uint32_t* est, uint32_t len_shift, hipStream_t st, bool* used, uint64_t max_in_hint) {
     *used = false;
     if (n > kFedMaxJobs || max_in_hint <= fed_min_in() || max_in_hint <= fed_min_hint()) return LZF_OK;
     FedCall f;
-    int rc = fed_front(f, d_jobs, d_results, n, perm, st, max_in_hint);
+    int rc = fed_front(f, d_jobs, d_results, n, perm, est, len_shift, st, max_in_hint);
     if (rc != LZF_OK || !f.live) return rc;
     *used = true;
     return fed_back(f, st, 0u);
@@ -659,19 +668,26 @@ int lzf_decompress_batch_sized(const lzf_decompress_job* d_jobs, lzf_job_result*
         // perm[n] + est[n]: the jobs by their estimated cost, largest first
         if (hipMallocAsync(&perm_owner.p, 2u * sizeof(uint32_t) * (size_t)n_jobs, st) != hipSuccess) { (void)hipGetLastError(); perm_owner.p = nullptr; }   // (then: the caller's order)
         perm = static_cast<uint32_t*>(perm_owner.p);
-        if (perm) {
-            uint32_t* const est = perm + n_jobs;
-            uint32_t len_shift = 2u;       // a job's cost: its sequences + a quarter of its compressed bytes (measured: 403 GiB/s with the sequences alone, 414-418 with len >> 4 .. len >> 1)
-#ifdef LZF_ANALYSIS      // LZF_ORDER_LEN_SHIFT=k: the estimate + input length >> k (A/B of the cost proxy)
-            { static const uint32_t k = [] { const char* e = getenv("LZF_ORDER_LEN_SHIFT"); return e ? (uint32_t)atol(e) : 2u; }(); len_shift = k; }
-#endif
-            LAUNCH(lzf::lzf_decompress_cost_kernel, dim3(n_jobs), dim3(64), 0, st, d_jobs, n_jobs, est, len_shift);
-            LAUNCH(lzf::lzf_order_by_estimate_kernel, dim3(1), dim3(1024), 0, st, (const uint32_t*)est, perm, n_jobs);
-        }
     }
+    uint32_t* const est = perm ? perm + n_jobs : nullptr;
+    uint32_t len_shift = 2u;       // a job's cost: its sequences + a quarter of its compressed bytes (measured: 403 GiB/s with the sequences alone, 414-418 with len >> 4 .. len >> 1)
+#ifdef LZF_ANALYSIS      // LZF_ORDER_LEN_SHIFT=k: the estimate + input length >> k (A/B of the cost proxy)
+    { static const uint32_t k = [] { const char* e = getenv("LZF_ORDER_LEN_SHIFT"); return e ? (uint32_t)atol(e) : 2u; }(); len_shift = k; }
+#endif
+    // The estimates are sampled by a kernel of their own (three windows per job) — unless the call takes the bitmap-fed path, whose parse
+    // counts every job's tokens anyway (fed_front).  So the sampling waits until the path is known: it runs in front of whatever else is launched.
+    bool ordered = false;
+    auto order_by_sampling = [&]() -> int {
+        if (!perm || ordered) return LZF_OK;
+        ordered = true;
+        LAUNCH(lzf::lzf_decompress_cost_kernel, dim3(n_jobs), dim3(64), 0, st, d_jobs, n_jobs, est, len_shift);
+        LAUNCH(lzf::lzf_order_by_estimate_kernel, dim3(1), dim3(1024), 0, st, (const uint32_t*)est, perm, n_jobs);
+        return LZF_OK;
+    };
     const uint32_t* cperm = perm;
 #ifdef LZF_ANALYSIS
     if (forced != kVariantAuto) {
+        if ((rc = order_by_sampling()) != LZF_OK) { HIP_TRY(perm_owner.release()); return rc; }
         g_last_decompress = "analysis variant (LZF_DECOMPRESS_KERNEL)";
         rc = analysis_launch_decompress(forced, d_jobs, d_results, n_jobs, cperm, st);
         HIP_TRY(perm_owner.release());
@@ -688,6 +704,7 @@ int lzf_decompress_batch_sized(const lzf_decompress_job* d_jobs, lzf_job_result*
       if (mode == 2) seg_on = false; }
 #endif
     if (seg_on) {
+        if ((rc = order_by_sampling()) != LZF_OK) { HIP_TRY(perm_owner.release()); return rc; }
         bool used = false; uint32_t ring = 0;
         rc = seg_decompress(d_jobs, d_results, n_jobs, seg_min_in, st, &used, max_input_len, &ring);
         if (used) g_last_decompress = ring == 131072u ? "segmented: lzf_seg_resolve_pair_kernel<131072> + lzf_decompress_paired_kernel<4096,48,640>"      // (the ring the call really used)
@@ -712,10 +729,11 @@ int lzf_decompress_batch_sized(const lzf_decompress_job* d_jobs, lzf_job_result*
 #endif
     if (fed_on) {
         bool used = false;
-        rc = fed_decompress(d_jobs, d_results, n_jobs, cperm, st, &used, max_input_len);
+        rc = fed_decompress(d_jobs, d_results, n_jobs, perm, est, len_shift, st, &used, max_input_len);      // (declines: nothing launched, the order is still to make)
         if (used) g_last_decompress = "bitmap-fed: lzf_seg_parse_kernel + lzf_decompress_fed_kernel<4096,32,352> + lzf_decompress_paired_kernel<4096,24,384>";
         if (rc != LZF_OK || used) { HIP_TRY(perm_owner.release()); return rc; }
     }
+    if ((rc = order_by_sampling()) != LZF_OK) { HIP_TRY(perm_owner.release()); return rc; }
     g_last_decompress = n_jobs <= resident48 ? "lzf_decompress_paired_kernel<4096,48,640>" : n_jobs <= 8u * resident48 ? "lzf_decompress_paired_kernel<4096,24,384>"
                                                                                                              : "lzf_decompress_batched_kernel<4096,16,256,staged>";
     if (n_jobs <= resident48)

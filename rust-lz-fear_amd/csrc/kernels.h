@@ -7,6 +7,7 @@
 // rounds 2-4 left the tree in round 5: git tag r4-kernel-generations); nothing below an `#ifdef LZF_ANALYSIS` is in the product.
 #pragma once
 #include "lzf_device.h"
+#include "lzf_fed_window.h"
 
 namespace lzf {
 // perm (optional, everywhere below): launch index -> job index; capi.hip launches large batches longest job first
@@ -110,16 +111,22 @@ struct seg_ctx {
     // One group: g_off = 0, g_n = n_jobs, grouped = 0.
     uint32_t g_off, g_n, grouped;
     uint32_t res_prio;           // the resolve stage's wavefronts raise their issue priority (grouped calls: they share their SIMDs with the next group's records stage)
-    uint32_t fed;                // the plan / parse / seam stages serve the bitmap-fed kernel: prefix and existing output do not make a job ineligible
+    uint32_t fed;                // the plan / parse stages serve the bitmap-fed kernel: prefix and existing output do not make a job ineligible, no xexit is stored
+    // the launch order of a fed call (capi.hip): est[j] = the job's cost, written by the plan stage (input_len >> len_shift; a guess by
+    // length for a job the map does not cover) and counted up by the parse (every chunk adds the tokens it owns).  null: no order asked for
+    uint32_t* est;
+    uint32_t len_shift;
 };
 // ---------------------------------------------------------------------------------------------------------------------
-// Bitmap-fed decompress (lz4_decompress_fed.hip): batches beyond what the chip holds at once.  plan + parse + seam of the
-// segmented pipeline run over the whole batch (seg_ctx::fed: a job's prefix / existing output do not matter to the parse),
-// then one wavefront per block lists its tokens from the bit map — verifying the chain link by link — and copies.  A job the
-// kernel does not finish cleanly stays !done for the pair kernel launched behind it.
+// Bitmap-fed decompress (lz4_decompress_fed.hip): batches beyond what the chip holds at once.  plan + parse of the segmented
+// pipeline run over the whole batch (seg_ctx::fed: a job's prefix / existing output do not matter to the parse), then one
+// wavefront per block lists its tokens from the bit map — the marks below the chain's own position masked off, the chain verified
+// link by link, a window the map gets wrong walked token by token — and copies.  There is no seam stage on this path: the chain
+// the wavefront carries says from where a chunk's marks are the true tokens.  A job the kernel does not finish cleanly stays
+// !done for the pair kernel launched behind it.
 // ---------------------------------------------------------------------------------------------------------------------
 // decoder state a job's pieces hand on: flag = pieces finished so far (piece p starts when it reads p), kFedEnded once the job needs no more
-struct fed_state { uint32_t flag, cstart, expect, o; };
+struct fed_state { uint32_t flag, expect, o, pad; };
 constexpr uint32_t kFedEnded = 0x80000000u;
 constexpr uint32_t kFedTicketStride = 32u;      // (a counter per 128-byte line)
 struct fed_args {
@@ -127,13 +134,13 @@ struct fed_args {
     lzf_job_result* results;
     seg_job* st;
     const uint32_t* bits;        // seg_ctx::bits
-    const uint32_t* vfrom;       // seg_ctx::vfrom
     const uint32_t* perm;        // launch order: rank -> job (optional)
     fed_state* state;            // [n_jobs]
     uint32_t* ticket;            // the launch's ticket counters, one per XCD, kFedTicketStride words apart
     uint32_t xcc_mask;           // the XCDs the kernel's wavefronts run on (census): bit i = HW_REG_XCC_ID i
     uint32_t n_jobs, maxch;
     uint32_t pieces;             // every job goes through the kernel in this many pieces (1: whole)
+    uint32_t carry;              // analysis library (LZF_FED_CARRY): the longest last batch of a window that waits for the next one (the product: kFedwCarry)
     uint32_t* census;            // not null: the launch only counts how many of its workgroups the device holds at once ([0] arrivals, [1] the answer, [2] mask of their XCDs)
 };
 __global__ void lzf_fed_reset_kernel(fed_args a);
@@ -163,6 +170,7 @@ LZF_FED_VARIANTS(LZF_EXTF)
 __device__ __forceinline__ uint32_t seg_job_of(const seg_ctx& c, uint32_t i) { return c.by_len ? c.by_len[i + c.g_off] : i + c.g_off; }
 constexpr uint32_t kSegRegion = 256, kSegChunk = 64u * kSegRegion, kSegOverlap = 2048, kSegStride = kSegChunk - kSegOverlap;
 constexpr uint32_t kSegChunkWords = kSegChunk / 32u, kSegTile = 2048;
+static_assert(kSegChunk == (uint32_t)kFedwChunk && kSegOverlap == (uint32_t)kFedwOverlap && kSegStride == (uint32_t)kFedwStride, "lzf_fed_window.h restates the chunk geometry");
 __global__ void lzf_seg_plan_kernel(seg_ctx c);
 // batches of more than one block per CU: which workgroup of the resolve stage takes which job — the jobs ranked by their number of
 // sequences and dealt out in rows of n_cu, every other row reversed, so that the blocks that share a CU (workgroups k, k + n_cu,

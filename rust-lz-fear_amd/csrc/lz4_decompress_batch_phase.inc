@@ -3,18 +3,30 @@
 // Expects in scope: lane, in, out, prefix, len, plen, cap, limit, rb, ring, ring_a, RIDX(), ring_fill(), ring_flush(),
 // rdb(), rd4(), cstart, Tc (tokens listed for this chunk), o, safe, status, the constants RING, kSpanMax, kNearHist,
 // STAGE / cbuf_a / kCB (chunk staged in LDS or not) and the macro LZF_TOKEN_AT(i) = chunk offset of listed token i.
-// With LZF_FED_DECODE (the bitmap-fed kernel, lz4_decompress_feed_phase.inc) instead of rd4() and LZF_TOKEN_AT: toks (round
-// offsets, not yet verified), expect (where the chain's next token starts) and bail; the set-up then decodes each token once and
-// checks the chain's links before the batch writes anything (a broken link or UnexpectedEnd: bail, the loop ends).
+// With LZF_FED_DECODE (the bitmap-fed kernel, lz4_decompress_feed_phase.inc) instead of rd4() and LZF_TOKEN_AT: toks (window
+// offsets, not yet verified), expect (where the chain's next token starts), fed_carry and bail; the set-up then decodes each token
+// once and checks the chain's links before the batch writes anything (a broken link or UnexpectedEnd: bail, the loop ends with
+// `expect` on the failing batch's first token), and a short last batch of the list may be left for the next window.
             // =====================================================================
             // B. batches of up to 64 sequences: lane j owns token tidx + j
             // =====================================================================
             uint32_t tidx = 0;
-            if (LZF_DBG_SKIP & 1) { tidx = Tc; o += Tc; }      // (LZF_FED_DECODE: no decode either, the chain stops after one round)
+            if (LZF_DBG_SKIP & 1) { tidx = Tc; o += Tc; }      // (LZF_FED_DECODE: no decode either, the chain stops after one window)
+#if defined(LZF_FED_DECODE)
+            if (LZF_DBG_SKIP & 1) expect = len;
+#endif
             while (tidx < Tc && status == LZF_OK) {
+#if defined(LZF_FED_DECODE)
+                // a short batch at the end of the window's list waits for the next window, which starts on its first token and fills it
+                // up (lzf_fed_window.h); `expect` stands on that token.  Never the window's first batch: every window runs a batch.
+                if (lzf_fedw_carry(Tc, tidx, cstart + kRound, len, fed_carry)) break;
+#endif
                 PHASE(0);
 #if defined(LZF_DBG_ROUNDS) && defined(LZF_DBG_ROUNDS_HERE)
                 ++dbg_batches;
+#endif
+#if defined(LZF_FED_DECODE) && defined(LZF_DBG_FED_COUNT)
+                ++dbg_fed[0];
 #endif
                 const uint32_t ob0 = o;
                 const uint32_t nb_try = Tc - tidx < kWave ? Tc - tidx : kWave;

@@ -1,21 +1,25 @@
 // lz4_decompress_fed.hip — raw::decompress_raw (src/raw/decompress.rs:58-138) for batches beyond what the chip holds at once,
 // with the PARSE taken out of the block's own wavefronts: the token positions of every block of the batch come from the hop
-// parse of the segmented pipeline (lzf_seg_parse_kernel + lzf_seg_seam_kernel: one bit per compressed byte, 3.8
-// wave-instructions per sequence against the 13.0 of the in-kernel region parse of lz4_decompress_paired.hip), and the kernel
-// here only FEEDS its copy stage from that map (lz4_decompress_feed_phase.inc: bit map -> token list) and runs the COPY stage
-// (lz4_decompress_batch_phase.inc) with a set-up of its own (LZF_FED_DECODE: each listed token decoded once, the chain verified
-// link by link before a batch writes anything).
+// parse of the segmented pipeline (lzf_seg_parse_kernel: one bit per compressed byte, 3.8 wave-instructions per sequence against
+// the 13.0 of the in-kernel region parse of lz4_decompress_paired.hip), and the kernel here only FEEDS its copy stage from that
+// map (lz4_decompress_feed_phase.inc: bit map -> token list) and runs the COPY stage (lz4_decompress_batch_phase.inc) with a
+// set-up of its own (LZF_FED_DECODE: each listed token decoded once, the chain verified link by link before a batch writes
+// anything).  The seam stage of the segmented pipeline is not part of this path: the wavefront walks the true chain and carries
+// `expect`, the position of its next token, which says from where a chunk's marks are the true tokens; the few windows in which a
+// chunk's chain has not fallen in step yet are walked token by token (walk mode, lz4_decompress_feed_phase.inc).
 //
-//   lzf_decompress_fed_kernel<RING, W, TOKCAP>        one wavefront per block: feed a round of 32 * W compressed bytes, copy it
+//   lzf_decompress_fed_kernel<RING, W, TOKCAP>        one wavefront per block: feed a window of 32 * W compressed bytes from where
+//                                                     the chain stands, copy it; a short last batch waits for the next window
 //
 // Contract with the dispatch (capi.hip): a job is taken only when the plan stage found it eligible (sizes inside the bit map's
-// window) and the seam stage did not fail on it; a job is FINISHED here (results written, seg_job::done set) only when it decodes
-// cleanly over a verified chain.  Everything else — every DecodeError, a capacity problem, a chain that does not verify — is
-// left untouched for the pair kernel launched behind this one, which decodes the job from its first byte and reports the
-// reference's status.  What this kernel wrote into `out` before it gave up is a prefix of what that kernel writes again.
+// window); a job is FINISHED here (results written, seg_job::done set) only when it decodes cleanly over a verified chain.
+// Everything else — every DecodeError, a capacity problem — is left untouched for the pair kernel launched behind this one, which
+// decodes the job from its first byte and reports the reference's status.  What this kernel wrote into `out` before it gave up
+// is a prefix of what that kernel writes again.
 #include "lzf_device.h"
 #include "kernels.h"
 #include "lzf_copy_helpers.h"
+#include "lzf_fed_window.h"
 
 namespace lzf {
 
@@ -47,7 +51,7 @@ __global__ LZF_FED_BOUNDS void lzf_decompress_fed_kernel(fed_args a) {      // (
     constexpr uint32_t kNearHist = RING - kSpanMax;    // history before the batch that stays intact in the ring
     constexpr uint32_t kRound = 32u * (uint32_t)W;     // compressed bytes whose tokens one round lists
     constexpr uint32_t kCB = kRound + 128u;            // staged bytes: the round + room for the bodies of its last tokens
-    static_assert(W >= 1 && W <= 64 && (kSegTile % kRound) == 0, "a round is one bit-map word per lane and subdivides a tile");
+    static_assert(W >= 1 && W <= 64 && kRound == (uint32_t)kFedwRound, "a window is one bit-map word per lane (whose owner is worked out per word: lzf_fed_window.h)");
     static_assert(TOKCAP >= (int)(kRound / 3u + 1u), "a round's tokens (at least three bytes each) fit the list");
     static_assert(kCB % 16 == 0, "the round is staged in 16-byte pieces");
     __shared__ __attribute__((aligned(16))) uint8_t ring[RING];
@@ -100,6 +104,9 @@ __global__ LZF_FED_BOUNDS void lzf_decompress_fed_kernel(fed_args a) {      // (
 #ifdef LZF_DBG_PHASE_SEL
     long long ph_acc_out = 0;
 #endif
+#ifdef LZF_DBG_FED_COUNT   // analysis: [0] batches, [1] windows listed from the map, [2] windows walked, of this wave's share of the job (LZF_FED_PIECES=1: the job) -> results[].reserved
+    uint32_t dbg_fed[3] = {0u, 0u, 0u};
+#endif
     if (job.input_len >= kMaxPosB || job.out_existing_len >= kMaxPosB || job.prefix_len >= kMaxPosB || job.out_existing_len > job.out_cap) continue;   // (LZF_CONTRACT: the pair kernel says so)
     {
         cgu8* __restrict__ in = as_global(job.input);
@@ -112,7 +119,6 @@ __global__ LZF_FED_BOUNDS void lzf_decompress_fed_kernel(fed_args a) {      // (
         const uint32_t rb = (uint32_t)(reinterpret_cast<uintptr_t>(out) & 15u);   // ring bias
         const uint32_t ring_a = lds_addr(ring), cbuf_a = lds_addr(cbuf);
         const LZF_GLOBAL uint32_t* const fed_bits = (const LZF_GLOBAL uint32_t*)a.bits + (size_t)jid * a.maxch * kSegChunkWords;
-        const LZF_GLOBAL uint32_t* const fed_vf = (const LZF_GLOBAL uint32_t*)a.vfrom + (size_t)jid * a.maxch;
 #define RIDX(x) (((x) + rb) & kMask)
 
         // ring <- out[a, b)   (b - a <= RING; caller made out[a,b) visible)
@@ -141,7 +147,7 @@ __global__ LZF_FED_BOUNDS void lzf_decompress_fed_kernel(fed_args a) {      // (
         uint32_t expect = 0;                 // where the next token of the chain starts (len: the chain has ended)
         uint32_t cstart = 0;
         o = (uint32_t)job.out_existing_len;
-        // this piece: rounds [piece, piece + 1) * per of the job's input
+        // this piece: the tokens that start in rounds [piece, piece + 1) * per of the job's input
         const uint32_t rounds = (len + kRound - 1u) / kRound, per = (rounds + pieces - 1u) / pieces;
         const uint32_t piece_end = (piece + 1u) * per >= rounds ? len : (piece + 1u) * per * kRound;
         if (piece > 0u) {
@@ -155,7 +161,7 @@ __global__ LZF_FED_BOUNDS void lzf_decompress_fed_kernel(fed_args a) {      // (
             f = __builtin_amdgcn_readfirstlane(f);
             if (f != piece) continue;        // the job ended in an earlier piece (kFedEnded), or that piece never came: the pair kernel looks at what is left
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");       // (this compute unit's L1 may hold lines of `out` from an earlier piece of the job)
-            cstart = fs->cstart; expect = fs->expect; o = fs->o;
+            expect = fs->expect; o = fs->o;  // (a short batch the piece before left at its end is simply this piece's first)
         }
         uint32_t safe = o;   // out[0, safe) is visible to this wave's global loads
         if (o > 0) ring_fill(o > (uint32_t)RING ? o - RING : 0u, o);   // Vec content on entry (or what the other slot wrote) = history
@@ -166,9 +172,28 @@ __global__ LZF_FED_BOUNDS void lzf_decompress_fed_kernel(fed_args a) {      // (
 #else
 #define PHASE(i) do { } while (0)
 #endif
-        while (cstart < len && expect < len && status == LZF_OK) {
-            if (cstart >= piece_end) { parked = true; break; }      // the next piece's
-            __syncthreads();                 // (one wave: orders the re-use of cbuf / toks between rounds)
+#if defined(LZF_FED_FIXED_ROUNDS)
+        constexpr int kFixed = 1;
+        const uint32_t fed_carry = 0u;
+#elif defined(LZF_ANALYSIS)
+        constexpr int kFixed = 0;
+        const uint32_t fed_carry = a.carry < kWave ? a.carry : kWave - 1u;      // (LZF_FED_CARRY)
+#else
+        constexpr int kFixed = 0;
+        constexpr uint32_t fed_carry = kFedwCarry;
+#endif
+        bool fed_walk = false;               // this window is listed by walking the chain, not from the bit map
+        // INVARIANT of the loop: a pass either ends the job for this kernel (status, bailed), parks it, asks for the same window again
+        // in walk mode (once: a failure in walk mode ends the job), or runs at least one batch — a window's first batch is never
+        // carried, and a batch that passes its checks moves `expect` on by a token or more.  The last `if` holds the loop to that.
+        while (expect < len && status == LZF_OK) {
+            if (expect >= piece_end) { parked = true; break; }      // the next piece's
+            const uint32_t expect_in = expect;
+            cstart = lzf_fedw_start(expect, kFixed);
+            __syncthreads();                 // (one wave: orders the re-use of cbuf / toks between windows)
+#ifdef LZF_DBG_FED_COUNT
+            ++dbg_fed[fed_walk ? 2 : 1];
+#endif
 #include "lz4_decompress_feed_phase.inc"
             if (Tc) {
 #define LZF_FED_DECODE
@@ -179,12 +204,13 @@ __global__ LZF_FED_BOUNDS void lzf_decompress_fed_kernel(fed_args a) {      // (
 #undef LZF_FAR_LATE
 #undef LZF_FED_DECODE
             }
-            if (bail) { bailed = true; break; }
-            // the next round the chain has a token in
-            const uint32_t nx = expect & ~(kRound - 1u);
-            cstart = nx > cstart ? nx : cstart + kRound;
+            if (bail) {
+                if (fed_walk) { bailed = true; break; }              // the chain itself fails: the pair kernel reports it
+                fed_walk = true; continue;                           // the map is wrong about this window: walk it from `expect`
+            }
+            fed_walk = false;
+            if (expect == expect_in && status == LZF_OK) { bailed = true; break; }      // (no progress: never, by the invariant — and never a spin)
         }
-        if (!parked && status == LZF_OK && expect < len) bailed = true;      // the map ends before the chain does
 #ifdef LZF_DBG_PHASE_SEL
         ph_acc_out = ph_acc;
 #endif
@@ -192,7 +218,7 @@ __global__ LZF_FED_BOUNDS void lzf_decompress_fed_kernel(fed_args a) {      // (
 #undef RIDX
         if (parked && status == LZF_OK && !bailed) {
             // hand the job on: what this wave wrote must be visible to another compute unit before the flag is
-            if (lane == 0u) { fs->cstart = cstart; fs->expect = expect; fs->o = o; }
+            if (lane == 0u) { fs->expect = expect; fs->o = o; }
             // (no release fence: the next piece runs on this XCD and reads through the same L2 — the stores only have to have arrived there)
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -205,7 +231,9 @@ __global__ LZF_FED_BOUNDS void lzf_decompress_fed_kernel(fed_args a) {      // (
     if (lane == 0) {
         a.results[jid].out_len = o;
         a.results[jid].status = LZF_OK;
-#ifdef LZF_DBG_PHASE_SEL
+#ifdef LZF_DBG_FED_COUNT
+        a.results[jid].reserved = dbg_fed[LZF_DBG_FED_COUNT];
+#elif defined(LZF_DBG_PHASE_SEL)
         a.results[jid].reserved = (uint32_t)(ph_acc_out >> 10);
 #elif defined(LZF_DBG_TIMELINE)   // analysis: when the job ran, on the 100 MHz wall clock every wave reads alike (units of 2.56 us): start << 16 | end
         a.results[jid].reserved = (uint32_t)(((t_wall0 >> 8) & 0xFFFFull) << 16) | (uint32_t)((wall_clock64() >> 8) & 0xFFFFull);

@@ -153,6 +153,12 @@ __global__ __launch_bounds__(256) void lzf_seg_plan_kernel(seg_ctx c) {
     s.ntile = (len + kSegTile - 1u) / kSegTile;
     if (s.nch > c.maxch || s.ntile > c.maxtile) { s.eligible = 0; s.nch = 0; s.ntile = 0; }
     c.st[j] = s;
+    // the launch order of a fed call: the bytes' share of the job's cost; the parse adds the sequences, chunk by chunk.  A job the
+    // map does not cover gets a guess by its length (what lzf_decompress_cost_kernel says of an input too short to sample).
+    if (c.est) {
+        const uint32_t l31 = job.input_len > 0x7FFFFFFFull ? 0x7FFFFFFFu : (uint32_t)job.input_len;
+        c.est[j] = (s.eligible ? 0u : l31 >> 4) + (c.len_shift < 32u ? l31 >> c.len_shift : 0u);
+    }
 }
 
 // =====================================================================================================================
@@ -414,10 +420,20 @@ __global__ __launch_bounds__(64) void lzf_seg_parse_kernel(seg_ctx c) {
             }
             LZF_GLOBAL u32x4* dst = (LZF_GLOBAL u32x4*)(c.bits + ((size_t)j * c.maxch + h) * kSegChunkWords + lane * 8u);
             dst[0] = o0; dst[1] = o1;
-            const uint32_t xm = __builtin_amdgcn_readlane(wave_scan_max(X), 63);
-            uint64_t xe = (uint64_t)cstart + xm;
-            if (xe > len) xe = len;
-            if (lane == 0u) c.xexit[(size_t)j * c.maxch + h] = (uint32_t)xe;
+            if (!c.fed) {                                      // (the seam stage's input: the fed kernel carries the chain itself)
+                const uint32_t xm = __builtin_amdgcn_readlane(wave_scan_max(X), 63);
+                uint64_t xe = (uint64_t)cstart + xm;
+                if (xe > len) xe = len;
+                if (lane == 0u) c.xexit[(size_t)j * c.maxch + h] = (uint32_t)xe;
+            }
+            if (c.est) {
+                // the job's sequences for the launch order: the marks this chunk owns (chunk 0 its whole row, chunk h >= 1 from kSegOverlap
+                // on: the regions of lanes 8 ..), counted from the words just stored
+                uint32_t cnt = 0;
+                if (h == 0u || rb0 >= kSegOverlap) cnt = (uint32_t)(__popc(o0[0]) + __popc(o0[1]) + __popc(o0[2]) + __popc(o0[3]) + __popc(o1[0]) + __popc(o1[1]) + __popc(o1[2]) + __popc(o1[3]));
+                const uint32_t tot = __builtin_amdgcn_readlane(wave_scan_add(cnt), 63);
+                if (lane == 0u) __hip_atomic_fetch_add(&c.est[j], tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
         }
     }
 }

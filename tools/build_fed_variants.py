@@ -12,6 +12,7 @@ VARIANTS = {
     "r6": ["LZF_DBG_FED_WAVES=6"],                                          # the product's bound
     "r6late": ["LZF_DBG_FED_WAVES=6", "LZF_FED_FAR_LATE"],                  # far-match loads issued behind the literal copy
     "r7": ["LZF_DBG_FED_WAVES=7"],                                          # as many as the LDS admits (25 per CU)
+    "fixed": ["LZF_DBG_FED_WAVES=6", "LZF_FED_FIXED_ROUNDS"],               # 1 KiB-aligned rounds, no carried tails: the kernel before the windows followed the chain
 }
 KERNEL = "lzf_decompress_fed_kernel"
 
