@@ -1,0 +1,272 @@
+// capi_drivers.hip — the host drivers of the two multi-launch decompress paths: the segmented pipeline (lz4_decompress_seg.hip) and
+// the bitmap-fed kernel behind its plan + parse stages (lz4_decompress_fed.hip).  They execute a plan of lzf_dispatch.h; whether a
+// call comes here at all, with which ring and in which groups, is decided there.
+#include "capi_internal.h"
+#include "kernels.h"
+
+namespace lzf_capi __attribute__((visibility("hidden"))) {
+namespace {
+namespace d = lzf_dispatch;
+
+static_assert(sizeof(lzf::seg_job) == d::kSegJobBytes && sizeof(lzf::u32x4) == d::kSegRecBytes && sizeof(lzf::fed_state) == d::kFedStateBytes, "lzf_dispatch.h lays the scratch out with these sizes");
+static_assert(d::kFedTicketBytes == sizeof(uint32_t) * 32u * lzf::kFedTicketStride, "32 ticket counters");
+static_assert(d::kSegChunk == lzf::kSegChunk && d::kSegStride == lzf::kSegStride && d::kSegChunkWords == lzf::kSegChunkWords && d::kSegTile == lzf::kSegTile, "lzf_dispatch.h restates the chunk geometry");
+
+using lzf::k_paired48; using lzf::k_paired24;
+constexpr auto k_fed32 = lzf::lzf_decompress_fed_kernel<4096, 32, 352>;
+
+template <class T> T* area(const AsyncScratch& s, uint64_t off) { return reinterpret_cast<T*>(s.at(off)); }
+
+// what both paths' contexts share: the jobs, the sizes of the parse, the state array, the arena's top and the bit maps
+lzf::seg_ctx seg_ctx_of(const d::Geometry& geo, const lzf_decompress_job* d_jobs, lzf_job_result* d_results, uint32_t n, const d::SegDims& dim, uint32_t min_in,
+                        const AsyncScratch& s, uint64_t o_st, uint64_t o_top, uint64_t o_bits) {
+    lzf::seg_ctx c{};
+    c.jobs = d_jobs; c.results = d_results; c.n_jobs = n;
+    c.max_in = dim.max_in; c.min_in = min_in; c.maxch = dim.maxch; c.maxtile = dim.maxtile;
+    c.st = area<lzf::seg_job>(s, o_st);
+    c.rec_top = area<unsigned long long>(s, o_top);
+    c.bits = area<uint32_t>(s, o_bits);
+    c.n_cu = geo.cu;
+    c.g_off = 0u; c.g_n = n;
+    return c;
+}
+
+// ---- the segmented pipeline -------------------------------------------------------------------------------------------------
+struct SegCall {
+    AsyncScratch mem;
+    lzf::seg_ctx ctx{};
+    uint32_t* est = nullptr;       // [n] grouped calls: the jobs by sequences, most first (lzf_seg_rank_kernel)
+    explicit SegCall(hipStream_t st) : mem(st) {}
+};
+// lays the scratch areas of a call out in one stream-ordered allocation; false (and nothing allocated) when the pool has no room
+bool seg_alloc(SegCall& s, const d::Geometry& geo, const lzf_decompress_job* d_jobs, lzf_job_result* d_results, uint32_t n, uint32_t min_in, uint32_t ring, uint64_t max_in_hint) {
+    const d::SegLayout l = d::seg_layout(n, max_in_hint);
+    if (!s.mem.alloc(l.total)) return false;
+    lzf::seg_ctx& c = s.ctx;
+    c = seg_ctx_of(geo, d_jobs, d_results, n, l.d, min_in, s.mem, l.o_st, l.o_top, l.o_bits);
+    c.rec_cap = l.rec_cap; c.ring_bytes = ring; c.dbg_force = knobs().seg_force;
+    c.xexit = area<uint32_t>(s.mem, l.o_xexit);
+    c.vfrom = area<uint32_t>(s.mem, l.o_vfrom);
+    c.tile_tok = area<uint32_t>(s.mem, l.o_tile_tok);
+    c.tile_out = area<uint32_t>(s.mem, l.o_tile_out);
+    c.recs = area<lzf::u32x4>(s.mem, l.o_recs);
+    const d::SegRanks r = d::seg_ranks(geo, n);
+    c.order = r.order ? area<uint32_t>(s.mem, l.o_order) : nullptr;
+    c.by_len = r.by_len ? area<uint32_t>(s.mem, l.o_by_len) : nullptr;
+    c.rec_by_len = r.rec_by_len ? 1u : 0u;
+    s.est = area<uint32_t>(s.mem, l.o_est);
+    return true;
+}
+inline uint32_t seg_grid(uint32_t target, uint32_t n, uint32_t cap) {
+    uint32_t g = target / n; if (g < 1u) g = 1u; if (g > cap) g = cap; return g;
+}
+// workgroups per launch of the chunk / tile kernels: about one chunk and a handful of tiles each — with 8 192 / 32 768 (each
+// workgroup looping over a dozen chunks) the launches ended on their slowest loops: parse 4.3 -> 3.3 ms at 980 blocks, 1.02 -> 0.83 at 196
+inline uint32_t seg_parse_target(const lzf::seg_ctx& c) { return knobs().seg_grid_parse ? knobs().seg_grid_parse : d::kSegParsePerCu * c.n_cu; }     // (MI355X: 262 144
+inline uint32_t seg_tile_target(const lzf::seg_ctx& c) { return knobs().seg_grid_tile ? knobs().seg_grid_tile : d::kSegTilePerCu * c.n_cu; }         //  and 524 288)
+// stages: 1 plan, 2 parse, 3 seam, 4 tilesum, 5 scan, 6 records (+ levels), 8 resolve (all when upto >= 8)
+// seg_launch_prep: the stages that look at every job of the call; seg_launch_front: the chunk / tile stages of the group the context
+// names (ranks g_off .. g_off + g_n) up to the scan; seg_launch_records, seg_launch_resolve: its last two stages.
+int seg_launch_prep(const lzf::seg_ctx& c, hipStream_t st) {
+    if (c.by_len && !c.grouped) LAUNCH(lzf::lzf_seg_by_len_kernel, dim3(1), dim3(1024), 0, st, c);
+    LAUNCH(lzf::lzf_seg_plan_kernel, dim3((c.n_jobs + 255u) / 256u), dim3(256), 0, st, c);
+    return LZF_OK;
+}
+int seg_launch_front(const lzf::seg_ctx& c, uint32_t upto, hipStream_t st) {
+    const uint32_t n = c.g_n;
+    if (upto >= 2) LAUNCH(lzf::lzf_seg_parse_kernel, dim3(seg_grid(seg_parse_target(c), n, c.maxch), n), dim3(64), 0, st, c);
+    if (upto >= 3) LAUNCH(lzf::lzf_seg_seam_kernel, dim3(n), dim3(64), 0, st, c);
+    if (upto >= 4) LAUNCH(lzf::lzf_seg_tilesum_kernel, dim3(seg_grid(seg_tile_target(c), n, c.maxtile), n), dim3(64), 0, st, c);
+    if (upto >= 5) LAUNCH(lzf::lzf_seg_scan_kernel, dim3(n), dim3(64), 0, st, c);
+    return LZF_OK;
+}
+// pad: bytes of unused LDS per workgroup (a grouped call's records stage under the resolve stages: the residency experiment)
+int seg_launch_records(const lzf::seg_ctx& c, uint32_t pad, hipStream_t st) {
+    if (c.order && !c.grouped) LAUNCH(lzf::lzf_seg_order_kernel, dim3(1), dim3(1024), 0, st, c);
+    LAUNCH(lzf::lzf_seg_records_kernel, dim3(seg_grid(seg_tile_target(c), c.g_n, c.maxtile), c.g_n), dim3(64), pad, st, c);
+    return LZF_OK;
+}
+int seg_launch_resolve(const lzf::seg_ctx& c, hipStream_t st) {
+    const uint32_t n = c.g_n;
+    if (c.ring_bytes == 131072u) LAUNCH(lzf::lzf_seg_resolve_pair_kernel<131072>, dim3(n), dim3(128), 0, st, c);
+    else if (c.ring_bytes == 65536u) LAUNCH(lzf::lzf_seg_resolve_pair_kernel<65536>, dim3(n), dim3(128), 0, st, c);
+    else LAUNCH(lzf::lzf_seg_resolve_pair_kernel<32768>, dim3(n), dim3(128), 0, st, c);
+    return LZF_OK;
+}
+int seg_launch(const lzf::seg_ctx& c, uint32_t upto, hipStream_t st) {
+    int rc = seg_launch_prep(c, st);
+    if (rc == LZF_OK) rc = seg_launch_front(c, upto, st);
+    if (rc == LZF_OK && upto >= 6) rc = seg_launch_records(c, 0u, st);
+    if (rc == LZF_OK && upto >= 8) rc = seg_launch_resolve(c, st);
+    return rc;
+}
+
+// ---- groups: the records stage of a group runs under the resolve stage of the groups before it -------------------------------
+// The resolve stage is a chain per block (one pair of wavefronts, 7 ms for a 4 MiB text block whatever the batch) and leaves most
+// of the chip idle; the stages before it are throughput kernels.  A call of several hundred blocks therefore takes its last two
+// stages in groups, by sequences (known once the tiles are counted: lzf_seg_rank_kernel), most first: the caller's stream
+// carries every group's records stage back to back, each group's resolve stage starts on a stream of its own as soon as its
+// records are written (an event), and the caller's stream waits for all of them before the pair kernel looks for jobs the
+// pipeline left.  The call then takes records(first group) + resolve(longest block) instead of records(all) + resolve(longest
+// block), as long as the later groups — the blocks with fewer sequences — are through their shorter resolve stages by then.
+// (The lanes are made at the highest stream priority: the runtime keeps a pool of hardware queues per priority, so they do not share
+//  a queue with the application's streams; a fifth group measured slower: 8.9 -> 13.2 ms at 196 blocks.)
+inline bool hip_ok(hipError_t e) { if (e != hipSuccess) { (void)hipGetLastError(); return false; } return true; }
+inline void lane_drain(hipStream_t s) { (void)hip_ok(hipStreamSynchronize(s)); }
+constexpr uint32_t kSegPauseUs = 10u;      // between a group's resolve stage and the next group's records stage (5 .. 80 us measured alike)
+int seg_enqueue_groups(const SegCall& s, const d::SegGroups& g, SegLanes& L, uint32_t wall_khz, hipStream_t st) {
+    lzf::seg_ctx c = s.ctx;
+    std::lock_guard<std::mutex> lk(L.mu);
+    int rc = seg_launch_prep(c, st);
+    if (rc == LZF_OK) rc = seg_launch_front(c, 5u, st);         // plan .. scan over the whole call
+    if (rc != LZF_OK) return rc;
+    static_assert(d::kSegMaxGroups == 4, "lzf_seg_rank_kernel takes the group sizes as a uint4");
+    LAUNCH(lzf::lzf_seg_rank_kernel, dim3(1), dim3(1024), 0, st, c, s.est, make_uint4(g.size[0], g.n > 1u ? g.size[1] : 0u, g.n > 2u ? g.size[2] : 0u, g.n > 3u ? g.size[3] : 0u));      // s.est: the jobs by sequences, most first; + every group's workgroup order
+    c.by_len = s.est; c.grouped = 1u; c.res_prio = 1u;
+    uint32_t off = 0, forked = 0;
+    const uint32_t pause_ticks = kSegPauseUs * (wall_khz / 1000u);       // (the device's wall clock: 100 ticks per microsecond on MI355X)
+    for (uint32_t k = 0; k < g.n && rc == LZF_OK; ++k) {
+        c.g_off = off; c.g_n = g.size[k]; off += g.size[k];
+        rc = seg_launch_records(c, knobs().seg_rec_pad, st);
+        if (rc != LZF_OK) break;
+        if (k + 1u == g.n) { rc = seg_launch_resolve(c, st); break; }      // the last group: on the caller's stream
+        if (!hip_ok(hipEventRecord(L.front[k], st)) || !hip_ok(hipStreamWaitEvent(L.s[k], L.front[k], 0))) { rc = LZF_E_HIP; break; }
+        rc = seg_launch_resolve(c, L.s[k]);
+        ++forked;                                                // (whatever was enqueued on the lane is joined below)
+        if (pause_ticks && rc == LZF_OK) LAUNCH_RC(rc, lzf::lzf_seg_pause_kernel, dim3(1), dim3(64), 0, st, pause_ticks);      // the resolve stage's workgroups first, then the next records stage
+        if (!hip_ok(hipEventRecord(L.done[k], L.s[k]))) { --forked; if (rc == LZF_OK) rc = LZF_E_HIP; lane_drain(L.s[k]); }
+    }
+    for (uint32_t k = 0; k < forked; ++k)
+        if (!hip_ok(hipStreamWaitEvent(st, L.done[k], 0))) { lane_drain(L.s[k]); if (rc == LZF_OK) rc = LZF_E_HIP; }
+    return rc;
+}
+int seg_launch_grouped(const SegCall& s, const d::SegGroups& g, SegLanes& L, uint32_t wall_khz, hipStream_t st) {
+    const int rc = seg_enqueue_groups(s, g, L, wall_khz, st);
+    if (rc != LZF_OK)                                            // (a launch failed part-way: nothing may still be running on a lane when the caller frees the scratch)
+        for (uint32_t k = 0; k < d::kSegMaxGroups - 1u; ++k) lane_drain(L.s[k]);
+    return rc;
+}
+
+}  // namespace
+
+// The whole call: pipeline, then the pair kernel over what the pipeline did not finish.
+int seg_decompress(Device& dv, const lzf_decompress_job* d_jobs, lzf_job_result* d_results, uint32_t n, const d::DecompressPlan& plan, hipStream_t st, bool* used, uint64_t max_in_hint) {
+    SegCall s(st);
+    *used = seg_alloc(s, dv.geo, d_jobs, d_results, n, plan.seg_min_in, plan.seg_ring, max_in_hint);
+    if (!*used) return LZF_OK;                                   // (no scratch: the caller launches the pair kernel over everything)
+    SegLanes* lanes = plan.groups.n > 1u ? seg_lanes(dv) : nullptr;
+    int rc = lanes ? seg_launch_grouped(s, plan.groups, *lanes, dv.geo.wall_khz, st) : seg_launch(s.ctx, 8u, st);
+    if (rc == LZF_OK) LAUNCH_RC(rc, k_paired48, dim3(n), dim3(128), 0, st, d_jobs, d_results, n, (const uint32_t*)nullptr, (const lzf::seg_job*)s.ctx.st);
+    if (s.mem.release() != hipSuccess && rc == LZF_OK) rc = LZF_E_HIP;
+    if (rc != LZF_OK) g_last_error = "segmented decompress: launch failed";
+    return rc;
+}
+
+// ---- the bitmap-fed kernel (lz4_decompress_fed.hip): batches beyond the segmented pipeline's ----------------------------------
+// plan + parse of the segmented pipeline over the whole batch (the token bit map of every block: one bit per compressed byte;
+// no seam stage — the fed wavefront carries the true chain and masks or walks what a chunk's parse marked before it fell in step),
+// then one wavefront per block that lists its tokens from the map and copies — the in-kernel parse of the pair kernel is
+// 13.0 of its 27.8 wave-instructions per sequence, the hop parse 3.8 — then the pair kernel over whatever that left (errors,
+// sizes outside the map's window).  The launch order comes from the parse as well: it counts every job's tokens.
+namespace {
+// Workgroups of the kernel the current device holds at once, COUNTED (lz4_decompress_fed.hip, census mode): the occupancy query
+// does not know the LDS allocation granule (an earlier build's 6 912 bytes took 7 680: 21 per CU where the query said 23; today's
+// 5 952 take 6 400: 25 per CU counted with the registers bounded to seven waves per SIMD), and a schedule with more slots than
+// residents runs its surplus slots after the others.  As built the REGISTERS limit the kernel: LZF_FED_WAVES (kernels.h) waves on
+// each of a CU's four SIMDs, 24 per CU counted.  Once per device and process: one launch of ~0.1 ms and a 4-byte copy (the one
+// place a batch call waits for the device).
+constexpr uint32_t kFedWavesPerCu = 4u * (LZF_FED_WAVES > 0 ? (uint32_t)LZF_FED_WAVES : 5u);   // (no bound: 82 VGPRs, five per SIMD)
+struct FedCensus { uint32_t slots, xcc_mask; };
+FedCensus fed_census(Device& dev, hipStream_t st) {
+    const uint32_t cu = dev.geo.cu;
+    {
+        std::lock_guard<std::mutex> lk(device_mutex());
+        if (dev.fed_slots) return FedCensus{dev.fed_slots, dev.fed_xcc_mask};
+    }
+    // (counted with the mutex free: it waits for the device; two first calls at once both count, and get the same answer)
+    FedCensus answer{0u, 0u};
+    uint32_t* dmem = nullptr;
+    if (hipMalloc(&dmem, 4u * sizeof(uint32_t)) == hipSuccess) {
+        const uint32_t init[4] = {0u, 0xFFFFFFFFu, 0u, 0u};
+        lzf::fed_args a{}; a.census = dmem;
+        if (hipMemcpyAsync(dmem, init, sizeof init, hipMemcpyHostToDevice, st) == hipSuccess) {
+            hipLaunchKernelGGL(k_fed32, dim3(40u * cu), dim3(64), 0, st, a);
+            uint32_t got[4] = {0, 0, 0, 0};
+            if (hipGetLastError() == hipSuccess && hipMemcpyAsync(got, dmem, sizeof got, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess &&
+                got[1] != 0xFFFFFFFFu && got[1] >= cu) { answer.slots = got[1]; answer.xcc_mask = got[2]; }
+        }
+        (void)hipFree(dmem);
+    }
+    (void)hipGetLastError();
+    if (!answer.slots) {             // (the census failed: the smaller of the LDS's and the registers' answer; no XCD mask: jobs stay whole)
+        const uint32_t by_lds = d::per_cu(dev.geo, d::kFedLdsAlloc);
+        answer.slots = (by_lds < kFedWavesPerCu ? by_lds : kFedWavesPerCu) * cu;
+    }
+    if (knobs().fed_verbose) fprintf(stderr, "[lzf] bitmap-fed kernel: %u workgroups resident at once (%u compute units), XCD mask 0x%x\n", answer.slots, cu, answer.xcc_mask);
+    std::lock_guard<std::mutex> lk(device_mutex());
+    if (!dev.spare) { dev.fed_slots = answer.slots; dev.fed_xcc_mask = answer.xcc_mask; }
+    return answer;
+}
+}  // namespace
+
+// scratch, plan + parse, the launch order, reset, the fed kernel, the pair kernel, scratch back.
+// perm + est (both or neither): the launch order is wanted and nobody has worked it out yet — est[] is filled here, by the plan stage
+// (the bytes' share) and the parse (the sequences: exact, where lzf_decompress_cost_kernel samples), and perm[] ordered by it.
+int fed_decompress(Device& dv, const lzf_decompress_job* d_jobs, lzf_job_result* d_results, uint32_t n, uint32_t* perm, uint32_t* est, hipStream_t st, bool* used, uint64_t max_in_hint) {
+    const d::Knobs& kn = knobs();
+    const d::FedLayout l = d::fed_layout(n, max_in_hint);
+    AsyncScratch mem(st);
+    *used = mem.alloc(l.total);
+    if (!*used) return LZF_OK;                                   // (no room for the bit maps: the pair kernel takes the call, the order is still to make)
+    lzf::seg_ctx c = seg_ctx_of(dv.geo, d_jobs, d_results, n, l.d, kn.fed_min_in, mem, l.o_st, l.o_top, l.o_bits);
+    c.fed = 1u; c.est = perm ? est : nullptr; c.len_shift = kn.order_len_shift;
+    int rc = seg_launch(c, 2u, st);                              // plan, parse
+    if (rc == LZF_OK && c.est) LAUNCH_RC(rc, lzf::lzf_order_by_estimate_kernel, dim3(1), dim3(1024), 0, st, (const uint32_t*)est, perm, n);
+    if (rc == LZF_OK) {
+        // The kernel runs as one wavefront per SLOT — as many as the device holds at once — and the slots share the jobs out in pieces
+        // (lz4_decompress_fed.hip): a call with more jobs than slots cuts every job into 16 (measured at 2.2 jobs per slot: 107.4 ms whole,
+        // 97.3 / 97.2 / 97.8 / 99.0 / 101.7 ms with 8 / 16 / 32 / 64 / 128 pieces), a smaller one leaves them whole.
+        const FedCensus fc = fed_census(dv, st);
+        const uint32_t slots = kn.fed_slots ? kn.fed_slots * c.n_cu : fc.slots;
+        uint32_t pieces = kn.fed_pieces ? kn.fed_pieces : n > fc.slots ? d::kFedPieces : 1u;
+        if ((uint64_t)n * pieces > 0xFFFFFFF0ull || !fc.xcc_mask) pieces = 1u;       // (no XCD mask: jobs stay whole)
+        lzf::fed_args a{d_jobs, d_results, c.st, c.bits, perm, area<lzf::fed_state>(mem, l.o_state), area<uint32_t>(mem, l.o_ticket), fc.xcc_mask ? fc.xcc_mask : 1u, n, c.maxch, pieces, kn.fed_carry, nullptr};
+        LAUNCH_RC(rc, lzf::lzf_fed_reset_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, a);
+        if (rc == LZF_OK) LAUNCH_RC(rc, k_fed32, dim3(slots < n ? slots : n), dim3(64), kn.fed_pad_lds, st, a);
+        if (rc == LZF_OK) LAUNCH_RC(rc, k_paired24, dim3(n), dim3(128), 0, st, d_jobs, d_results, n, (const uint32_t*)perm, (const lzf::seg_job*)c.st);
+    }
+    if (mem.release() != hipSuccess && rc == LZF_OK) rc = LZF_E_HIP;
+    if (rc != LZF_OK) g_last_error = "bitmap-fed decompress: launch failed";
+    return rc;
+}
+
+}  // namespace lzf_capi
+
+using namespace lzf_capi;
+#ifdef LZF_ANALYSIS
+extern "C"
+// Analysis only: run the segmented pipeline up to a stage and copy its scratch areas to host buffers (NULL = skip).
+// geom[0..3] = maxch, maxtile, chunk words, records in the arena.
+int lzf_debug_seg(const lzf_decompress_job* d_jobs, lzf_job_result* d_results, uint32_t n, uint32_t min_in, uint32_t upto,
+                  void* h_state, void* h_bits, void* h_xexit, void* h_vfrom, void* h_tile_tok, void* h_tile_out, void* h_recs, uint64_t recs_bytes,
+                  uint32_t* geom) {
+    int rc = ensure_device();
+    if (rc < 0) return rc;
+    SegCall s(nullptr);
+    const d::Geometry& geo = device().geo;
+    if (knobs().seg_force == 3u || !seg_alloc(s, geo, d_jobs, d_results, n, min_in, d::seg_ring(geo, knobs(), n), ~0ull)) return LZF_E_HIP;
+    const lzf::seg_ctx& c = s.ctx;
+    rc = seg_launch(c, upto, nullptr);
+    HIP_TRY(hipDeviceSynchronize());
+    if (geom) { geom[0] = c.maxch; geom[1] = c.maxtile; geom[2] = lzf::kSegChunkWords; geom[3] = (uint32_t)c.rec_cap; }
+    if (h_state) HIP_TRY(hipMemcpy(h_state, c.st, sizeof(lzf::seg_job) * n, hipMemcpyDeviceToHost));
+    if (h_bits) HIP_TRY(hipMemcpy(h_bits, c.bits, sizeof(uint32_t) * (size_t)n * c.maxch * lzf::kSegChunkWords, hipMemcpyDeviceToHost));
+    if (h_xexit) HIP_TRY(hipMemcpy(h_xexit, c.xexit, sizeof(uint32_t) * (size_t)n * c.maxch, hipMemcpyDeviceToHost));
+    if (h_vfrom) HIP_TRY(hipMemcpy(h_vfrom, c.vfrom, sizeof(uint32_t) * (size_t)n * c.maxch, hipMemcpyDeviceToHost));
+    if (h_tile_tok) HIP_TRY(hipMemcpy(h_tile_tok, c.tile_tok, sizeof(uint32_t) * (size_t)n * c.maxtile, hipMemcpyDeviceToHost));
+    if (h_tile_out) HIP_TRY(hipMemcpy(h_tile_out, c.tile_out, sizeof(uint32_t) * (size_t)n * c.maxtile, hipMemcpyDeviceToHost));
+    if (h_recs) { uint64_t nb = sizeof(lzf::u32x4) * c.rec_cap; if (nb > recs_bytes) nb = recs_bytes; HIP_TRY(hipMemcpy(h_recs, c.recs, nb, hipMemcpyDeviceToHost)); }
+    HIP_TRY(s.mem.release());
+    return rc;
+}
+#endif

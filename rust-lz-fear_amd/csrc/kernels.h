@@ -61,6 +61,8 @@ __global__ __launch_bounds__(128) void lzf_decompress_paired_kernel(const lzf_de
 #define LZF_EXTP(NAME, RG, S_, T) extern template __global__ void lzf_decompress_paired_kernel<RG, S_, T>(const lzf_decompress_job*, lzf_job_result*, uint32_t, const uint32_t*, const seg_job*);
 LZF_PAIRED_VARIANTS(LZF_EXTP)
 #undef LZF_EXTP
+constexpr auto k_paired48 = lzf_decompress_paired_kernel<4096, 48, 640>;      // the two forms of the product dispatch (lzf_dispatch.h: kPaired48Lds, kPaired24Lds)
+constexpr auto k_paired24 = lzf_decompress_paired_kernel<4096, 24, 384>;
 // ---------------------------------------------------------------------------------------------------------------------
 // Segmented decompress (lz4_decompress_seg.hip): one block decoded by MANY wavefronts, as a pipeline of launches over the
 // whole batch.  Used for batches that leave the chip mostly empty with one workgroup per block (per-block latency regime).
@@ -106,13 +108,13 @@ struct seg_ctx {
     uint32_t* by_len;            // [n_jobs]  chunk / tile stages: grid row -> job, longest input first (null: identity)
     uint32_t rec_by_len;         // the records stage follows by_len too (64 jobs and more; measured: below that its own order is quicker)
     uint32_t dbg_force;          // analysis library only (LZF_SEG_FORCE): 1 = stagers of odd jobs give up, 2 = resolvers of odd jobs give up
-    // A call's jobs may go through the last two stages in GROUPS (capi.hip: the next group's records stage runs under the resolve
+    // A call's jobs may go through the last two stages in GROUPS (capi_drivers.hip: the next group's records stage runs under the resolve
     // stage of the one before): a launch then serves ranks [g_off, g_off + g_n) of by_len[] (which is the jobs by sequences then).
     // One group: g_off = 0, g_n = n_jobs, grouped = 0.
     uint32_t g_off, g_n, grouped;
     uint32_t res_prio;           // the resolve stage's wavefronts raise their issue priority (grouped calls: they share their SIMDs with the next group's records stage)
     uint32_t fed;                // the plan / parse stages serve the bitmap-fed kernel: prefix and existing output do not make a job ineligible, no xexit is stored
-    // the launch order of a fed call (capi.hip): est[j] = the job's cost, written by the plan stage (input_len >> len_shift; a guess by
+    // the launch order of a fed call (capi_drivers.hip): est[j] = the job's cost, written by the plan stage (input_len >> len_shift; a guess by
     // length for a job the map does not cover) and counted up by the parse (every chunk adds the tokens it owns).  null: no order asked for
     uint32_t* est;
     uint32_t len_shift;

@@ -50,7 +50,7 @@ __global__ __launch_bounds__(64) void lzf_compress_compact_kernel(
     __shared__ __attribute__((aligned(16))) uint32_t tab32[kSlots / 2 + kSlots / 32 + kWave + LZF_DBG_LDS_PAD / 4];      // occupancy experiment
 #else
     __shared__ __attribute__((aligned(16))) uint32_t tab32[kSlots / 2 + kSlots / 32 + kWave];
-    static_assert(sizeof(tab32) == kCompactLdsBytes, "capi.hip derives the kernel's residency from kCompactLdsBytes");
+    static_assert(sizeof(tab32) == kCompactLdsBytes, "lzf_dispatch.h derives the kernel's residency from this (capi.hip asserts kCompactLds against it)");
 #endif
     uint32_t* const par = tab32 + kParBase;
     uint16_t* const tab16 = reinterpret_cast<uint16_t*>(tab32);

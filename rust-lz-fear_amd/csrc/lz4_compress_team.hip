@@ -4,10 +4,11 @@
 // gfx950 primitives.  160 KiB of LDS per workgroup (all of a CU's): one workgroup per CU.
 #include "lz4_compress_team.inc"
 #include "kernels.h"
+#include "lzf_dispatch.h"
 
 namespace lzf {
 
-static_assert(team::kLdsWords * 4u == 163840u, "capi.hip's kTeamLds (the dispatch's LDS requirement) is this number");
+static_assert(team::kLdsWords * 4u == lzf_dispatch::kTeamLds, "the dispatch's LDS requirement of the team kernel");
 
 __global__ __launch_bounds__(192) void lzf_compress_team_kernel(const lzf_compress_job* __restrict__ jobs, lzf_job_result* __restrict__ results,
                                                                 uint32_t n_jobs, const uint32_t* __restrict__ perm, uint32_t alone) {

@@ -11,7 +11,7 @@
 //   lzf_decompress_fed_kernel<RING, W, TOKCAP>        one wavefront per block: feed a window of 32 * W compressed bytes from where
 //                                                     the chain stands, copy it; a short last batch waits for the next window
 //
-// Contract with the dispatch (capi.hip): a job is taken only when the plan stage found it eligible (sizes inside the bit map's
+// Contract with the dispatch (lzf_dispatch.h, capi_drivers.hip): a job is taken only when the plan stage found it eligible (sizes inside the bit map's
 // window); a job is FINISHED here (results written, seg_job::done set) only when it decodes cleanly over a verified chain.
 // Everything else — every DecodeError, a capacity problem — is left untouched for the pair kernel launched behind this one, which
 // decodes the job from its first byte and reports the reference's status.  What this kernel wrote into `out` before it gave up
@@ -20,6 +20,7 @@
 #include "kernels.h"
 #include "lzf_copy_helpers.h"
 #include "lzf_fed_window.h"
+#include "lzf_dispatch.h"
 
 namespace lzf {
 
@@ -29,7 +30,7 @@ __device__ __forceinline__ uint32_t xcc_id() {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// The launch is a fixed set of SLOTS — as many wavefronts as the device holds at once (capi.hip counts them) — that share the
+// The launch is a fixed set of SLOTS — as many wavefronts as the device holds at once (capi_drivers.hip counts them) — that share the
 // jobs out in PIECES instead of one workgroup per job.  With one workgroup per job a launch of 2.2 jobs per slot takes three
 // rounds of the longest jobs' time, and inside a round every slot waits for the longest job (the timeline of round 6: 86 ms for
 // 66 ms of work; a block costs 42 .. 86 M cycles and nothing cheap predicts which).  Here every job is cut into `pieces`
@@ -57,6 +58,7 @@ __global__ LZF_FED_BOUNDS void lzf_decompress_fed_kernel(fed_args a) {      // (
     __shared__ __attribute__((aligned(16))) uint8_t ring[RING];
     __shared__ __attribute__((aligned(16))) uint8_t cbuf[kCB];
     __shared__ __attribute__((aligned(16))) uint16_t toks[TOKCAP];
+    static_assert(RING != 4096 || W != 32 || TOKCAP != 352 || lzf_dispatch::lds_alloc(sizeof ring + sizeof cbuf + sizeof toks) == lzf_dispatch::kFedLdsAlloc, "lzf_dispatch.h: the residency the census falls back on");
 
     const uint32_t lane = threadIdx.x;
     if (a.census) {

@@ -9,6 +9,7 @@
 #include "kernels.h"
 #include "lzf_copy_helpers.h"
 #include "lzf_parse_helpers.h"
+#include "lzf_dispatch.h"
 
 namespace lzf {
 
@@ -34,6 +35,9 @@ __global__ __launch_bounds__(128) void lzf_decompress_paired_kernel(
     __shared__ __attribute__((aligned(16))) uint8_t tokexs[2u * kTokex];   // ex[] while parsing, then the token list
     __shared__ uint32_t ctl_T[2], ctl_cstart[2];
     __shared__ int ctl_err[2], ctl_valid[2], ctl_stop;
+    constexpr uint32_t kLds = lzf_dispatch::lds_alloc(sizeof ring + sizeof cbufs + sizeof nxt + sizeof tokexs + sizeof ctl_T + sizeof ctl_cstart + sizeof ctl_err + sizeof ctl_valid + sizeof ctl_stop);
+    static_assert(RING != 4096 || TOKCAP != 640 || S != 48 || kLds == lzf_dispatch::kPaired48Lds, "lzf_dispatch.h derives the classes of the decompress call from this");
+    static_assert(RING != 4096 || TOKCAP != 384 || S != 24 || kLds == lzf_dispatch::kPaired24Lds, "lzf_dispatch.h derives the classes of the decompress call from this");
 
     if (blockIdx.x >= n_jobs) return;
     const uint32_t jid = perm ? perm[blockIdx.x] : blockIdx.x;

@@ -16,6 +16,7 @@
 // skips finished jobs — so statuses and partial outputs are exactly the pair kernel's.
 #include "lzf_device.h"
 #include "kernels.h"
+#include "lzf_dispatch.h"
 #include "lzf_copy_helpers.h"
 #include <type_traits>
 
@@ -82,9 +83,13 @@ __device__ __forceinline__ void wave_copy_long(gu8* __restrict__ dst, cgu8* __re
     wave_copy(dst + i, src + i, n - i, lane);
 }
 
-__device__ __forceinline__ uint32_t seg_nch(uint32_t len) {
+__device__ __forceinline__ constexpr uint32_t seg_nch(uint32_t len) {
     return len <= kSegChunk ? 1u : 1u + (len - kSegChunk + kSegStride - 1u) / kSegStride;
 }
+// (the host sizes the bit maps with its own copy)
+static_assert(seg_nch(1u) == lzf_dispatch::seg_nch(1u) && seg_nch(kSegChunk) == lzf_dispatch::seg_nch(kSegChunk) && seg_nch(kSegChunk + 1u) == lzf_dispatch::seg_nch(kSegChunk + 1u) &&
+              seg_nch(kSegChunk + kSegStride + 1u) == lzf_dispatch::seg_nch(kSegChunk + kSegStride + 1u) && seg_nch(lzf_dispatch::kSegMaxIn) == lzf_dispatch::seg_nch(lzf_dispatch::kSegMaxIn),
+              "lzf_dispatch.h restates seg_nch");
 
 // Length of the run of 0xFF bytes that starts at q (stops at len): the body of read_lsic (decompress.rs:30-43) eight bytes
 // at a time.  RD8(q) = 8 bytes at q (q + 8 <= len), RDB(q) = one byte.
@@ -875,7 +880,7 @@ __global__ __launch_bounds__(64) void lzf_seg_records_kernel(seg_ctx c) {
 __global__ __launch_bounds__(1024) void lzf_seg_by_len_kernel(seg_ctx c) {
     __shared__ uint32_t cost[1024];
     const uint32_t i = threadIdx.x, n = c.n_jobs;
-    if (n > 1024u) return;                                        // (one workgroup ranks the call: the dispatch never asks for more, capi.hip kSegRankMax)
+    if (n > 1024u) return;                                        // (one workgroup ranks the call: the dispatch never asks for more, lzf_dispatch.h kSegRankMax)
     if (i < n) { const uint64_t l = c.jobs[i].input_len; cost[i] = l > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)l; }
     __syncthreads();
     if (i >= n) return;
@@ -884,7 +889,7 @@ __global__ __launch_bounds__(1024) void lzf_seg_by_len_kernel(seg_ctx c) {
     for (uint32_t k = 0; k < n; ++k) { const uint32_t o = cost[k]; r += (o > mine || (o == mine && k < i)) ? 1u : 0u; }
     c.by_len[r] = i;
 }
-// Grouped calls: one wavefront that does nothing for `ticks` of the device's wall clock (capi.hip converts from microseconds by the rate the runtime reports).  It sits on the caller's stream between a group's
+// Grouped calls: one wavefront that does nothing for `ticks` of the device's wall clock (capi_drivers.hip converts from microseconds by the rate the runtime reports).  It sits on the caller's stream between a group's
 // records stage and the next one's: the group's resolve stage starts on another stream (an event away: a few microseconds later), and
 // its workgroups — 32+ KiB of LDS each — should find the compute units empty rather than squeeze in between the next records stage's
 // (measured at 980 blocks: 15.4 ms with such a pause, 17.0 without).

@@ -1,4 +1,4 @@
-"""The dispatch thresholds are functions of the device's compute units and LDS (capi.hip `geometry()`), not literals: with the analysis
+"""The dispatch thresholds are functions of the device's compute units and LDS (lzf_dispatch.h `Geometry`), not literals: with the analysis
 knob LZF_FAKE_CU=64 the same device dispatches as one with 64 CUs — the segmented pipeline up to 4 x 64 blocks with rings of 128 / 64 /
 32 KiB at 64 / 128 / 256 blocks, paired48 up to 8 x 64, paired24 up to 12 x 64, the bitmap-fed kernel beyond (round 6; paired24 /
 staged16 behind it when it declines a call) — and every class still decodes to the oracle's bytes.  Run as a script by tests/test_gpu_hardening.py (the knob is read once per process)."""
@@ -22,7 +22,7 @@ def main():
     bigc = [o.compress2(d)[1] for d in big]
     assert all(len(c) > 262144 for c in bigc), [len(c) for c in bigc]
     seen = {}
-    # more compute units than the pipeline's rank kernels take jobs (one 1024-thread workgroup, capi.hip kSegRankMax): with
+    # more compute units than the pipeline's rank kernels take jobs (one 1024-thread workgroup, lzf_dispatch.h kSegRankMax): with
     # LZF_FAKE_CU=512 the pipeline's limit is 1024 jobs, not 4 x 512 — 1000 jobs go through it, 1500 go to the pair kernel
     sizes = (1000, 1500) if cu > 256 else (cu - 4, cu + 4, 2 * cu + 4, 4 * cu - 4, 4 * cu + 8, 8 * cu + 8, 13 * cu + 8, 64 * cu + 16)
     for n in sizes:

@@ -286,7 +286,7 @@ def test_segmented_pipeline_mixed_batch():
 
 
 def test_segmented_pipeline_grouped_mixed_batch():
-    """Calls of 32 jobs and more take the pipeline's last two stages in groups (capi.hip: seg_groups — the records stage of the next
+    """Calls of 32 jobs and more take the pipeline's last two stages in groups (lzf_dispatch.h: seg_groups — the records stage of the next
     quarter of the jobs, by sequences, under the resolve stage of the one before, on streams of the library's own).  The mixed
     batch twice over, so that every group holds jobs the pipeline finishes, jobs it fails (damaged blocks, capacity, limit) and jobs
     it never takes (prefix, existing output, below the window): statuses and bytes as the oracle's, whatever group a job fell into."""
