@@ -17,6 +17,7 @@
 // Error precedence is the reference's (decompress.rs:63-75,82-89): literal EOF, LSIC EOF ->
 // UnexpectedEnd; then MemoryLimitExceeded; ZeroDeduplicationOffset; InvalidDeduplicationOffset.
 #include "../lzf_device.h"
+#include "../lzf_copy_helpers.h"
 
 namespace lzf {
 
@@ -51,7 +52,6 @@ struct InWindow {
     }
 };
 
-constexpr uint32_t kMaxPos = 0x7FFFFF00u;   // positions are 32-bit inside the kernel
 
 __global__ __launch_bounds__(64) void lzf_decompress_wave_kernel(
     const lzf_decompress_job* __restrict__ jobs, lzf_job_result* __restrict__ results, uint32_t n_jobs,
@@ -64,73 +64,67 @@ __global__ __launch_bounds__(64) void lzf_decompress_wave_kernel(
 
     int status = LZF_OK;
     uint32_t o = 0;
-    if (job.input_len >= kMaxPos || job.out_existing_len >= kMaxPos || job.prefix_len >= kMaxPos || job.out_existing_len > job.out_cap) {
+    if (LZF_DECODE_JOB_OUT_OF_CONTRACT(job)) {
         status = LZF_CONTRACT;   // blocks beyond 2 GiB are outside this kernel's contract
     } else {
-        cgu8* __restrict__ in = as_global(job.input);
-        cgu8* __restrict__ prefix = as_global(job.prefix);
-        gu8* out = as_global(job.out);
-        const uint32_t len = (uint32_t)job.input_len;
-        const uint32_t plen = (uint32_t)job.prefix_len;
-        const uint32_t cap = job.out_cap > kMaxPos ? kMaxPos : (uint32_t)job.out_cap;
-        const uint64_t limit = job.output_limit;
+        const DecodeJob jv = LZF_DECODE_JOB_VIEW(job);
         o = (uint32_t)job.out_existing_len;
         uint32_t safe = o;   // out[0, safe) is known to be visible to this wave's loads
         uint32_t p = 0;
-        InWindow win{in, len, 0xFFFFFFFFu, 0u, 0u};
+        InWindow win{jv.in, jv.len, 0xFFFFFFFFu, 0u, 0u};
 
-        while (p < len) {                                              // decompress.rs:61
+        while (p < jv.len) {                                              // decompress.rs:61
             const uint32_t token = win.byte(p, lane); ++p;
             // ---- literal length: read_lsic, decompress.rs:30-43,63
             uint32_t lit = token >> 4;
             if (lit == 15u) {
                 bool eof = false;
                 for (;;) {
-                    if (p >= len) { eof = true; break; }
+                    if (p >= jv.len) { eof = true; break; }
                     const uint32_t b = win.byte(p, lane); ++p;
-                    lit = lit + b; if (lit > kMaxPos) lit = kMaxPos;
+                    lit = lit + b; if (lit > kMaxPosB) lit = kMaxPosB;
                     if (b != 255u) break;
                 }
                 if (eof) { status = LZF_UNEXPECTED_END; break; }
             }
-            if (len - p < lit) { status = LZF_UNEXPECTED_END; break; }  // :67 read_exact
-            if (cap - o < lit) { status = LZF_OUT_CAPACITY; break; }
-            wave_copy(out + o, in + p, lit, lane);                      // :65-67 (no limit check)
+            if (jv.len - p < lit) { status = LZF_UNEXPECTED_END; break; }  // :67 read_exact
+            if (jv.cap - o < lit) { status = LZF_OUT_CAPACITY; break; }
+            wave_copy(jv.out + o, jv.in + p, lit, lane);                      // :65-67 (no limit check)
             p += lit; o += lit;
 
-            if (len - p < 2u) break;                                    // :70 read_u16 Err: stop
+            if (jv.len - p < 2u) break;                                    // :70 read_u16 Err: stop
             uint32_t offset = win.byte(p, lane); offset |= win.byte(p + 1u, lane) << 8; p += 2u;
             // ---- match length: 4 + read_lsic, :71
             uint32_t mlen = token & 15u;
             if (mlen == 15u) {
                 bool eof = false;
                 for (;;) {
-                    if (p >= len) { eof = true; break; }
+                    if (p >= jv.len) { eof = true; break; }
                     const uint32_t b = win.byte(p, lane); ++p;
-                    mlen = mlen + b; if (mlen > kMaxPos) mlen = kMaxPos;
+                    mlen = mlen + b; if (mlen > kMaxPosB) mlen = kMaxPosB;
                     if (b != 255u) break;
                 }
                 if (eof) { status = LZF_UNEXPECTED_END; break; }
             }
             mlen += 4u;
-            if ((uint64_t)o + mlen > limit) { status = LZF_MEMORY_LIMIT_EXCEEDED; break; }   // :72-74
+            if ((uint64_t)o + mlen > jv.limit) { status = LZF_MEMORY_LIMIT_EXCEEDED; break; }   // :72-74
             if (offset == 0u) { status = LZF_ZERO_DEDUP_OFFSET; break; }                      // :83
             if (offset > o) {                                                                 // :84-99
                 const uint32_t need = offset - o;
-                if (need > plen) { status = LZF_INVALID_DEDUP_OFFSET; break; }                // :87-89
+                if (need > jv.plen) { status = LZF_INVALID_DEDUP_OFFSET; break; }                // :87-89
                 const uint32_t n = need < mlen ? need : mlen;                                 // :90
-                if (cap - o < n) { status = LZF_OUT_CAPACITY; break; }
-                wave_copy(out + o, prefix + (plen - need), n, lane);
+                if (jv.cap - o < n) { status = LZF_OUT_CAPACITY; break; }
+                wave_copy(jv.out + o, jv.prefix + (jv.plen - need), n, lane);
                 o += n; mlen -= n;          // rest comes from out[0..): offset now equals o
                 if (mlen == 0u) continue;
             }
-            if (cap - o < mlen) { status = LZF_OUT_CAPACITY; break; }
+            if (jv.cap - o < mlen) { status = LZF_OUT_CAPACITY; break; }
             // ---- copy_overlapping :100-135, as a period-`offset` parallel copy
             const uint32_t src0 = o - offset;
             const uint32_t span = mlen < offset ? mlen : offset;   // distinct source bytes
             if (src0 + span > safe) { wave_store_fence(); safe = o; }
-            cgu8* hist = out + src0;
-            gu8* dst = out + o;
+            cgu8* hist = jv.out + src0;
+            gu8* dst = jv.out + o;
             if (mlen <= offset) {
                 wave_copy(dst, hist, mlen, lane);                   // :104-111 non-overlapping
             } else if (offset == 1u) {                              // :102 memset

@@ -70,6 +70,7 @@ __global__ __launch_bounds__(64) void lzf_decoded_size_kernel(const lzf_decompre
             status = LZF_CONTRACT;
         } else {
             const uint32_t len = (uint32_t)input_len;
+            const DecodeJob jv{in, nullptr, nullptr, len, 0u, 0u, 0ull, 0u};      // what the parse stage reads of a job: its input (there is no output here)
             uint32_t cstart = 0;                       // a true token position (or len)
             // readers of the input in HBM / L2 for the one token looked at ahead of a chunk (wave-uniform addresses)
             auto g1 = [&](uint32_t p) -> uint32_t { return (uint32_t)in[p]; };
@@ -109,7 +110,9 @@ __global__ __launch_bounds__(64) void lzf_decoded_size_kernel(const lzf_decompre
 #include "lz4_decompress_parse_phase.inc"
 #undef LZF_THOP_RECORD
 #undef LZF_TOK_T
-                // how many bytes from p on are 0xFF (no further than len); here the run ends within a chunk
+                // the staged chunk's readers, and how many bytes from p on are 0xFF (no further than len); here the run ends within a chunk
+                auto rdb = [&](uint32_t q) -> uint32_t { return sb.rdb(q); };
+                auto rd4 = [&](uint32_t q) -> uint32_t { return sb.rd4(q); };
                 auto ffrun = [&](uint32_t p) -> uint32_t {
                     uint32_t n = 0;
                     while (p + n < len && rdb(p + n) == 255u) ++n;

@@ -1,25 +1,38 @@
 // lz4_decompress_batch_phase.inc — the COPY stage shared by the batched decompress kernels (textual include
 // inside the kernel's chunk loop; see lz4_decompress_batched.hip for the description of the stage).
-// Expects in scope: lane, in, out, prefix, len, plen, cap, limit, rb, ring, ring_a, RIDX(), ring_fill(), ring_flush(),
-// rdb(), rd4(), cstart, Tc (tokens listed for this chunk), o, safe, status, the constants RING, kSpanMax, kNearHist,
-// STAGE / cbuf_a / kCB (chunk staged in LDS or not) and the macro LZF_TOKEN_AT(i) = chunk offset of listed token i.
-// With LZF_FED_DECODE (the bitmap-fed kernel, lz4_decompress_feed_phase.inc) instead of rd4() and LZF_TOKEN_AT: toks (window
-// offsets, not yet verified), expect (where the chain's next token starts), fed_carry and bail; the set-up then decodes each token
-// once and checks the chain's links before the batch writes anything (a broken link or UnexpectedEnd: bail, the loop ends with
-// `expect` on the failing batch's first token), and a short last batch of the list may be left for the next window.
+// The stage's interface (checked below: a kernel that forgets one fails at the include):
+//   objects    lane; jv (DecodeJob: the job view); rg (OutRing<RING>: the output ring, its fill / flush); sb (StagedBytes: the staged
+//              window, rdb / rd4 — the parse and feed stages leave it); kSpanMax, kNearHist (a batch's output bytes, the intact history)
+//   carried    o, safe, status of the kernel's loop; cstart and Tc (tokens listed) of this chunk
+//   the token list, as macros the kernel defines around the include:
+//     LZF_TOKEN_AT(i)     chunk offset of listed token i
+//     LZF_TOKEN_WORD(i)   optional: entry i with the lengths the parser decoded (offset | L << 16 | (M - 4) << 24; the pair kernel)
+//     LZF_FED_DECODE      the bitmap-fed kernel, instead of the two above: toks (window offsets, not yet verified) and the carried expect
+//                         (where the chain's next token starts), fed_carry and bail; the set-up then decodes each token once and checks the
+//                         chain's links before the batch writes anything (a broken link or UnexpectedEnd: bail, the loop ends with `expect` on
+//                         the failing batch's first token), and a short last batch of the list may be left for the next window
+//     LZF_FAR_LATE        optional: the far matches' loads behind the literal copy instead of in front of it
+            LZF_STAGE_NEEDS(jv, DecodeJob); LZF_STAGE_NEEDS(rg.kRing, uint32_t); LZF_STAGE_NEEDS(sb.kCB, uint32_t); LZF_STAGE_NEEDS(lane, uint32_t);
+            LZF_STAGE_NEEDS(o, uint32_t); LZF_STAGE_NEEDS(safe, uint32_t); LZF_STAGE_NEEDS(status, int); LZF_STAGE_NEEDS(cstart, uint32_t); LZF_STAGE_NEEDS(Tc, uint32_t);
+            static_assert(kSpanMax + kNearHist == rg.kRing, "a batch's span and the intact history share the ring");
+#if defined(LZF_FED_DECODE)
+            LZF_STAGE_NEEDS(expect, uint32_t); LZF_STAGE_NEEDS(fed_carry, uint32_t); LZF_STAGE_NEEDS(bail, bool); LZF_STAGE_NEEDS(toks[0], uint16_t);
+#elif !defined(LZF_TOKEN_AT)
+#error "lz4_decompress_batch_phase.inc: define LZF_TOKEN_AT(i) (or LZF_FED_DECODE) around the include"
+#endif
             // =====================================================================
             // B. batches of up to 64 sequences: lane j owns token tidx + j
             // =====================================================================
             uint32_t tidx = 0;
             if (LZF_DBG_SKIP & 1) { tidx = Tc; o += Tc; }      // (LZF_FED_DECODE: no decode either, the chain stops after one window)
 #if defined(LZF_FED_DECODE)
-            if (LZF_DBG_SKIP & 1) expect = len;
+            if (LZF_DBG_SKIP & 1) expect = jv.len;
 #endif
             while (tidx < Tc && status == LZF_OK) {
 #if defined(LZF_FED_DECODE)
                 // a short batch at the end of the window's list waits for the next window, which starts on its first token and fills it
                 // up (lzf_fed_window.h); `expect` stands on that token.  Never the window's first batch: every window runs a batch.
-                if (lzf_fedw_carry(Tc, tidx, cstart + kRound, len, fed_carry)) break;
+                if (lzf_fedw_carry(Tc, tidx, cstart + kRound, jv.len, fed_carry)) break;
 #endif
                 PHASE(0);
 #if defined(LZF_DBG_ROUNDS) && defined(LZF_DBG_ROUNDS_HERE)
@@ -41,34 +54,34 @@
                 const uint32_t pos = toks[act0 ? tidx + lane : tidx];
                 const uint32_t tp = cstart + pos;
                 uint32_t w;                                        // token + first literal-length byte (pos < kRound: staged)
-                asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(w) : "v"(cbuf_a + pos) : "memory");
+                asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(w) : "v"(sb.lds + pos) : "memory");
                 const uint32_t l0 = (w >> 4) & 15u, b1 = (w >> 8) & 255u, m0 = w & 15u;
                 const bool lx = l0 == 15u;
                 L = l0 + (lx ? b1 : 0u);
                 src = tp + (lx ? 2u : 1u);
                 const uint32_t q = src + L;                        // the offset (a missing extension byte reads as 0: q > len then)
-                has = q + 2u <= len;                               // :70 read_u16 fails: last literals
+                has = q + 2u <= jv.len;                               // :70 read_u16 fails: last literals
                 const bool mx = has && m0 == 15u;
                 const uint32_t r1 = q + 2u - cstart;               // the match-length byte
-                const uint32_t m1 = lds_ld8(cbuf_a + (r1 < kCB ? r1 : 0u));
+                const uint32_t m1 = lds_ld8(sb.lds + (r1 < sb.kCB ? r1 : 0u));
                 M = has ? (mx ? 19u + m1 : m0 + 4u) : 0u;
-                next = has ? q + (mx ? 3u : 2u) : len;
-                bool bad = q > len || (mx && q + 2u >= len);       // :67 read_exact, read_lsic: UnexpectedEnd
-                const bool general = (lx && b1 == 255u) || (mx && (r1 >= kCB || m1 == 255u));
+                next = has ? q + (mx ? 3u : 2u) : jv.len;
+                bool bad = q > jv.len || (mx && q + 2u >= jv.len);       // :67 read_exact, read_lsic: UnexpectedEnd
+                const bool general = (lx && b1 == 255u) || (mx && (r1 >= sb.kCB || m1 == 255u));
                 if (__ballot(act0 && general)) {
                     if (general) {                                 // decompress.rs:61-71 without the copies, byte by byte
                         uint32_t p = tp + 1u, b = 0;
-                        L = l0; M = 0; has = false; next = len; bad = false;
+                        L = l0; M = 0; has = false; next = jv.len; bad = false;
                         if (lx) {
-                            do { if (p >= len) { bad = true; break; } b = rdb(p); ++p; L += b; if (L > kMaxPosB) L = kMaxPosB; } while (b == 255u);
+                            do { if (p >= jv.len) { bad = true; break; } b = sb.rdb(p); ++p; L += b; if (L > kMaxPosB) L = kMaxPosB; } while (b == 255u);
                         }
                         src = p;
-                        if (!bad && len - p < L) bad = true;       // :67 read_exact
+                        if (!bad && jv.len - p < L) bad = true;       // :67 read_exact
                         p += L;
-                        if (!bad && len - p >= 2u) {
+                        if (!bad && jv.len - p >= 2u) {
                             has = true; p += 2u; M = m0;
                             if (m0 == 15u) {
-                                do { if (p >= len) { bad = true; break; } b = rdb(p); ++p; M += b; if (M > kMaxPosB) M = kMaxPosB; } while (b == 255u);
+                                do { if (p >= jv.len) { bad = true; break; } b = sb.rdb(p); ++p; M += b; if (M > kMaxPosB) M = kMaxPosB; } while (b == 255u);
                             }
                             M += 4u; next = p;
                         }
@@ -96,20 +109,20 @@
                 if (act0) {
 #endif
                     const uint32_t tp = cstart + LZF_TOKEN_AT(tidx + lane);
-                    const uint32_t w = rd4(tp);                      // token + first literal-length extension byte
+                    const uint32_t w = sb.rd4(tp);                      // token + first literal-length extension byte
                     const uint32_t tok = w & 255u;
                     uint32_t q = tp + 1u;
                     L = tok >> 4;
                     if (L == 15u) {
                         uint32_t b = (w >> 8) & 255u; ++q;
                         L += b;
-                        while (b == 255u) { b = rdb(q); ++q; L += b; if (L > kMaxPosB) L = kMaxPosB; }
+                        while (b == 255u) { b = sb.rdb(q); ++q; L += b; if (L > kMaxPosB) L = kMaxPosB; }
                     }
                     src = q; q += L;
-                    if (len - q >= 2u) {
+                    if (jv.len - q >= 2u) {
                         has = true; q += 2u;
                         M = tok & 15u;
-                        if (M == 15u) { for (;;) { const uint32_t b = rdb(q); ++q; M += b; if (M > kMaxPosB) M = kMaxPosB; if (b != 255u) break; } }
+                        if (M == 15u) { for (;;) { const uint32_t b = sb.rdb(q); ++q; M += b; if (M > kMaxPosB) M = kMaxPosB; if (b != 255u) break; } }
                         M += 4u;
                     }
                 }
@@ -133,32 +146,32 @@
                     const uint32_t s_M = __builtin_amdgcn_readlane(M, 0);
                     const uint32_t s_src = __builtin_amdgcn_readlane(src, 0);
                     const bool s_has = __builtin_amdgcn_readlane((uint32_t)has, 0) != 0u;
-                    if (cap - o < s_L) { status = LZF_OUT_CAPACITY; break; }
-                    if (s_has && (uint64_t)o + s_L + s_M > limit) { status = LZF_MEMORY_LIMIT_EXCEEDED; break; }   // :72-74
+                    if (jv.cap - o < s_L) { status = LZF_OUT_CAPACITY; break; }
+                    if (s_has && (uint64_t)o + s_L + s_M > jv.limit) { status = LZF_MEMORY_LIMIT_EXCEEDED; break; }   // :72-74
                     const uint32_t o_before = o;
-                    wave_copy(out + o, in + s_src, s_L, lane);                           // literals :65-67
+                    wave_copy(jv.out + o, jv.in + s_src, s_L, lane);                           // literals :65-67
                     o += s_L;
                     if (s_has) {
-                        const uint32_t offset = (uint32_t)in[s_src + s_L] | ((uint32_t)in[s_src + s_L + 1u] << 8);
+                        const uint32_t offset = (uint32_t)jv.in[s_src + s_L] | ((uint32_t)jv.in[s_src + s_L + 1u] << 8);
                         uint32_t mlen = s_M;
                         if (offset == 0u) { status = LZF_ZERO_DEDUP_OFFSET; break; }      // :83
                         bool done = false;
                         if (offset > o) {                                                 // :84-99
                             const uint32_t need = offset - o;
-                            if (need > plen) { status = LZF_INVALID_DEDUP_OFFSET; break; }
+                            if (need > jv.plen) { status = LZF_INVALID_DEDUP_OFFSET; break; }
                             const uint32_t nn = need < mlen ? need : mlen;
-                            if (cap - o < nn) { status = LZF_OUT_CAPACITY; break; }
-                            wave_copy(out + o, prefix + (plen - need), nn, lane);
+                            if (jv.cap - o < nn) { status = LZF_OUT_CAPACITY; break; }
+                            wave_copy(jv.out + o, jv.prefix + (jv.plen - need), nn, lane);
                             o += nn; mlen -= nn;
                             done = mlen == 0u;
                         }
                         if (!done) {
-                            if (cap - o < mlen) { status = LZF_OUT_CAPACITY; break; }
+                            if (jv.cap - o < mlen) { status = LZF_OUT_CAPACITY; break; }
                             const uint32_t src0 = o - offset;
                             const uint32_t span = mlen < offset ? mlen : offset;
                             if (src0 + span > safe) { wave_store_fence(); safe = o; }
-                            cgu8* hist = out + src0;
-                            gu8* dst = out + o;
+                            cgu8* hist = jv.out + src0;
+                            gu8* dst = jv.out + o;
                             if (mlen <= offset) {
                                 wave_copy(dst, hist, mlen, lane);
                             } else if (offset == 1u) {
@@ -181,7 +194,7 @@
                     }
                     // ring <- the tail of what was just written
                     wave_store_fence(); safe = o;
-                    ring_fill((o - o_before > (uint32_t)RING) ? o - RING : o_before, o);
+                    rg.fill((o - o_before > rg.kRing) ? o - rg.kRing : o_before, o);
                     tidx += 1u;
                     continue;
                 }
@@ -191,18 +204,18 @@
                 if (!act) { L = 0; M = 0; }
                 uint32_t off = 0;
                 if (has) {
-                    if (!STAGE) off = ld2(in + src + L);
-                    else if (src + L - cstart + 2u <= kCB) off = lds_ld16(cbuf_a + (src + L - cstart));      // (one unaligned 2-byte LDS read)
-                    else off = rdb(src + L) | (rdb(src + L + 1u) << 8);
+                    if (!sb.kStage) off = ld2(jv.in + src + L);
+                    else if (src + L - cstart + 2u <= sb.kCB) off = lds_ld16(sb.lds + (src + L - cstart));      // (one unaligned 2-byte LDS read)
+                    else off = sb.rdb(src + L) | (sb.rdb(src + L + 1u) << 8);
                 }
                 // ---- errors, first sequence in stream order wins; inside a sequence the reference's order
                 int code = LZF_OK;
                 if (act) {
-                    if (lo > cap || cap - lo < L) code = LZF_OUT_CAPACITY;                        // our buffer (literals)
-                    else if (has && (uint64_t)mo + M > limit) code = LZF_MEMORY_LIMIT_EXCEEDED;    // :72-74
+                    if (lo > jv.cap || jv.cap - lo < L) code = LZF_OUT_CAPACITY;                        // our buffer (literals)
+                    else if (has && (uint64_t)mo + M > jv.limit) code = LZF_MEMORY_LIMIT_EXCEEDED;    // :72-74
                     else if (has && off == 0u) code = LZF_ZERO_DEDUP_OFFSET;                       // :83
-                    else if (has && off > mo && off - mo > plen) code = LZF_INVALID_DEDUP_OFFSET;  // :84-89
-                    else if (has && cap - mo < M) code = LZF_OUT_CAPACITY;                         // our buffer (match)
+                    else if (has && off > mo && off - mo > jv.plen) code = LZF_INVALID_DEDUP_OFFSET;  // :84-89
+                    else if (has && jv.cap - mo < M) code = LZF_OUT_CAPACITY;                         // our buffer (match)
                 }
                 const uint32_t e = first_lane(__ballot(code != LZF_OK));
                 if (e < 64u) { status = __builtin_amdgcn_readlane(code, e); break; }
@@ -217,7 +230,7 @@
                 const bool is_far = has && !from_prefix && s0 + span <= near_lo;
                 const bool is_slow = has && !is_near && !is_far;          // prefix or straddling
                 const uint32_t mi = RIDX(mo);
-                const bool mwrap = mi + M > (uint32_t)RING;               // destination wraps around the ring
+                const bool mwrap = mi + M > rg.kRing;               // destination wraps around the ring
                 // HBM visibility of what far / slow lanes read back
                 {
                     uint32_t need = 0;
@@ -233,7 +246,7 @@
                 uint64_t fv0 = 0, fv1 = 0, fv2 = 0, fv3 = 0;
 #ifndef LZF_FAR_LATE
                 if (far_own) {
-                    cgu8* g = out + s0;
+                    cgu8* g = jv.out + s0;
                     if (M >= 8u) {
                         fv0 = ld8(g); fv3 = ld8(g + M - 8u);
                         if (M > 16u) { fv1 = ld8(g + 8u); fv2 = ld8(g + M - 16u); }
@@ -247,12 +260,12 @@
                     const uint32_t n1 = L < kShort ? L : kShort;            // the lane's own share
                     const uint32_t ri = RIDX(lo);
                     if (n1 > 0u) {
-                        if (ri + n1 > (uint32_t)RING) {                     // wraps around the ring: bytes
-                            for (uint32_t t = 0; t < n1; ++t) ring[RIDX(lo + t)] = (uint8_t)rdb(src + t);
-                        } else if (STAGE && src - cstart + n1 <= kCB) {
-                            put_small_lds(ring_a + ri, cbuf_a + (src - cstart), n1);
+                        if (ri + n1 > rg.kRing) {                     // wraps around the ring: bytes
+                            for (uint32_t t = 0; t < n1; ++t) rg.ring[RIDX(lo + t)] = (uint8_t)sb.rdb(src + t);
+                        } else if (sb.kStage && src - cstart + n1 <= sb.kCB) {
+                            put_small_lds(rg.lds + ri, sb.lds + (src - cstart), n1);
                         } else {
-                            put_small_glb(ring_a + ri, in + src, n1);
+                            put_small_glb(rg.lds + ri, jv.in + src, n1);
                         }
                     }
                     for (unsigned long long m = __ballot(L > kShort); m; m &= m - 1ull) {      // long runs: all lanes
@@ -262,14 +275,14 @@
                         const uint32_t jo = __builtin_amdgcn_readlane(lo, j);
                         for (uint32_t i = kShort + lane; i < jl; i += 4u * kWave) {
                             const uint32_t i1 = i + kWave, i2 = i + 2u * kWave, i3 = i + 3u * kWave;
-                            const uint8_t b0 = in[js + i];
-                            const uint8_t b1 = i1 < jl ? in[js + i1] : (uint8_t)0;
-                            const uint8_t b2 = i2 < jl ? in[js + i2] : (uint8_t)0;
-                            const uint8_t b3 = i3 < jl ? in[js + i3] : (uint8_t)0;
-                            ring[RIDX(jo + i)] = b0;
-                            if (i1 < jl) ring[RIDX(jo + i1)] = b1;
-                            if (i2 < jl) ring[RIDX(jo + i2)] = b2;
-                            if (i3 < jl) ring[RIDX(jo + i3)] = b3;
+                            const uint8_t b0 = jv.in[js + i];
+                            const uint8_t b1 = i1 < jl ? jv.in[js + i1] : (uint8_t)0;
+                            const uint8_t b2 = i2 < jl ? jv.in[js + i2] : (uint8_t)0;
+                            const uint8_t b3 = i3 < jl ? jv.in[js + i3] : (uint8_t)0;
+                            rg.ring[RIDX(jo + i)] = b0;
+                            if (i1 < jl) rg.ring[RIDX(jo + i1)] = b1;
+                            if (i2 < jl) rg.ring[RIDX(jo + i2)] = b2;
+                            if (i3 < jl) rg.ring[RIDX(jo + i3)] = b3;
                         }
                     }
                 }
@@ -277,7 +290,7 @@
 
 #ifdef LZF_FAR_LATE      // (the loads here instead of in front of the literals: eight registers fewer across the literal copy)
                 if (far_own) {
-                    cgu8* g = out + s0;
+                    cgu8* g = jv.out + s0;
                     if (M >= 8u) {
                         fv0 = ld8(g); fv3 = ld8(g + M - 8u);
                         if (M > 16u) { fv1 = ld8(g + 8u); fv2 = ld8(g + M - 16u); }
@@ -287,7 +300,7 @@
                 }
 #endif
                 if (far_own) {
-                    const uint32_t dsta = ring_a + mi;
+                    const uint32_t dsta = rg.lds + mi;
                     if (M >= 8u) {
                         lds_st64(dsta, fv0);
                         if (M > 16u) { lds_st64(dsta + 8u, fv1); lds_st64(dsta + M - 16u, fv2); }
@@ -297,8 +310,8 @@
                     }
                 }
                 if (!(LZF_DBG_SKIP & 4) && __ballot(is_far && !far_own)) {
-                    if (is_far && M <= kShort && mwrap) { for (uint32_t t = 0; t < M; ++t) ring[RIDX(mo + t)] = out[s0 + t]; }
-                    if (is_far && M > kFarShort && M <= kShort && !mwrap) put_small_glb(ring_a + mi, out + s0, M);   // 33..64 bytes: own loads now
+                    if (is_far && M <= kShort && mwrap) { for (uint32_t t = 0; t < M; ++t) rg.ring[RIDX(mo + t)] = jv.out[s0 + t]; }
+                    if (is_far && M > kFarShort && M <= kShort && !mwrap) put_small_glb(rg.lds + mi, jv.out + s0, M);   // 33..64 bytes: own loads now
                     for (unsigned long long m = __ballot(is_far && M > kShort); m; m &= m - 1ull) {
                         const uint32_t j = (uint32_t)__builtin_ctzll(m);
                         const uint32_t jm = __builtin_amdgcn_readlane(M, j);
@@ -306,14 +319,14 @@
                         const uint32_t jo = __builtin_amdgcn_readlane(mo, j);
                         for (uint32_t i = lane; i < jm; i += 4u * kWave) {
                             const uint32_t i1 = i + kWave, i2 = i + 2u * kWave, i3 = i + 3u * kWave;
-                            const uint8_t b0 = out[js + i];
-                            const uint8_t b1 = i1 < jm ? out[js + i1] : (uint8_t)0;
-                            const uint8_t b2 = i2 < jm ? out[js + i2] : (uint8_t)0;
-                            const uint8_t b3 = i3 < jm ? out[js + i3] : (uint8_t)0;
-                            ring[RIDX(jo + i)] = b0;
-                            if (i1 < jm) ring[RIDX(jo + i1)] = b1;
-                            if (i2 < jm) ring[RIDX(jo + i2)] = b2;
-                            if (i3 < jm) ring[RIDX(jo + i3)] = b3;
+                            const uint8_t b0 = jv.out[js + i];
+                            const uint8_t b1 = i1 < jm ? jv.out[js + i1] : (uint8_t)0;
+                            const uint8_t b2 = i2 < jm ? jv.out[js + i2] : (uint8_t)0;
+                            const uint8_t b3 = i3 < jm ? jv.out[js + i3] : (uint8_t)0;
+                            rg.ring[RIDX(jo + i)] = b0;
+                            if (i1 < jm) rg.ring[RIDX(jo + i1)] = b1;
+                            if (i2 < jm) rg.ring[RIDX(jo + i2)] = b2;
+                            if (i3 < jm) rg.ring[RIDX(jo + i3)] = b3;
                         }
                     }
                 }
@@ -328,7 +341,7 @@
                 // LDS runs one wave's accesses in order, so no wait separates dependent rounds.
                 {
                     const uint32_t si = RIDX(s0);
-                    const bool solo_ok = is_near && M <= off && M <= kShort && !mwrap && !(si + M > (uint32_t)RING);
+                    const bool solo_ok = is_near && M <= off && M <= kShort && !mwrap && !(si + M > rg.kRing);
                     const unsigned long long solo_mask = __ballot(solo_ok);
                     uint32_t src_end = solo_ok ? s0 + span : 0xFFFFFFFFu;     // ~0 once the lane's match has been moved
                     if (LZF_DBG_SKIP & 2) unresolved = 0;
@@ -341,7 +354,7 @@
                         if (solo_mask & bit) {
                             const uint32_t H = __builtin_amdgcn_readlane(mo, f);
                             const bool mine = src_end <= H;                    // includes lane f
-                            if (mine) { put_match_lds(ring_a + mi, ring_a + si, M); src_end = 0xFFFFFFFFu; }
+                            if (mine) { put_match_lds(rg.lds + mi, rg.lds + si, M); src_end = 0xFFFFFFFFu; }
 #if defined(LZF_DBG_ROUNDS) && defined(LZF_DBG_ROUNDS_HERE) && LZF_DBG_ROUNDS >= 3      // analysis: active lanes of the rounds (s_bcnt1 of the lanes that move)
                             { const uint32_t nl = (uint32_t)__builtin_popcountll(__ballot(mine));
                               dbg_lane_stat += LZF_DBG_ROUNDS == 3 ? nl : LZF_DBG_ROUNDS == 4 ? 1u : LZF_DBG_ROUNDS == 5 ? (nl == 1u) : LZF_DBG_ROUNDS == 6 ? (nl >= 2u && nl <= 4u)
@@ -356,12 +369,12 @@
                             if (lane == f) {
                                 for (uint32_t t = 0; t < M; ++t) {
                                     uint8_t v;
-                                    if (off > mo + t) v = prefix[plen - (off - mo) + t];                // :91-93
+                                    if (off > mo + t) v = jv.prefix[jv.plen - (off - mo) + t];                // :91-93
                                     else {
                                         const uint32_t s = mo + t - off;
-                                        v = s < near_lo ? out[s] : ring[RIDX(s)];
+                                        v = s < near_lo ? jv.out[s] : rg.ring[RIDX(s)];
                                     }
-                                    ring[RIDX(mo + t)] = v;
+                                    rg.ring[RIDX(mo + t)] = v;
                                 }
                             }
                             continue;
@@ -373,20 +386,20 @@
                         if (jm <= joff) {                                   // non-overlapping: 4 bytes in flight per lane
                             for (uint32_t i = lane; i < jm; i += 4u * kWave) {
                                 const uint32_t i1 = i + kWave, i2 = i + 2u * kWave, i3 = i + 3u * kWave;
-                                const uint8_t b0 = ring[RIDX(js + i)];
-                                const uint8_t b1 = i1 < jm ? ring[RIDX(js + i1)] : (uint8_t)0;
-                                const uint8_t b2 = i2 < jm ? ring[RIDX(js + i2)] : (uint8_t)0;
-                                const uint8_t b3 = i3 < jm ? ring[RIDX(js + i3)] : (uint8_t)0;
-                                ring[RIDX(jo + i)] = b0;
-                                if (i1 < jm) ring[RIDX(jo + i1)] = b1;
-                                if (i2 < jm) ring[RIDX(jo + i2)] = b2;
-                                if (i3 < jm) ring[RIDX(jo + i3)] = b3;
+                                const uint8_t b0 = rg.ring[RIDX(js + i)];
+                                const uint8_t b1 = i1 < jm ? rg.ring[RIDX(js + i1)] : (uint8_t)0;
+                                const uint8_t b2 = i2 < jm ? rg.ring[RIDX(js + i2)] : (uint8_t)0;
+                                const uint8_t b3 = i3 < jm ? rg.ring[RIDX(js + i3)] : (uint8_t)0;
+                                rg.ring[RIDX(jo + i)] = b0;
+                                if (i1 < jm) rg.ring[RIDX(jo + i1)] = b1;
+                                if (i2 < jm) rg.ring[RIDX(jo + i2)] = b2;
+                                if (i3 < jm) rg.ring[RIDX(jo + i3)] = b3;
                             }
                         } else {                                            // overlapping: period-`offset` addressing
                             uint32_t rr = lane % joff;
                             const uint32_t adv = kWave % joff;
                             for (uint32_t i = lane; i < jm; i += kWave) {
-                                ring[RIDX(jo + i)] = ring[RIDX(js + rr)];
+                                rg.ring[RIDX(jo + i)] = rg.ring[RIDX(js + rr)];
                                 rr += adv; if (rr >= joff) rr -= joff;
                             }
                         }
@@ -395,7 +408,7 @@
                 PHASE(4);
                 // ---- flush the batch ring -> HBM
                 o = ob0 + __builtin_amdgcn_readlane(incl, (nb - 1u) & 63u);
-                if (!(LZF_DBG_SKIP & 16)) ring_flush(ob0, o);
+                if (!(LZF_DBG_SKIP & 16)) rg.flush(ob0, o);
                 tidx += nb;
                 PHASE(5);
             }

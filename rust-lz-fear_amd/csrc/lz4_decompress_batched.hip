@@ -41,15 +41,14 @@
 #include "kernels.h"
 #include "lzf_copy_helpers.h"
 #include "lzf_parse_helpers.h"
+#include "lzf_phase_timers.h"
 
 namespace lzf {
-
 
 template <int RING, int S, int TOKCAP, bool STAGE>
 __global__ __launch_bounds__(64) void lzf_decompress_batched_kernel(
     const lzf_decompress_job* __restrict__ jobs, lzf_job_result* __restrict__ results, uint32_t n_jobs,
     const uint32_t* __restrict__ perm) {
-    constexpr uint32_t kMask = RING - 1;
 #ifndef LZF_SPAN_DIV
 #define LZF_SPAN_DIV 3
 #endif
@@ -80,58 +79,19 @@ __global__ __launch_bounds__(64) void lzf_decompress_batched_kernel(
 
     int status = LZF_OK;
     uint32_t o = 0;
-#ifdef LZF_PHASE_TIMING
-    long long g_tph[6] = {0, 0, 0, 0, 0, 0}; uint32_t g_pk_hi = 0;
-#endif
-    if (job.input_len >= kMaxPosB || job.out_existing_len >= kMaxPosB || job.prefix_len >= kMaxPosB || job.out_existing_len > job.out_cap) {
+    PhaseTimers ph;
+    if (LZF_DECODE_JOB_OUT_OF_CONTRACT(job)) {
         status = LZF_CONTRACT;
     } else {
-        cgu8* __restrict__ in = as_global(job.input);
-        cgu8* __restrict__ prefix = as_global(job.prefix);
-        gu8* out = as_global(job.out);
-        const uint32_t len = (uint32_t)job.input_len;
-        const uint32_t plen = (uint32_t)job.prefix_len;
-        const uint32_t cap = job.out_cap > kMaxPosB ? kMaxPosB : (uint32_t)job.out_cap;
-        const uint64_t limit = job.output_limit;
-        const uint32_t rb = (uint32_t)(reinterpret_cast<uintptr_t>(out) & 15u);   // ring bias
-        const uint32_t ring_a = lds_addr(ring), cbuf_a = lds_addr(cbuf), nxt_a = lds_addr(nxt), ex_a = lds_addr(tokex);
-#define RIDX(x) (((x) + rb) & kMask)
-
-        // ring <- out[a, b)   (b - a <= RING; caller made out[a,b) visible)
-        auto ring_fill = [&](uint32_t a, uint32_t b) {
-            uint32_t nh = (16u - ((a + rb) & 15u)) & 15u; if (nh > b - a) nh = b - a;
-            if (lane < nh) ring[RIDX(a + lane)] = out[a + lane];
-            a += nh;
-            const uint32_t nchunks = (b - a) >> 4;
-            for (uint32_t c = lane; c < nchunks; c += kWave)
-                *reinterpret_cast<u32x4*>(&ring[RIDX(a + 16u * c)]) = *reinterpret_cast<const LZF_GLOBAL u32x4*>(out + a + 16u * c);
-            a += nchunks << 4;
-            if (lane < b - a) ring[RIDX(a + lane)] = out[a + lane];
-        };
-        // out[a, b) <- ring
-        auto ring_flush = [&](uint32_t a, uint32_t b) {
-            uint32_t nh = (16u - ((a + rb) & 15u)) & 15u; if (nh > b - a) nh = b - a;
-            if (lane < nh) out[a + lane] = ring[RIDX(a + lane)];
-            a += nh;
-            const uint32_t nchunks = (b - a) >> 4;
-            for (uint32_t c = lane; c < nchunks; c += kWave)
-                *reinterpret_cast<LZF_GLOBAL u32x4*>(out + a + 16u * c) = *reinterpret_cast<const u32x4*>(&ring[RIDX(a + 16u * c)]);
-            a += nchunks << 4;
-            if (lane < b - a) out[a + lane] = ring[RIDX(a + lane)];
-        };
-
+        const DecodeJob jv = LZF_DECODE_JOB_VIEW(job);
+        const OutRing<RING> rg{ring, jv.out, jv.rb, lane, lds_addr(ring)};
+        const uint32_t cbuf_a = lds_addr(cbuf), nxt_a = lds_addr(nxt), ex_a = lds_addr(tokex);
         o = (uint32_t)job.out_existing_len;
         uint32_t safe = o;   // out[0, safe) is visible to this wave's global loads
-        if (o > 0) ring_fill(o > (uint32_t)RING ? o - RING : 0u, o);   // Vec content on entry = history
-
-#ifdef LZF_PHASE_TIMING
-        long long tph[6] = {0, 0, 0, 0, 0, 0}; long long tq = clock64();
-#define PHASE(i) do { const long long tn = clock64(); tph[i] += tn - tq; tq = tn; } while (0)
-#else
-#define PHASE(i) do { } while (0)
-#endif
+        if (o > 0) rg.fill(o > (uint32_t)RING ? o - RING : 0u, o);   // Vec content on entry = history
+        ph.start();
         uint32_t cstart = 0;                 // a true token position (or len)
-        while (cstart < len && status == LZF_OK) {
+        while (cstart < jv.len && status == LZF_OK) {
 #define LZF_TOK_T uint16_t
 #define LZF_THOP_RECORD thop_loop_record
 #include "lz4_decompress_parse_phase.inc"
@@ -145,25 +105,12 @@ __global__ __launch_bounds__(64) void lzf_decompress_batched_kernel(
             if (status == LZF_OK && cerr != LZF_OK) status = cerr;
             cstart = cend;
         }
-#ifdef LZF_PHASE_TIMING
-        for (int i = 0; i < 6; ++i) g_tph[i] = tph[i];
-#endif
-#undef RIDX
     }
     if (lane == 0) {
         results[jid].out_len = o;
-#ifdef LZF_PHASE_TIMING
-        // debug build only: six phase totals, 10 bits each in units of 2^20 cycles, above bit 32 / in `reserved`
-        {
-            unsigned long long pk = 0;
-            for (int i = 0; i < 6; ++i) { unsigned long long u = (unsigned long long)(g_tph[i] >> 20); if (u > 1023) u = 1023; pk |= u << (10 * i); }
-            results[jid].out_len = (unsigned long long)o | ((pk & 0xFFFFFFFFull) << 32);
-            g_pk_hi = (uint32_t)(pk >> 32);
-        }
-#endif
         results[jid].status = status;
 #ifdef LZF_PHASE_TIMING
-        results[jid].reserved = g_pk_hi;
+        ph.report(results[jid]);
 #else
         results[jid].reserved = (uint32_t)((clock64() - t_start) >> 10);   // diagnostic: shader kilo-cycles spent on this job
 #endif

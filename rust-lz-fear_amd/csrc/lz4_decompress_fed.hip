@@ -19,6 +19,7 @@
 #include "lzf_device.h"
 #include "kernels.h"
 #include "lzf_copy_helpers.h"
+#include "lzf_phase_timers.h"
 #include "lzf_fed_window.h"
 #include "lzf_dispatch.h"
 
@@ -46,8 +47,6 @@ __device__ __forceinline__ uint32_t xcc_id() {
 // ---------------------------------------------------------------------------------------------------------------------
 template <int RING, int W, int TOKCAP>
 __global__ LZF_FED_BOUNDS void lzf_decompress_fed_kernel(fed_args a) {      // (kernels.h: six waves per SIMD, bound on the declaration too)
-    constexpr bool STAGE = true;
-    constexpr uint32_t kMask = RING - 1;
     constexpr uint32_t kSpanMax = RING / 3;            // output bytes one batch may produce
     constexpr uint32_t kNearHist = RING - kSpanMax;    // history before the batch that stays intact in the ring
     constexpr uint32_t kRound = 32u * (uint32_t)W;     // compressed bytes whose tokens one round lists
@@ -103,55 +102,22 @@ __global__ LZF_FED_BOUNDS void lzf_decompress_fed_kernel(fed_args a) {      // (
     int status = LZF_OK;
     bool bailed = false, parked = false;
     uint32_t o = 0;
-#ifdef LZF_DBG_PHASE_SEL
-    long long ph_acc_out = 0;
-#endif
+    PhaseTimers ph;
 #ifdef LZF_DBG_FED_COUNT   // analysis: [0] batches, [1] windows listed from the map, [2] windows walked, of this wave's share of the job (LZF_FED_PIECES=1: the job) -> results[].reserved
     uint32_t dbg_fed[3] = {0u, 0u, 0u};
 #endif
-    if (job.input_len >= kMaxPosB || job.out_existing_len >= kMaxPosB || job.prefix_len >= kMaxPosB || job.out_existing_len > job.out_cap) continue;   // (LZF_CONTRACT: the pair kernel says so)
+    if (LZF_DECODE_JOB_OUT_OF_CONTRACT(job)) continue;      // (LZF_CONTRACT: the pair kernel says so)
     {
-        cgu8* __restrict__ in = as_global(job.input);
-        cgu8* __restrict__ prefix = as_global(job.prefix);
-        gu8* out = as_global(job.out);
-        const uint32_t len = (uint32_t)job.input_len;
-        const uint32_t plen = (uint32_t)job.prefix_len;
-        const uint32_t cap = job.out_cap > kMaxPosB ? kMaxPosB : (uint32_t)job.out_cap;
-        const uint64_t limit = job.output_limit;
-        const uint32_t rb = (uint32_t)(reinterpret_cast<uintptr_t>(out) & 15u);   // ring bias
-        const uint32_t ring_a = lds_addr(ring), cbuf_a = lds_addr(cbuf);
+        const DecodeJob jv = LZF_DECODE_JOB_VIEW(job);
+        const OutRing<RING> rg{ring, jv.out, jv.rb, lane, lds_addr(ring)};
+        const uint32_t cbuf_a = lds_addr(cbuf);
         const LZF_GLOBAL uint32_t* const fed_bits = (const LZF_GLOBAL uint32_t*)a.bits + (size_t)jid * a.maxch * kSegChunkWords;
-#define RIDX(x) (((x) + rb) & kMask)
-
-        // ring <- out[a, b)   (b - a <= RING; caller made out[a,b) visible)
-        auto ring_fill = [&](uint32_t a_, uint32_t b) {
-            uint32_t nh = (16u - ((a_ + rb) & 15u)) & 15u; if (nh > b - a_) nh = b - a_;
-            if (lane < nh) ring[RIDX(a_ + lane)] = out[a_ + lane];
-            a_ += nh;
-            const uint32_t nchunks = (b - a_) >> 4;
-            for (uint32_t c = lane; c < nchunks; c += kWave)
-                *reinterpret_cast<u32x4*>(&ring[RIDX(a_ + 16u * c)]) = *reinterpret_cast<const LZF_GLOBAL u32x4*>(out + a_ + 16u * c);
-            a_ += nchunks << 4;
-            if (lane < b - a_) ring[RIDX(a_ + lane)] = out[a_ + lane];
-        };
-        // out[a, b) <- ring
-        auto ring_flush = [&](uint32_t a_, uint32_t b) {
-            uint32_t nh = (16u - ((a_ + rb) & 15u)) & 15u; if (nh > b - a_) nh = b - a_;
-            if (lane < nh) out[a_ + lane] = ring[RIDX(a_ + lane)];
-            a_ += nh;
-            const uint32_t nchunks = (b - a_) >> 4;
-            for (uint32_t c = lane; c < nchunks; c += kWave)
-                *reinterpret_cast<LZF_GLOBAL u32x4*>(out + a_ + 16u * c) = *reinterpret_cast<const u32x4*>(&ring[RIDX(a_ + 16u * c)]);
-            a_ += nchunks << 4;
-            if (lane < b - a_) out[a_ + lane] = ring[RIDX(a_ + lane)];
-        };
-
         uint32_t expect = 0;                 // where the next token of the chain starts (len: the chain has ended)
         uint32_t cstart = 0;
         o = (uint32_t)job.out_existing_len;
         // this piece: the tokens that start in rounds [piece, piece + 1) * per of the job's input
-        const uint32_t rounds = (len + kRound - 1u) / kRound, per = (rounds + pieces - 1u) / pieces;
-        const uint32_t piece_end = (piece + 1u) * per >= rounds ? len : (piece + 1u) * per * kRound;
+        const uint32_t rounds = (jv.len + kRound - 1u) / kRound, per = (rounds + pieces - 1u) / pieces;
+        const uint32_t piece_end = (piece + 1u) * per >= rounds ? jv.len : (piece + 1u) * per * kRound;
         if (piece > 0u) {
             // the piece before this one was drawn n tickets ago: as a rule it is done; else wait for it (bounded), then take its state over
             uint32_t f = 0;
@@ -166,14 +132,8 @@ __global__ LZF_FED_BOUNDS void lzf_decompress_fed_kernel(fed_args a) {      // (
             expect = fs->expect; o = fs->o;  // (a short batch the piece before left at its end is simply this piece's first)
         }
         uint32_t safe = o;   // out[0, safe) is visible to this wave's global loads
-        if (o > 0) ring_fill(o > (uint32_t)RING ? o - RING : 0u, o);   // Vec content on entry (or what the other slot wrote) = history
-#ifdef LZF_DBG_PHASE_SEL   // analysis: cycles the wave spends in section LZF_DBG_PHASE_SEL (section i ends at PHASE(i); 0-5: the copy stage's, lz4_decompress_paired.hip,
-                           // 1 here with the tokens' decode and the chain check; 6 stage + bit map, 7 bit map -> list) -> results[].reserved
-        long long ph_t = clock64(), ph_acc = 0;
-#define PHASE(i) do { const long long tn__ = clock64(); if ((i) == LZF_DBG_PHASE_SEL) ph_acc += tn__ - ph_t; ph_t = tn__; } while (0)
-#else
-#define PHASE(i) do { } while (0)
-#endif
+        if (o > 0) rg.fill(o > (uint32_t)RING ? o - RING : 0u, o);   // Vec content on entry (or what the other slot wrote) = history
+        ph.start();          // (section 1 here with the tokens' decode and the chain check: lzf_phase_timers.h)
 #if defined(LZF_FED_FIXED_ROUNDS)
         constexpr int kFixed = 1;
         const uint32_t fed_carry = 0u;
@@ -188,7 +148,7 @@ __global__ LZF_FED_BOUNDS void lzf_decompress_fed_kernel(fed_args a) {      // (
         // INVARIANT of the loop: a pass either ends the job for this kernel (status, bailed), parks it, asks for the same window again
         // in walk mode (once: a failure in walk mode ends the job), or runs at least one batch — a window's first batch is never
         // carried, and a batch that passes its checks moves `expect` on by a token or more.  The last `if` holds the loop to that.
-        while (expect < len && status == LZF_OK) {
+        while (expect < jv.len && status == LZF_OK) {
             if (expect >= piece_end) { parked = true; break; }      // the next piece's
             const uint32_t expect_in = expect;
             cstart = lzf_fedw_start(expect, kFixed);
@@ -213,11 +173,6 @@ __global__ LZF_FED_BOUNDS void lzf_decompress_fed_kernel(fed_args a) {      // (
             fed_walk = false;
             if (expect == expect_in && status == LZF_OK) { bailed = true; break; }      // (no progress: never, by the invariant — and never a spin)
         }
-#ifdef LZF_DBG_PHASE_SEL
-        ph_acc_out = ph_acc;
-#endif
-#undef PHASE
-#undef RIDX
         if (parked && status == LZF_OK && !bailed) {
             // hand the job on: what this wave wrote must be visible to another compute unit before the flag is
             if (lane == 0u) { fs->expect = expect; fs->o = o; }
@@ -236,7 +191,7 @@ __global__ LZF_FED_BOUNDS void lzf_decompress_fed_kernel(fed_args a) {      // (
 #ifdef LZF_DBG_FED_COUNT
         a.results[jid].reserved = dbg_fed[LZF_DBG_FED_COUNT];
 #elif defined(LZF_DBG_PHASE_SEL)
-        a.results[jid].reserved = (uint32_t)(ph_acc_out >> 10);
+        ph.report(a.results[jid]);
 #elif defined(LZF_DBG_TIMELINE)   // analysis: when the job ran, on the 100 MHz wall clock every wave reads alike (units of 2.56 us): start << 16 | end
         a.results[jid].reserved = (uint32_t)(((t_wall0 >> 8) & 0xFFFFull) << 16) | (uint32_t)((wall_clock64() >> 8) & 0xFFFFull);
 #else

@@ -23,28 +23,25 @@
 // mode (a token whose body leaves the input: UnexpectedEnd) is a real one: the job is left to the pair kernel, which decodes it
 // from its first byte and reports the reference's status.  The next window tries the map again.
 //
-// Expects in scope: lane, in, len, cstart (window start), cbuf / cbuf_a (kCB staged bytes), toks (uint16_t[TOKCAP]),
-// fed_bits (the job's rows of seg_ctx::bits), expect (uniform, cstart <= expect < cstart + 32 — kRound with fixed rounds),
-// fed_walk (uniform), the constants W, TOKCAP, kRound, kCB.
-// Leaves: Tc (tokens listed for this window), bail (uniform), and the lambda rdb for the copy stage.  Token-list entry = the
-// token's offset in the window (< kRound), two aligned bytes.
+// The stage's interface (checked below): lane, jv (DecodeJob); cstart (window start) and expect (uniform, cstart <= expect < cstart + 32 —
+// kRound with fixed rounds) of the kernel's loop; fed_walk (uniform); cbuf / cbuf_a (kCB staged bytes), toks (uint16_t[TOKCAP]), fed_bits (the
+// job's rows of seg_ctx::bits), the constants W, TOKCAP, kRound, kCB.  Leaves: sb (StagedBytes over the window), Tc (tokens listed for this
+// window), bail (uniform).  Token-list entry = the token's offset in the window (< kRound), two aligned bytes.
 // (Three-byte entries of offset and pre-decoded lengths were measured: 97.5 -> 110 ms per call, misaligned DS accesses.)
+            LZF_STAGE_NEEDS(jv, DecodeJob); LZF_STAGE_NEEDS(lane, uint32_t); LZF_STAGE_NEEDS(cstart, uint32_t); LZF_STAGE_NEEDS(expect, uint32_t);
+            LZF_STAGE_NEEDS(fed_walk, bool); LZF_STAGE_NEEDS(cbuf[0], uint8_t); LZF_STAGE_NEEDS(toks[0], uint16_t); LZF_STAGE_NEEDS(fed_bits[0] + 0u, uint32_t);
+            static_assert(kRound == 32u * (uint32_t)W && kCB >= kRound && TOKCAP > 0, "the window's geometry");
             uint32_t Tc = 0;
             bool bail = false;
-            // byte of the input at absolute position q >= cstart (LDS while staged; asm on purpose, see lz4_decompress_parse_phase.inc)
-            auto rdb = [&](uint32_t q) -> uint32_t {
-                const uint32_t r = q - cstart;
-                if (r < kCB) return lds_ld8(cbuf_a + r);
-                return (uint32_t)in[q];
-            };
+            const StagedBytes<true, kCB> sb{cbuf_a, cstart, jv.len, jv.in};      // the staged window, for walk mode and for the copy stage
             {
                 // ---- F0. stage in[cstart, cstart + kCB) (zeros beyond the input) and fetch the window's words of the bit map
                 // (Asking for the next round one round ahead — held in registers, or one load per 64 bytes to bring its lines into
                 // L2 — changed nothing at five or at six waves per SIMD: the other wavefronts already cover this round trip,
                 // profiles/fed_residency_prefetch.txt section 3.)
                 {
-                    const uint32_t avail = len - cstart < kCB ? len - cstart : kCB;
-                    cgu8* g = in + cstart;
+                    const uint32_t avail = jv.len - cstart < kCB ? jv.len - cstart : kCB;
+                    cgu8* g = jv.in + cstart;
                     constexpr uint32_t kPieces = (kCB + 1023u) / 1024u;
                     u32x4 v[kPieces];
 #pragma unroll
@@ -58,12 +55,12 @@
                     // first kSegChunk bytes, chunk h >= 1 the kSegStride bytes from h * kSegStride + kSegOverlap on)
                     uint32_t w = 0;
                     const uint32_t wpos = cstart + lane * 32u;                 // position of bit 0
-                    if (!fed_walk && lane < (uint32_t)W && wpos < len) {
+                    if (!fed_walk && lane < (uint32_t)W && wpos < jv.len) {
                         const uint32_t h = lzf_fedw_chunk(wpos);
                         w = fed_bits[(size_t)h * kSegChunkWords + lzf_fedw_word(wpos, h)];
                         if (expect >= wpos + 32u) w = 0u;                      // marks below the chain's position are not the chain's
                         else if (expect > wpos) w &= ~((1u << (expect - wpos)) - 1u);
-                        if (len - wpos < 32u) w &= (1u << (len - wpos)) - 1u;
+                        if (jv.len - wpos < 32u) w &= (1u << (jv.len - wpos)) - 1u;
                     }
 #pragma unroll
                     for (uint32_t k = 0; k < kPieces; ++k) {
@@ -86,16 +83,16 @@
                         uint32_t np = 0, werr = 0;
                         if (lane == 0u) {
                             uint32_t p = expect;
-                            while (p - cstart < kRound && p < len && np < (uint32_t)TOKCAP) {
+                            while (p - cstart < kRound && p < jv.len && np < (uint32_t)TOKCAP) {
                                 toks[np++] = (uint16_t)(p - cstart);
-                                const uint32_t tok = rdb(p);
+                                const uint32_t tok = sb.rdb(p);
                                 uint32_t q = p + 1u, L = tok >> 4, b = 0;
-                                if (L == 15u) { do { if (q >= len) { werr = 1u; break; } b = rdb(q); ++q; L += b; if (L > kMaxPosB) L = kMaxPosB; } while (b == 255u); }
-                                if (werr || len - q < L) { werr = 1u; break; }      // :67 read_exact
+                                if (L == 15u) { do { if (q >= jv.len) { werr = 1u; break; } b = sb.rdb(q); ++q; L += b; if (L > kMaxPosB) L = kMaxPosB; } while (b == 255u); }
+                                if (werr || jv.len - q < L) { werr = 1u; break; }      // :67 read_exact
                                 q += L;
-                                if (len - q < 2u) { p = len; break; }               // :70 read_u16 fails: last literals
+                                if (jv.len - q < 2u) { p = jv.len; break; }               // :70 read_u16 fails: last literals
                                 q += 2u;
-                                if ((tok & 15u) == 15u) { do { if (q >= len) { werr = 1u; break; } b = rdb(q); ++q; } while (b == 255u); }
+                                if ((tok & 15u) == 15u) { do { if (q >= jv.len) { werr = 1u; break; } b = sb.rdb(q); ++q; } while (b == 255u); }
                                 if (werr) break;
                                 p = q;
                             }

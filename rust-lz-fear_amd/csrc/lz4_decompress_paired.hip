@@ -9,6 +9,7 @@
 #include "kernels.h"
 #include "lzf_copy_helpers.h"
 #include "lzf_parse_helpers.h"
+#include "lzf_phase_timers.h"
 #include "lzf_dispatch.h"
 
 namespace lzf {
@@ -18,7 +19,6 @@ __global__ __launch_bounds__(128) void lzf_decompress_paired_kernel(
     const lzf_decompress_job* __restrict__ jobs, lzf_job_result* __restrict__ results, uint32_t n_jobs,
     const uint32_t* __restrict__ perm, const seg_job* __restrict__ done) {
     constexpr bool STAGE = true;
-    constexpr uint32_t kMask = RING - 1;
     constexpr uint32_t kSpanMax = RING / 3;            // output bytes one batch may produce
     constexpr uint32_t kNearHist = RING - kSpanMax;    // history before the batch that stays intact in the ring
     constexpr uint32_t kChunk = 64u * S;               // compressed bytes whose tokens one parse covers
@@ -49,57 +49,17 @@ __global__ __launch_bounds__(128) void lzf_decompress_paired_kernel(
 
     int status = LZF_OK;
     uint32_t o = 0;
-#ifdef LZF_DBG_PHASE_SEL
-    long long ph_acc_out = 0;
-#endif
+    PhaseTimers ph;          // (the copier's: section 0 is what lies between its batches — loop control, chunk hand-over, waiting for the parser)
 #ifdef LZF_DBG_ROUNDS
     uint32_t dbg_rounds = 0, dbg_batches = 0, dbg_lane_stat = 0;
 #endif
-    if (job.input_len >= kMaxPosB || job.out_existing_len >= kMaxPosB || job.prefix_len >= kMaxPosB || job.out_existing_len > job.out_cap) {
+    if (LZF_DECODE_JOB_OUT_OF_CONTRACT(job)) {
         status = LZF_CONTRACT;                         // (uniform over the workgroup: no barrier is reached)
     } else {
-        cgu8* __restrict__ in = as_global(job.input);
-        cgu8* __restrict__ prefix = as_global(job.prefix);
-        gu8* out = as_global(job.out);
-        const uint32_t len = (uint32_t)job.input_len;
-        const uint32_t plen = (uint32_t)job.prefix_len;
-        const uint32_t cap = job.out_cap > kMaxPosB ? kMaxPosB : (uint32_t)job.out_cap;
-        const uint64_t limit = job.output_limit;
-        const uint32_t rb = (uint32_t)(reinterpret_cast<uintptr_t>(out) & 15u);   // ring bias
-        const uint32_t ring_a = lds_addr(ring), nxt_a = lds_addr(nxt);
-#define RIDX(x) (((x) + rb) & kMask)
-
-        // ring <- out[a, b)   (b - a <= RING; caller made out[a,b) visible)
-        auto ring_fill = [&](uint32_t a, uint32_t b) {
-            uint32_t nh = (16u - ((a + rb) & 15u)) & 15u; if (nh > b - a) nh = b - a;
-            if (lane < nh) ring[RIDX(a + lane)] = out[a + lane];
-            a += nh;
-            const uint32_t nchunks = (b - a) >> 4;
-            for (uint32_t c = lane; c < nchunks; c += kWave)
-                *reinterpret_cast<u32x4*>(&ring[RIDX(a + 16u * c)]) = *reinterpret_cast<const LZF_GLOBAL u32x4*>(out + a + 16u * c);
-            a += nchunks << 4;
-            if (lane < b - a) ring[RIDX(a + lane)] = out[a + lane];
-        };
-        // out[a, b) <- ring
-        auto ring_flush = [&](uint32_t a, uint32_t b) {
-            uint32_t nh = (16u - ((a + rb) & 15u)) & 15u; if (nh > b - a) nh = b - a;
-            if (lane < nh) out[a + lane] = ring[RIDX(a + lane)];
-            a += nh;
-            const uint32_t nchunks = (b - a) >> 4;
-            for (uint32_t c = lane; c < nchunks; c += kWave)
-                *reinterpret_cast<LZF_GLOBAL u32x4*>(out + a + 16u * c) = *reinterpret_cast<const u32x4*>(&ring[RIDX(a + 16u * c)]);
-            a += nchunks << 4;
-            if (lane < b - a) out[a + lane] = ring[RIDX(a + lane)];
-        };
-
-
-#ifdef LZF_DBG_PHASE_SEL   // analysis: cycles the copier spends in section LZF_DBG_PHASE_SEL of its batch loop (section i ends at PHASE(i);
-                           // 0 = between batches: loop control, chunk hand-over, waiting for the parser) -> results[].reserved
-        long long ph_t = clock64(), ph_acc = 0;
-#define PHASE(i) do { const long long tn__ = clock64(); if ((i) == LZF_DBG_PHASE_SEL) ph_acc += tn__ - ph_t; ph_t = tn__; } while (0)
-#else
-#define PHASE(i) do { } while (0)
-#endif
+        const DecodeJob jv = LZF_DECODE_JOB_VIEW(job);
+        const OutRing<RING> rg{ring, jv.out, jv.rb, lane, lds_addr(ring)};
+        const uint32_t nxt_a = lds_addr(nxt);
+        ph.start();
         if (threadIdx.x == 0) ctl_stop = 0;
         __syncthreads();
         if (role == 0u) {
@@ -111,7 +71,7 @@ __global__ __launch_bounds__(128) void lzf_decompress_paired_kernel(
                 uint8_t* const tokex = tokexs + bsel * kTokex;
                 uint32_t* const toks = reinterpret_cast<uint32_t*>(tokex);
                 const uint32_t cbuf_a = lds_addr(cbufs) + bsel * kCB, ex_a = lds_addr(tokexs) + bsel * kTokex;
-                const bool valid = cstart < len && *(volatile int*)&ctl_stop == 0;
+                const bool valid = cstart < jv.len && *(volatile int*)&ctl_stop == 0;
                 uint32_t cend_next = cstart;
                 if (valid) {
 #define LZF_TOK_T uint32_t
@@ -127,16 +87,16 @@ __global__ __launch_bounds__(128) void lzf_decompress_paired_kernel(
                         if (t < Tc) {
                             const uint32_t pos = toks[t] & 0xFFFFu;
                             const uint32_t tp = cstart + pos;
-                            const uint32_t w = rd4(tp);
+                            const uint32_t w = sb.rd4(tp);
                             uint32_t L = (w >> 4) & 15u, q = tp + 1u, Lc, Mc = 255u;
                             if (L == 15u) { L += (w >> 8) & 255u; ++q; }
                             Lc = L < 255u && !(((w >> 4) & 15u) == 15u && ((w >> 8) & 255u) == 255u) ? L : 255u;
                             if (Lc != 255u) {
                                 q += L;
-                                if (len - q < 2u) Mc = 254u;                 // :70 read_u16 fails: last literals
+                                if (jv.len - q < 2u) Mc = 254u;                 // :70 read_u16 fails: last literals
                                 else {
                                     uint32_t M = w & 15u;
-                                    if (M == 15u) { const uint32_t m1 = rdb(q + 2u); M = m1 < 239u ? 15u + m1 : 255u; }
+                                    if (M == 15u) { const uint32_t m1 = sb.rdb(q + 2u); M = m1 < 239u ? 15u + m1 : 255u; }
                                     Mc = M;
                                 }
                             }
@@ -155,7 +115,7 @@ __global__ __launch_bounds__(128) void lzf_decompress_paired_kernel(
             // ================================ COPIER ================================
             o = (uint32_t)job.out_existing_len;
             uint32_t safe = o;   // out[0, safe) is visible to this wave's global loads
-            if (o > 0) ring_fill(o > (uint32_t)RING ? o - RING : 0u, o);   // Vec content on entry = history
+            if (o > 0) rg.fill(o > (uint32_t)RING ? o - RING : 0u, o);   // Vec content on entry = history
             for (uint32_t kc = 0;; ++kc) {
                 __syncthreads();                 // chunk kc is parsed
                 const uint32_t bsel = kc & 1u;
@@ -166,25 +126,7 @@ __global__ __launch_bounds__(128) void lzf_decompress_paired_kernel(
                 const uint32_t cstart = *(volatile uint32_t*)&ctl_cstart[bsel];
                 const uint32_t Tc = *(volatile uint32_t*)&ctl_T[bsel];
                 const int cerr = *(volatile int*)&ctl_err[bsel];
-                // byte of the input at absolute position q >= cstart
-                // (asm LDS read on purpose: with two plain loads hipcc selects between the pointers and emits
-                //  one FLAT load, which waits on both memory counters at every use)
-                auto rdb = [&](uint32_t q) -> uint32_t {
-                    const uint32_t r = q - cstart;
-                    if (r < kCB) return lds_ld8(cbuf_a + r);
-                    return (uint32_t)in[q];
-                };
-                // One token at p (p < len): position of the next token; false on UnexpectedEnd.
-                // decompress.rs:61-71 without the copies.
-                // 4 input bytes at q (missing bytes past the end read as 0)
-                auto rd4 = [&](uint32_t q) -> uint32_t {
-                    const uint32_t r = q - cstart;
-                    if (!STAGE) { if (q + 4u <= len) return ld4(in + q); }
-                    else if (r + 4u <= kCB) { uint32_t v; asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(cbuf_a + r) : "memory"); return v; }
-                    uint32_t v = 0;
-                    for (uint32_t i = 0; i < 4u && q + i < len; ++i) v |= rdb(q + i) << (8u * i);
-                    return v;
-                };
+                const StagedBytes<true, kCB> sb{cbuf_a, cstart, jv.len, jv.in};
 
 #define LZF_TOKEN_AT(i) (toks[(i)] & 0xFFFFu)
 #define LZF_TOKEN_WORD(i) toks[(i)]
@@ -197,17 +139,12 @@ __global__ __launch_bounds__(128) void lzf_decompress_paired_kernel(
                 if (status != LZF_OK && lane == 0u) *(volatile int*)&ctl_stop = 1;
             }
         }
-#ifdef LZF_DBG_PHASE_SEL
-        ph_acc_out = ph_acc;
-#endif
-#undef PHASE
-#undef RIDX
     }
     if (role == 1u && lane == 0u) {
         results[jid].out_len = o;
         results[jid].status = status;
 #ifdef LZF_DBG_PHASE_SEL
-        results[jid].reserved = (uint32_t)(ph_acc_out >> 10);
+        ph.report(results[jid]);
 #elif defined(LZF_DBG_ROUNDS)
         results[jid].reserved = LZF_DBG_ROUNDS == 1 ? dbg_rounds : LZF_DBG_ROUNDS == 2 ? dbg_batches : dbg_lane_stat;
 #else

@@ -1,10 +1,13 @@
-// lz4_decompress_parse_phase.inc — the PARSE stage of one chunk, shared by lz4_decompress_batched.hip (one wave per
-// block) and lz4_decompress_paired.hip (the parser wave of a pair); textual include inside the kernel's chunk loop,
-// see lz4_decompress_batched.hip for the description.  Expects in scope: lane, in, len, cstart, the LDS arrays cbuf / nxt /
-// toks with their addresses cbuf_a / nxt_a / ex_a, the constants S, TOKCAP, STAGE, kChunk, kCB, kExStride, and the macros
-// LZF_TOK_T (token-list entry type: uint16_t or uint32_t) and LZF_THOP_RECORD (the matching record loop).
-// Leaves: Tc (tokens listed), cend (where the next chunk starts), cerr (UnexpectedEnd right after the listed tokens),
-// and the lambdas rdb / rd4 / token_next.
+// lz4_decompress_parse_phase.inc — the PARSE stage of one chunk, shared by lz4_decompress_batched.hip (one wave per block) and
+// lz4_decompress_paired.hip (the parser wave of a pair); textual include inside the kernel's chunk loop, see lz4_decompress_batched.hip.
+// The stage's interface (checked below): lane, jv (DecodeJob), cstart of the kernel's loop; the stage's own LDS — the arrays cbuf / nxt / toks
+// with their addresses cbuf_a / nxt_a / ex_a — and constants S, TOKCAP, STAGE, kChunk, kCB, kExStride; as parameters the macros LZF_TOK_T
+// (token-list entry type: uint16_t or uint32_t) and LZF_THOP_RECORD (the matching record loop).  Leaves: sb (StagedBytes over the chunk),
+// Tc (tokens listed), cend (where the next chunk starts), cerr (UnexpectedEnd right after the listed tokens).
+            LZF_STAGE_NEEDS(jv, DecodeJob); LZF_STAGE_NEEDS(lane, uint32_t); LZF_STAGE_NEEDS(cstart, uint32_t);
+            LZF_STAGE_NEEDS(cbuf[0], uint8_t); LZF_STAGE_NEEDS(nxt[0], uint8_t); LZF_STAGE_NEEDS(toks[0], LZF_TOK_T);
+            static_assert(kCB == (STAGE ? kChunk + 64u : 0u) && kExStride == (uint32_t)S + 4u && TOKCAP > 0, "the chunk's geometry");
+            const uint32_t len = jv.len; cgu8* __restrict__ in = jv.in;     // (scalars for the lambdas below: capturing the view changed the kernels' code, profiles/copy_stage_one_ring.txt)
             // =====================================================================
             // A0. stage in[cstart, cstart + kCB) in LDS
             // =====================================================================
@@ -62,31 +65,13 @@
                     *reinterpret_cast<uint32_t*>(&nxt[j]) = o4;
                 }
             }
-            // byte of the input at absolute position q >= cstart
-            // (asm LDS read on purpose: with two plain loads hipcc selects between the pointers and emits
-            //  one FLAT load, which waits on both memory counters at every use)
-            auto rdb = [&](uint32_t q) -> uint32_t {
-                const uint32_t r = q - cstart;
-                if (r < kCB) return lds_ld8(cbuf_a + r);
-                return (uint32_t)in[q];
-            };
-            // One token at p (p < len): position of the next token; false on UnexpectedEnd.
-            // decompress.rs:61-71 without the copies.
+            const StagedBytes<STAGE, kCB> sb{cbuf_a, cstart, len, in};     // the staged chunk, for this stage and for the copy stage
             uint32_t cutpos_w = 0;     // position of token #TOKCAP when a chunk has more tokens than the list holds
-            // 4 input bytes at q (missing bytes past the end read as 0)
-            auto rd4 = [&](uint32_t q) -> uint32_t {
-                const uint32_t r = q - cstart;
-                if (!STAGE) { if (q + 4u <= len) return ld4(in + q); }
-                else if (r + 4u <= kCB) { uint32_t v; asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(cbuf_a + r) : "memory"); return v; }
-                uint32_t v = 0;
-                for (uint32_t i = 0; i < 4u && q + i < len; ++i) v |= rdb(q + i) << (8u * i);
-                return v;
-            };
             // One token at p (p < len): position of the next token; false on UnexpectedEnd.
             // decompress.rs:61-71 without the copies.  One LDS read covers the token and the first
             // length-extension byte, which is all a hop needs in the common cases.
             auto token_next = [&](uint32_t p, uint32_t& next) -> bool {
-                const uint32_t w = rd4(p);
+                const uint32_t w = sb.rd4(p);
                 const uint32_t tok = w & 255u;
                 uint32_t q = p + 1u;
                 uint32_t L = tok >> 4;
@@ -96,7 +81,7 @@
                     L += b;
                     while (b == 255u) {
                         if (q >= len) return false;
-                        b = rdb(q); ++q;
+                        b = sb.rdb(q); ++q;
                         L += b; if (L > kMaxPosB) L = kMaxPosB;
                     }
                 }
@@ -107,7 +92,7 @@
                 if ((tok & 15u) == 15u) {
                     for (;;) {
                         if (q >= len) return false;
-                        const uint32_t b = rdb(q); ++q;
+                        const uint32_t b = sb.rdb(q); ++q;
                         if (b != 255u) break;
                     }
                 }

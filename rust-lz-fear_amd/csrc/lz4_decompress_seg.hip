@@ -715,7 +715,7 @@ __global__ __launch_bounds__(64) void lzf_seg_scan_kernel(seg_ctx c) {
         }
     }
     if (lane == 0u) {
-        const uint64_t cap = job.out_cap > kMaxPosB ? kMaxPosB : job.out_cap;
+        const uint64_t cap = LZF_DECODE_JOB_VIEW(job).cap;                       // (64 bits here: it is set against 64-bit sums)
         ctok *= 64ull;                                                           // batches -> records (padded)
         bool ok = cout <= cap && ctok < 0x7FFFFFFFull;
         uint64_t off = 0;
@@ -752,6 +752,7 @@ __global__ __launch_bounds__(64) void lzf_seg_records_kernel(seg_ctx c) {
     if (!sj.eligible || sj.failed) return;
     const uint32_t lane = threadIdx.x & 63u;
     const lzf_decompress_job job = c.jobs[j];
+    // (as DecodeJob of lzf_copy_helpers.h has them; the view itself moved three instructions here: profiles/copy_stage_one_ring.txt)
     cgu8* __restrict__ in = as_global(job.input);
     gu8* out = as_global(job.out);
     const uint32_t len = (uint32_t)job.input_len;
@@ -1409,6 +1410,7 @@ __global__ __launch_bounds__(128) void lzf_seg_resolve_pair_kernel(seg_ctx c) {
         static_assert(NT <= 32, "the ends of the tickets in flight live in the lanes of one register");
         uint32_t endv = rb;                              // lane t % 64: biased end (rounded down to a granule) of published ticket t
         uint32_t flushed_t = 0;                          // tickets whose bytes are in HBM
+        // (the split is lzf_ring_split(y0, y1, 0) of lzf_out_ring.h, the rule's one home, written out: calling it changed this kernel's code)
         auto flush_range = [&](uint32_t y0, uint32_t y1) {
             if (y1 <= y0) return;
             uint32_t nh = (16u - (y0 & 15u)) & 15u; if (nh > y1 - y0) nh = y1 - y0;

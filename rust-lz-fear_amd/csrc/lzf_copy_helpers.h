@@ -1,6 +1,10 @@
-// lzf_copy_helpers.h — constants and per-lane copy helpers shared by the batched decompress kernels.
+// lzf_copy_helpers.h — what the batched decompress kernels and their three textual stages (lz4_decompress_{parse,feed,batch}_phase.inc) share:
+// constants, the job view (DecodeJob), the reader over a staged window of the input (StagedBytes), the check with which a stage names what it
+// needs from the kernel that includes it (LZF_STAGE_NEEDS), and the per-lane copy helpers.  The output ring is lzf_out_ring.h.
 #pragma once
+#include <type_traits>
 #include "lzf_device.h"
+#include "lzf_out_ring.h"
 
 namespace lzf {
 namespace {
@@ -12,6 +16,54 @@ constexpr uint32_t kTotClamp = 1u << 25; // per-sequence output clamp inside the
 #ifndef LZF_DBG_SKIP
 #define LZF_DBG_SKIP 0      // analysis builds only: bit0 batches, bit1 serial matches, bit2 far, bit3 literals, bit4 flush, bit5 round 1
 #endif
+
+// The job as a decompress kernel sees it: global pointers, 32-bit positions, the output capacity clamped to them.
+struct DecodeJob {
+    cgu8 *in, *prefix;
+    gu8* out;
+    uint32_t len, plen, cap;    // cap: out_cap, clamped at kMaxPosB
+    uint64_t limit;
+    uint32_t rb;                // out & 15: the bias of the output ring (lzf_out_ring.h)
+};
+// LZF_DECODE_JOB_OUT_OF_CONTRACT(job): the kernel says LZF_CONTRACT — a length beyond its 31-bit positions, or more existing output than capacity.
+// LZF_DECODE_JOB_VIEW(job): the view of a job that passed (the decode starts at job.out_existing_len, which the kernel carries as `o`).
+// lz4_decoded_size.hip has a rule of its own: no output, so no out_cap test.  Two macros and not one function that fills the view and returns
+// false, on purpose: every function form tried changed the kernels' code far beyond their prologues (profiles/copy_stage_one_ring.txt).
+#define LZF_DECODE_JOB_OUT_OF_CONTRACT(job) \
+    ((job).input_len >= kMaxPosB || (job).out_existing_len >= kMaxPosB || (job).prefix_len >= kMaxPosB || (job).out_existing_len > (job).out_cap)
+#define LZF_DECODE_JOB_VIEW(job) \
+    DecodeJob{as_global((job).input), as_global((job).prefix), as_global((job).out), (uint32_t)(job).input_len, (uint32_t)(job).prefix_len, \
+              (job).out_cap > kMaxPosB ? kMaxPosB : (uint32_t)(job).out_cap, (job).output_limit, (uint32_t)(reinterpret_cast<uintptr_t>((job).out) & 15u)}
+
+// A window of the input staged in LDS: in[cstart, cstart + CB) sits at LDS address `lds` (zeros beyond the input); bytes behind the window are
+// read from `in`.  STAGE = false (direct variants, CB = 0): everything is read from `in`.
+template <bool STAGE_, uint32_t CB>
+struct StagedBytes {
+    static constexpr bool kStage = STAGE_;
+    static constexpr uint32_t kCB = CB;
+    uint32_t lds, cstart, len;
+    cgu8* in;
+    // byte of the input at absolute position q >= cstart  (asm LDS read on purpose: with two plain loads hipcc selects between the pointers
+    // and emits one FLAT load, which waits on both memory counters at every use)
+    __device__ __forceinline__ uint32_t rdb(uint32_t q) const {
+        const uint32_t r = q - cstart;
+        if (r < CB) return lds_ld8(lds + r);
+        return (uint32_t)in[q];
+    }
+    // 4 input bytes at q (missing bytes past the end read as 0)
+    __device__ __forceinline__ uint32_t rd4(uint32_t q) const {
+        const uint32_t r = q - cstart;
+        if (!STAGE_) { if (q + 4u <= len) return ld4(in + q); }
+        else if (r + 4u <= CB) { uint32_t v; asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(lds + r) : "memory"); return v; }
+        uint32_t v = 0;
+        for (uint32_t i = 0; i < 4u && q + i < len; ++i) v |= rdb(q + i) << (8u * i);
+        return v;
+    }
+};
+
+// The interface of a textual stage, checked where the stage opens: LZF_STAGE_NEEDS(x, T) — the including kernel has an `x` in
+// scope (an object, or a member of one such as rg.kRing) and it is a T.  A kernel that forgets one fails at the include.
+#define LZF_STAGE_NEEDS(x, T) static_assert(std::is_same<std::remove_cv_t<std::remove_reference_t<decltype(x)>>, T>::value, "this stage needs `" #x "` (" #T ") from the kernel that includes it")
 
 // Bytes 32..n-1 of a 33..64-byte run whose first 32 bytes are moved separately: last four 8-byte pieces (they may
 // overlap the first 32 bytes: same data).

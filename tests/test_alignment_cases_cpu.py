@@ -1,10 +1,17 @@
 """The shapes of the buffer-alignment sweep (tests/alignment_cases.py), checked without a GPU: every claimed residue matrix is
 complete, every expectation has the intended status, every structural claim holds — and a byte-wise model of ring_flush's
-(head, vector, tail) split shows that the tiny shapes reach each of its branches at every rb.  The model is not compared with the
-kernels; tests/test_gpu_alignment.py compares the kernels' bytes with the oracle's.  (The model itself, ring_flush_split, is in
-tests/alignment_cases.py beside the builders; ring_fill splits a range the same way.)"""
+(head, vector, tail) split shows that the tiny shapes reach each of its branches at every rb.  The model is held against the rule
+the kernels compile (lzf_ring_split of rust-lz-fear_amd/csrc/lzf_out_ring.h, through tests/emu/emu_ring_split.cpp and g++), not
+against the kernels; tests/test_gpu_alignment.py compares the kernels' bytes with the oracle's.  (The model itself,
+ring_flush_split, is in tests/alignment_cases.py beside the builders; ring_fill splits a range the same way.)"""
+import ctypes as C
+import os
+import subprocess
+
 import alignment_cases as ac
 import oracle_ffi as o
+
+HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 def _pairs(s, idx=None):
@@ -37,6 +44,31 @@ def test_ring_flush_model_is_a_partition():
                 assert nh + 16 * nv + nt == b - a and 0 <= nh < 16 and 0 <= nt < 16
                 assert nv == 0 or (a + nh + rb) % 16 == 0                # vector stores at 16-byte addresses only
                 assert clamped == (b - a < (-(a + rb)) % 16)
+
+
+def test_ring_flush_model_is_the_kernels_split_rule():
+    """ring_flush_split(a, b, rb) against lzf_ring_split, the one function OutRing::fill and OutRing::flush take their split from,
+    for every rb 0..15, a 0..31 and b - a 0..80: the clamped head, no vector store, one and several, and every tail 0..15."""
+    src = os.path.join(HERE, "emu", "emu_ring_split.cpp")
+    hdr = os.path.join(os.path.dirname(HERE), "rust-lz-fear_amd", "csrc", "lzf_out_ring.h")
+    so = os.path.join(HERE, "emu", "libemu_ring_split.so")
+    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", "-o", so, src])
+    L = C.CDLL(so)
+    L.lzf_emu_ring_split_sweep.restype = None
+    L.lzf_emu_ring_split_sweep.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
+    n_a, n_len = 32, 81
+    parts = (C.c_uint32 * (16 * n_a * n_len * 3))()
+    L.lzf_emu_ring_split_sweep(n_a, n_len, parts)
+    seen_tails, clamped_heads, vecs = set(), 0, set()
+    for rb in range(16):
+        for a in range(n_a):
+            for n in range(n_len):
+                k = ((rb * n_a + a) * n_len + n) * 3
+                nh, nv, nt, clamped = ac.ring_flush_split(a, a + n, rb)
+                assert (nh, nv, nt) == tuple(parts[k:k + 3]), (rb, a, n)
+                seen_tails.add(nt); vecs.add(nv); clamped_heads += clamped
+    assert seen_tails == set(range(16)) and {0, 1, 2} <= vecs and clamped_heads > 0
 
 
 def test_tiny_shape():
