@@ -178,6 +178,22 @@ __global__ __launch_bounds__(256) void lzf_seg_plan_kernel(seg_ctx c) {
 // A plain hop is ONE unaligned 4-byte LDS read from position - 1: [previous token's match-length extension byte, token,
 // first literal-length extension byte, ...].  Tokens a plain hop cannot express (0xFF length bytes, the last 24 bytes of
 // the input) go through the general routine.
+// -DLZF_DBG_PARSE_TIME (analysis): cycles of a parse wave by section, summed over the launch — 0 staging (loads issued and waited for,
+// LDS stores), 1 pass 0, 2 the fixed-point passes, 3 the rows written out; [4] chunks, [5] workgroups that had one.
+// lzf_debug_parse_timers() reads (and clears) the sums: tools/parse_staging.py.
+#ifdef LZF_DBG_PARSE_TIME
+__device__ unsigned long long lzf_dbg_parse_cycles[6];
+#define PT_START() long long pt_t = clock64(); unsigned long long pt[4] = {0, 0, 0, 0}; uint32_t pt_n = 0
+#define PT_MARK(i) do { const long long tn_ = clock64(); pt[i] += (unsigned long long)(tn_ - pt_t); pt_t = tn_; } while (0)
+#define PT_CHUNK() (++pt_n)
+#define PT_REPORT() do { if (lane == 0u && pt_n) { for (int i_ = 0; i_ < 4; ++i_) atomicAdd(&lzf_dbg_parse_cycles[i_], pt[i_]); \
+                                                     atomicAdd(&lzf_dbg_parse_cycles[4], (unsigned long long)pt_n); atomicAdd(&lzf_dbg_parse_cycles[5], 1ull); } } while (0)
+#else
+#define PT_START() do { } while (0)
+#define PT_MARK(i) do { } while (0)
+#define PT_CHUNK() do { } while (0)
+#define PT_REPORT() do { } while (0)
+#endif
 __global__ __launch_bounds__(64) void lzf_seg_parse_kernel(seg_ctx c) {
     // one array: rows A, rows B, the chunk's bytes.  A hop reads 4 bytes from position - 1: for the chunk's first byte that is the last
     // byte of row B (any value: a walk's first hop does not look at it), and no hop lands on the last two bytes (see `fe`).
@@ -198,30 +214,36 @@ __global__ __launch_bounds__(64) void lzf_seg_parse_kernel(seg_ctx c) {
 #define ROWA(w) rowsA[(w) * 64u + lane]
 #define ROWB(w) rowsB[(w) * 64u + lane]
 
+    PT_START();
     for (uint32_t h = blockIdx.x; h < sj.nch; h += gridDim.x) {
         const uint32_t cstart = h * kSegStride;
         __syncthreads();                         // (one wave: orders the LDS re-use between iterations)
-        // ---- stage in[cstart, cstart + kCB) (zeros beyond the input)
+        // ---- stage in[cstart, cstart + kCB) (zeros beyond the input): ONE round trip — a lane's kLd 16-byte loads are all issued before
+        //      the first is waited for (a fully unrolled register array; issued four at a time, a chunk cost four dependent HBM round trips
+        //      before its first hop).  No branch around a load: a lane whose 16 bytes end behind `avail` loads the last whole 16 bytes in
+        //      front of it instead — nothing at or beyond in + len is read — and stores zeros.
         {
             const uint32_t avail = len - cstart < kCB ? len - cstart : kCB;
             cgu8* g = in + cstart;
-#pragma unroll 1
-            for (uint32_t b4 = 0; b4 < kCB; b4 += 4u * 1024u) {
-                u32x4 v[4];
+            constexpr uint32_t kLd = kCB / 1024u;
+            u32x4 v[kLd];
+            if (avail >= 16u) {
 #pragma unroll
-                for (uint32_t k = 0; k < 4u; ++k) {
-                    const uint32_t i = b4 + k * 1024u + lane * 16u;
-                    v[k] = u32x4{0, 0, 0, 0};
-                    if (i + 16u <= avail) v[k] = ld16(g + i);
-                }
+                for (uint32_t k = 0; k < kLd; ++k) { const uint32_t i = k * 1024u + lane * 16u; v[k] = ld16(g + (i < avail - 16u ? i : avail - 16u)); }
+            } else {
 #pragma unroll
-                for (uint32_t k = 0; k < 4u; ++k) {
-                    const uint32_t i = b4 + k * 1024u + lane * 16u;
-                    if (i < kCB) *reinterpret_cast<u32x4*>(&cbuf[i]) = v[k];
-                }
+                for (uint32_t k = 0; k < kLd; ++k) v[k] = u32x4{0, 0, 0, 0};
+            }
+            if (avail == kCB) {
+#pragma unroll
+                for (uint32_t k = 0; k < kLd; ++k) *reinterpret_cast<u32x4*>(&cbuf[k * 1024u + lane * 16u]) = v[k];
+            } else {
+#pragma unroll
+                for (uint32_t k = 0; k < kLd; ++k) { const uint32_t i = k * 1024u + lane * 16u; *reinterpret_cast<u32x4*>(&cbuf[i]) = i + 16u <= avail ? v[k] : u32x4{0, 0, 0, 0}; }
             }
             { const uint32_t t0 = avail & ~15u; if (t0 < kCB && lane < (avail & 15u)) cbuf[t0 + lane] = g[t0 + lane]; }   // the ragged end of the input
         }
+        PT_MARK(0);
 #pragma unroll
         for (uint32_t i = 0; i < 8u; ++i) { ROWA(i) = 0u; ROWB(i) = 0u; }
         const uint32_t room = len - cstart;                                      // bytes from the chunk start to the end of the input
@@ -393,6 +415,7 @@ __global__ __launch_bounds__(64) void lzf_seg_parse_kernel(seg_ctx c) {
         const bool in_input = cstart + rb0 < len;
         bool mdummy = false;
         const uint32_t x0 = walk(rb0, in_input, mdummy, M0T{});
+        PT_MARK(1);
         uint32_t X = in_input ? x0 : 0u, walked = rb0, mpos = rb0;
         for (uint32_t pass = 0; pass < 80u; ++pass) {
             const uint32_t entry = wave_prev(wave_scan_max(X), 0u);
@@ -412,6 +435,7 @@ __global__ __launch_bounds__(64) void lzf_seg_parse_kernel(seg_ctx c) {
                 else { X = x1; mpos = end_r; }
             }
         }
+        PT_MARK(2);
         // ---- the rows and the exit
         {
             const uint32_t mb = mpos - rb0;                    // 0..256: row A is valid from this bit on
@@ -440,11 +464,18 @@ __global__ __launch_bounds__(64) void lzf_seg_parse_kernel(seg_ctx c) {
                 if (lane == 0u) __hip_atomic_fetch_add(&c.est[j], tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
+        PT_MARK(3);
+        PT_CHUNK();
     }
+    PT_REPORT();
 }
 
 #undef ROWA
 #undef ROWB
+#undef PT_START
+#undef PT_MARK
+#undef PT_CHUNK
+#undef PT_REPORT
 
 // =====================================================================================================================
 // seam: from which position on is a chunk's chain the true one
@@ -1662,3 +1693,13 @@ template __global__ void lzf_seg_resolve_pair_kernel<65536>(seg_ctx);
 template __global__ void lzf_seg_resolve_pair_kernel<131072>(seg_ctx);
 
 }  // namespace lzf
+
+#ifdef LZF_DBG_PARSE_TIME
+// Analysis only: the section sums of lzf_seg_parse_kernel since the last call with `reset` (out6 may be NULL).
+extern "C" int lzf_debug_parse_timers(unsigned long long* out6, int reset) {
+    if (out6 && hipMemcpyFromSymbol(out6, HIP_SYMBOL(lzf::lzf_dbg_parse_cycles), sizeof(unsigned long long) * 6u) != hipSuccess) return LZF_E_HIP;
+    const unsigned long long z[6] = {0, 0, 0, 0, 0, 0};
+    if (reset && hipMemcpyToSymbol(HIP_SYMBOL(lzf::lzf_dbg_parse_cycles), z, sizeof(z)) != hipSuccess) return LZF_E_HIP;
+    return LZF_OK;
+}
+#endif
