@@ -33,23 +33,33 @@ static inline uint32_t hash_for_u16(const uint8_t* p) {
     return (rd32le(p) * 2654435761U) >> (32 - 12 - 1);
 }
 
-/* mod.rs:63-76 */
-size_t lzfo_u32_replace(lzfo_u32_table* t, const uint8_t* input, size_t len, size_t pos, int* contract) {
+/* mod.rs:63-76; *raw receives the slot's value before the insert (trace only) */
+static inline size_t u32_replace(lzfo_u32_table* t, const uint8_t* input, size_t len, size_t pos, int* contract, uint64_t* raw) {
     uint64_t o = (uint64_t)pos + t->offset;                 /* :65 */
     if (o > 0xFFFFFFFFull) { *contract = 1; return 0; }     /* :67 try_into().expect() */
     uint32_t h = hash_for_u32(input + pos, len - pos);      /* :68 */
     uint64_t old = t->dict[h];
     t->dict[h] = (uint32_t)o;
+    *raw = old;
     return old > t->offset ? (size_t)(old - t->offset) : 0; /* :70 saturating_sub */
 }
 /* mod.rs:88-101 */
-size_t lzfo_u16_replace(lzfo_u16_table* t, const uint8_t* input, size_t len, size_t pos, int* contract) {
+static inline size_t u16_replace(lzfo_u16_table* t, const uint8_t* input, size_t len, size_t pos, int* contract, uint64_t* raw) {
     uint64_t o = (uint64_t)pos + t->offset;                 /* :90 */
     if (o > 0xFFFFull || len - pos < 4) { *contract = 1; return 0; } /* :92, read_u32 panic */
     uint32_t h = hash_for_u16(input + pos);                 /* :93 */
     uint64_t old = t->dict[h];
     t->dict[h] = (uint16_t)o;
+    *raw = old;
     return old > t->offset ? (size_t)(old - t->offset) : 0; /* :95 */
+}
+size_t lzfo_u32_replace(lzfo_u32_table* t, const uint8_t* input, size_t len, size_t pos, int* contract) {
+    uint64_t raw = 0;
+    return u32_replace(t, input, len, pos, contract, &raw);
+}
+size_t lzfo_u16_replace(lzfo_u16_table* t, const uint8_t* input, size_t len, size_t pos, int* contract) {
+    uint64_t raw = 0;
+    return u16_replace(t, input, len, pos, contract, &raw);
 }
 
 /* ------------------------------------------------------------------------------------------
@@ -96,19 +106,28 @@ static size_t count_matching_bytes(const uint8_t* a, size_t alen, const uint8_t*
 }
 
 /* ------------------------------------------------------------------------------------------
- * compress2 — src/raw/compress/mod.rs:165-238
+ * compress2 — src/raw/compress/mod.rs:165-238.  One loop for lzfo_compress2 (tr == NULL) and lzfo_compress2_trace: the trace
+ * only looks at what the loop computed, except for the byte comparison of a refused probe (trace mode only).
  * ---------------------------------------------------------------------------------------- */
-int lzfo_compress2(const uint8_t* input, size_t len, size_t cursor, int kind, void* table,
-                   uint8_t* out, size_t cap, size_t* out_len) {
+typedef struct { lzfo_trace_event* ev; size_t cap, n; } trace_t;
+static void trace_put(trace_t* tr, const lzfo_trace_event* e) {
+    if (tr->n < tr->cap) tr->ev[tr->n] = *e;                /* beyond the capacity: counted, not written */
+    tr->n++;
+}
+
+static int compress2_walk(const uint8_t* input, size_t len, size_t cursor, int kind, void* table,
+                          uint8_t* out, size_t cap, size_t* out_len, trace_t* tr) {
     sink_t s = {out, 0, cap};
     int contract = 0;
+    uint64_t raw = 0;
+    const uint64_t table_offset = kind == LZFO_TABLE_U16 ? ((lzfo_u16_table*)table)->offset : ((lzfo_u32_table*)table)->offset;
     size_t limit = kind == LZFO_TABLE_U16 ? 0xFFFFu : 0xFFFFFFFFull;   /* :75, :100 */
     *out_len = 0;
     if (len > limit) return LZFO_CONTRACT;                             /* :167 (cursor >= len: the loop at :171 never runs -> Ok, nothing written) */
 
 #define REPLACE(pos) (kind == LZFO_TABLE_U16                                          \
-        ? lzfo_u16_replace((lzfo_u16_table*)table, input, len, (pos), &contract)      \
-        : lzfo_u32_replace((lzfo_u32_table*)table, input, len, (pos), &contract))
+        ? u16_replace((lzfo_u16_table*)table, input, len, (pos), &contract, &raw)      \
+        : u32_replace((lzfo_u32_table*)table, input, len, (pos), &contract, &raw))
 
     const size_t init_cursor = cursor;                                 /* :169 */
     while (cursor < len) {                                             /* :171 (B4: empty -> nothing) */
@@ -139,10 +158,29 @@ int lzfo_compress2(const uint8_t* input, size_t len, size_t cursor, int kind, vo
                     while (bt < max_backtrack && bt < candidate &&
                            input[cursor - 1 - bt] == input[candidate - 1 - bt]) bt++;
                     extra_bytes = m - 4 + bt;                          /* :206,:214 */
+                    if (tr) {
+                        lzfo_trace_event e = {LZFO_EV_MATCH, 0, literal_start, cursor, raw, table_offset, candidate, m, bt, step};
+                        if (bt == max_backtrack) e.flags |= LZFO_STOP_LITERAL_START;
+                        if (bt == candidate) e.flags |= LZFO_STOP_CANDIDATE_ZERO;
+                        if (bt < max_backtrack && bt < candidate) e.flags |= LZFO_STOP_MISMATCH;
+                        trace_put(tr, &e);
+                    }
                     cursor += m;                                       /* :215 */
+                    if (tr && kind == LZFO_TABLE_U32 && len - (cursor - 2) < 8) {   /* B3: this insert hashes 0, not the bytes (U32 only, :41-51) */
+                        lzfo_trace_event e = {LZFO_EV_SHORT_INSERT, 0, literal_start, cursor - 2, 0, table_offset, 0, 0, 0, 0};
+                        trace_put(tr, &e);
+                    }
                     (void)REPLACE(cursor - 2);                         /* :218 (B1, B3) */
                     if (contract) return LZFO_CONTRACT;
                     break;                                             /* :220 */
+                }
+            } else if (tr && candidate < cursor) {                     /* a repeat the rules refuse: :200 (first position) or :201 (distance)? */
+                size_t m = count_matching_bytes(input + cursor, (len - 5) - cursor, input + candidate, len - candidate);
+                if (m >= 4) {
+                    lzfo_trace_event e = {LZFO_EV_REFUSED, 0, literal_start, cursor, raw, table_offset, candidate, m, 0, step};
+                    if (cursor == init_cursor) e.flags |= LZFO_REFUSED_FIRST_POSITION;
+                    if (cursor - candidate > 0xFFFF) e.flags |= LZFO_REFUSED_DISTANCE;
+                    trace_put(tr, &e);
                 }
             }
             cursor += step;                                            /* :225 */
@@ -167,6 +205,20 @@ full:
     *out_len = s.pos;
     return LZFO_OUTPUT_FULL;
 #undef REPLACE
+}
+
+int lzfo_compress2(const uint8_t* input, size_t len, size_t cursor, int kind, void* table,
+                   uint8_t* out, size_t cap, size_t* out_len) {
+    return compress2_walk(input, len, cursor, kind, table, out, cap, out_len, NULL);
+}
+
+int lzfo_compress2_trace(const uint8_t* input, size_t len, size_t cursor, int kind, void* table,
+                         uint8_t* out, size_t cap, size_t* out_len,
+                         lzfo_trace_event* events, size_t event_cap, size_t* event_count) {
+    trace_t tr = {events, event_cap, 0};
+    int rc = compress2_walk(input, len, cursor, kind, table, out, cap, out_len, &tr);
+    *event_count = tr.n;
+    return rc;
 }
 
 /* ------------------------------------------------------------------------------------------

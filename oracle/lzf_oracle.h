@@ -92,6 +92,28 @@ size_t lzfo_u16_replace(lzfo_u16_table* t, const uint8_t* input, size_t len, siz
 int lzfo_compress2(const uint8_t* input, size_t len, size_t cursor, int kind, void* table,
                    uint8_t* out, size_t cap, size_t* out_len);
 
+/* The same loop with a trace of its decisions, for tests that must prove an input reaches a rule (tests/compress_edge_cases.py).
+ * Status, bytes and table are those of lzfo_compress2.  Up to `event_cap` events are written to `events`; *event_count is the
+ * number there were (events beyond the capacity are counted, not written).
+ *   LZFO_EV_MATCH         one per emitted match: literal_start, pos (the cursor at the hit), raw_slot (the slot's value as read),
+ *                         table_offset (EncoderTable::offset at the call), candidate, matching_bytes, backtrack, step (the stride in
+ *                         force at that probe), flags = why the backtrack stopped (LZFO_STOP_*, several may hold)
+ *   LZFO_EV_REFUSED       a probe the rules of :200-201 refuse although its candidate lies before the cursor and has >= 4 equal bytes
+ *                         under the bounds of :195/:203 (compared in trace mode only): pos, candidate, matching_bytes, raw_slot, step,
+ *                         flags = LZFO_REFUSED_* (which rule; both may hold)
+ *   LZFO_EV_SHORT_INSERT  the unconditional `cursor - 2` insert of :218 at a position with fewer than 8 bytes left, U32 table only:
+ *                         its hash reads 8 bytes or takes 0 (B3, :41-51); the U16 hash reads 4 bytes and has no such case: pos */
+enum { LZFO_EV_MATCH = 1, LZFO_EV_REFUSED = 2, LZFO_EV_SHORT_INSERT = 3 };
+enum { LZFO_STOP_MISMATCH = 1, LZFO_STOP_LITERAL_START = 2, LZFO_STOP_CANDIDATE_ZERO = 4 };
+enum { LZFO_REFUSED_FIRST_POSITION = 1, LZFO_REFUSED_DISTANCE = 2 };
+typedef struct {
+    uint32_t type, flags;
+    uint64_t literal_start, pos, raw_slot, table_offset, candidate, matching_bytes, backtrack, step;
+} lzfo_trace_event;
+int lzfo_compress2_trace(const uint8_t* input, size_t len, size_t cursor, int kind, void* table,
+                         uint8_t* out, size_t cap, size_t* out_len,
+                         lzfo_trace_event* events, size_t event_cap, size_t* event_count);
+
 /* decompress_raw (decompress.rs:58-78).  `out` holds `*out_len` bytes of addressable history
  * on entry (the Vec's existing content) and `out_cap` bytes of room in total. */
 int lzfo_decompress_raw(const uint8_t* input, size_t len, const uint8_t* prefix, size_t prefix_len,

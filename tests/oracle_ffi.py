@@ -47,6 +47,18 @@ class Settings(C.Structure):
     ]
 
 
+EV_MATCH, EV_REFUSED, EV_SHORT_INSERT = 1, 2, 3
+STOP_MISMATCH, STOP_LITERAL_START, STOP_CANDIDATE_ZERO = 1, 2, 4
+REFUSED_FIRST_POSITION, REFUSED_DISTANCE = 1, 2
+
+
+class TraceEvent(C.Structure):
+    """lzfo_trace_event (oracle/lzf_oracle.h)"""
+    _fields_ = [("type", C.c_uint32), ("flags", C.c_uint32), ("literal_start", C.c_uint64), ("pos", C.c_uint64),
+                ("raw_slot", C.c_uint64), ("table_offset", C.c_uint64), ("candidate", C.c_uint64),
+                ("matching_bytes", C.c_uint64), ("backtrack", C.c_uint64), ("step", C.c_uint64)]
+
+
 _lib = None
 
 
@@ -68,6 +80,10 @@ def lib():
         L.lzfo_compress2.restype = C.c_int
         L.lzfo_compress2.argtypes = [C.c_char_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p,
                                      C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.lzfo_compress2_trace.restype = C.c_int
+        L.lzfo_compress2_trace.argtypes = [C.c_char_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p,
+                                           C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                                           C.POINTER(TraceEvent), C.c_size_t, C.POINTER(C.c_size_t)]
         L.lzfo_decompress_raw.restype = C.c_int
         L.lzfo_decompress_raw.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t,
                                           C.c_void_p, C.POINTER(C.c_size_t), C.c_size_t, C.c_size_t]
@@ -102,6 +118,32 @@ def compress2(data, cursor=0, kind=TABLE_U32, table=None, cap=None):
     n = C.c_size_t(0)
     rc = lib().lzfo_compress2(data, len(data), cursor, kind, C.addressof(table), out, cap, C.byref(n))
     return rc, out.raw[: n.value]
+
+
+def compress2_trace(data, cursor=0, kind=TABLE_U32, table=None, cap=None, max_events=None):
+    """compress2 with the oracle's trace of its decisions.  Returns (status, bytes, events): events is a numpy record array with the
+    fields of lzfo_trace_event (events_as_dicts for a list of dicts).  Every probe is one event at most, so the default capacity
+    holds them all; with a smaller max_events an overflow is an error here, nothing is dropped silently."""
+    import numpy as np
+    data = bytes(data)
+    if table is None:
+        table = new_table(kind)
+    if cap is None:
+        cap = len(data) + len(data) // 255 + 64
+    if max_events is None:
+        max_events = len(data) + 1
+    out = C.create_string_buffer(max(cap, 1))
+    n, ne = C.c_size_t(0), C.c_size_t(0)
+    ev = np.zeros(max_events, dtype=TraceEvent)
+    rc = lib().lzfo_compress2_trace(data, len(data), cursor, kind, C.addressof(table), out, cap, C.byref(n),
+                                    ev.ctypes.data_as(C.POINTER(TraceEvent)), max_events, C.byref(ne))
+    assert ne.value <= max_events, f"{ne.value} trace events, room for {max_events}"
+    return rc, out.raw[: n.value], ev[: ne.value].copy()
+
+
+def events_as_dicts(ev):
+    names = ev.dtype.names
+    return [dict(zip(names, t)) for t in ev.tolist()]
 
 
 def decompress_raw(data, prefix=b"", existing=b"", limit=None, cap=None):

@@ -158,6 +158,16 @@ def test_ring_skips_and_far_candidates():
               a + vectors.rng_bytes(2, 65535 - 40) + a + vectors.rng_bytes(3, 65536 - 40) + a + t,     # distances 65535 (legal) and 65536 (not)
               r[:300000] + t + r[300000:310000] + t,                  # a literal run of 300 000 (emitter: HBM), then matches at distance ~13 000
               t + r[:140000] + t[:200] + bytes(150000) + t[:300]]
+    # In the third input the skip schedule strides over the planted bytes inside 64 KiB of noise: the oracle's trace shows neither a
+    # match at 65535 nor a refusal at 65536 there.  The same with one zero run as the filler (one match, stride back to 1) reaches both:
+    far = [a + bytes(65535 - 40) + a + t, a + bytes(65536 - 40) + a + t]
+    ev = [o.compress2_trace(d)[2] for d in far]
+    assert any(e["type"] == o.EV_MATCH and e["pos"] == 65535 and e["pos"] - e["candidate"] == 65535 and e["matching_bytes"] == 40
+               for e in o.events_as_dicts(ev[0])), "no match at offset 65535 in the oracle"
+    assert any(e["type"] == o.EV_REFUSED and e["flags"] == o.REFUSED_DISTANCE and e["pos"] == 65536 and e["candidate"] == 0 and e["matching_bytes"] == 40
+               for e in o.events_as_dicts(ev[1])), "no distance refusal at 65536 in the oracle"
+    assert not any(e["type"] == o.EV_MATCH and e["pos"] - e["candidate"] > 65535 for e in o.events_as_dicts(ev[1]))
+    inputs += far
     expect(inputs, run(inputs))
     data = synth.silesia_mix(8 << 20, (8 << 20) + 400000).tobytes()
     inputs = [data, data[:300000], data]
