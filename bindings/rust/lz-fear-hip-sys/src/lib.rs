@@ -54,6 +54,17 @@ pub struct lzf_decompress_job {
 #[derive(Default, Clone, Copy)]
 pub struct lzf_job_result { pub out_len: u64, pub status: i32, pub reserved: u32 }
 
+/// One entry of a stream's frame index (lzf_frame_stream_decompressed_size_device), 48 bytes.
+#[repr(C)] #[derive(Default, Clone, Copy)]
+pub struct lzf_stream_frame {
+    pub in_off: u64, pub consumed: u64, pub out_off: u64, pub out_len: u64,
+    pub content_size: u64,                             // LZF_STREAM_NO_CONTENT_SIZE when absent or the header fails
+    pub status: i32, pub flags: u32,                   // LZF_SFRAME_*
+}
+pub const LZF_STREAM_NO_CONTENT_SIZE: u64 = u64::MAX;
+pub const LZF_SFRAME_COMPLETE: u32 = 1;                // ended at its EndMark with LZF_OK (content checksum not verified)
+pub const LZF_SFRAME_BEHIND_STOP: u32 = 2;             // the stream rule never reaches it: an earlier frame ended the stream
+
 #[repr(C)]
 #[derive(Default, Clone, Copy)]
 pub struct lzf_chain_state { pub length: u64, pub dead: u32, pub reserved: u32 }
@@ -135,6 +146,17 @@ extern "C" {
     pub fn lzf_frame_compress_stream_device(s: *const lzf_settings, frame_bytes: usize, n_streams: u32, d_in: *const *const u8,
                                             in_len: *const usize, d_dict: *const u8, dict_len: usize, d_out: *const *mut u8,
                                             out_cap: *const usize, d_out_len: *mut u64, d_status: *mut i32, hip_stream: *mut c_void) -> c_int;
+    // exact sizes and a frame index of streams, without decoding: what lzf_frame_decompress_stream_device would report per stream (the content
+    // checksum not verified) and, with room for lzf_frame_stream_count_device's number of entries per stream, every frame's lzf_stream_frame.
+    // d_index / index_cap: host arrays of device addresses / capacities in entries, both null for sizes only; d_n_frames, d_n_listed may be null
+    pub fn lzf_frame_stream_count_device(n_streams: u32, d_in: *const *const u8, in_len: *const usize, n_found: *mut usize,
+                                         hip_stream: *mut c_void) -> c_int;
+    pub fn lzf_frame_stream_decompressed_size_device(n_streams: u32, d_in: *const *const u8, in_len: *const usize, dict_len: usize,
+                                                     d_index: *const *mut lzf_stream_frame, index_cap: *const usize,
+                                                     d_out_len: *mut u64, d_consumed: *mut u64, d_status: *mut i32,
+                                                     d_n_frames: *mut u64, d_n_listed: *mut u64, hip_stream: *mut c_void) -> c_int;
+    // host only: frames [first, first + count) of an index (host copy) whose output meets the bytes [a, b) of the stream's output
+    pub fn lzf_stream_index_locate(index: *const lzf_stream_frame, n: usize, a: u64, b: u64, first: *mut usize, count: *mut usize) -> c_int;
     pub fn lzf_frame_release_scratch();
     pub fn lzf_frame_set_host_threads(n: u32);
     pub fn lzf_frame_set_memory_budget(bytes: usize);

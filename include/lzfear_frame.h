@@ -299,6 +299,61 @@ int lzf_frame_decompress_stream_device(uint32_t n_streams, const uint8_t* const*
                                        uint8_t* const* d_out, const size_t* out_cap,
                                        uint64_t* d_out_len, uint64_t* d_consumed, int32_t* d_status, uint64_t* d_n_frames,
                                        void* hip_stream);
+
+/* ---- exact sizes and a frame index of streams, found without decoding --------------------------------------------------
+ * lzf_frame_stream_decompressed_size_device is to lzf_frame_decompress_stream_device what lzf_frame_decompressed_size_device is
+ * to lzf_frame_decompress_device_many: per stream the status, out_len, consumed and n_frames that call reports for the same
+ * bytes, a dictionary of dict_len bytes and unlimited out_cap[s] — with the size query's ONE exception: the content checksum is
+ * not verified, so a frame that would end its stream with LZF_F_FRAME_CHECKSUM_FAIL counts as LZF_OK and the stream goes on
+ * behind it.  Never LZF_OUT_CAPACITY and never LZF_E_NO_MEMORY: no output slots, one pass whatever the memory budget is.
+ * On request it also lists the frames.  Entry k of stream s describes the k-th frame the structural walk finds (the failing
+ * last one included), with the frame size query's own results for in[in_off, len):
+ *   out_off   the sum of out_len over the frames before it: where the decode call puts its output.
+ *   flags     LZF_SFRAME_COMPLETE: the frame ended at its EndMark with LZF_OK.  The first frame without it ends the stream
+ *             (its own out_len and consumed still count, as in the rule above); every frame behind that one has
+ *             LZF_SFRAME_BEHIND_STOP and out_off = the stream's out_len: the walk found it, the decode call never reaches it.
+ * A run of whole frames is itself a stream: in[in_off of frame i, in_off + consumed of frame j) decodes, with
+ * lzf_frame_decompress_stream_device, to bytes [out_off of i, out_off + out_len of j) of the stream's output, and only the
+ * content checksums of the frames i..j are then verified.  lzf_stream_index_locate finds i and j for a byte range.
+ * Conventions of lzf_frame_decompress_stream_device: d_in, in_len are HOST arrays of n_streams entries holding DEVICE addresses;
+ * streams may alias each other.  d_index / index_cap: HOST arrays of n_streams entries, d_index[s] the DEVICE address (8-byte
+ * aligned) of room for index_cap[s] entries; at most index_cap[s] entries are written and nothing behind them; both NULL: sizes
+ * only.  d_out_len, d_consumed, d_status, d_n_frames (may be NULL; the decode call's count) and d_n_listed (may be NULL; the
+ * frames found, whatever the capacity — lzf_frame_stream_count_device's number) are DEVICE arrays of n_streams entries, written
+ * in stream order on `hip_stream`.  The host waits four times, as for the decode: twice for the stream scan, then for the
+ * per-frame scan summary and the block table; it then enqueues the frame size query's work over all frames, the fold of the
+ * frames' results into the streams' (the decode call's own kernel) and one index kernel (one wavefront per stream: a prefix of
+ * the lengths, the stop, the entries), waits for its own small upload and returns.  No host memory of the call is read after
+ * it returns.  An empty call is LZF_OK; an empty stream is LZF_OK, 0, 0, 0 with 0 frames listed.  Not graph-capturable. */
+#define LZF_STREAM_NO_CONTENT_SIZE 0xFFFFFFFFFFFFFFFFull
+#define LZF_SFRAME_COMPLETE    1u   /* ended at its EndMark with LZF_OK (content checksum not verified) */
+#define LZF_SFRAME_BEHIND_STOP 2u   /* the stream rule never reaches it: an earlier frame ended the stream */
+typedef struct lzf_stream_frame {   /* 48 bytes */
+    uint64_t in_off;        /* the frame is in[in_off, len) as its reader sees it */
+    uint64_t consumed;      /* lzf_frame_decompressed_size_device's consumed for it: the next frame starts at in_off + consumed */
+    uint64_t out_off;       /* where its output starts in the stream's output */
+    uint64_t out_len;       /* lzf_frame_decompressed_size_device's out_len for it, with dict_len */
+    uint64_t content_size;  /* the header's content size field; LZF_STREAM_NO_CONTENT_SIZE when absent or the header fails */
+    int32_t  status;        /* lzf_frame_decompressed_size_device's status for it */
+    uint32_t flags;         /* LZF_SFRAME_* */
+} lzf_stream_frame;
+/* Frames the walk finds per stream (the failing last one included): the entries the index call can list.  n_found: a HOST
+ * array.  Synchronous, one wait (the stream scan's first launch). */
+int lzf_frame_stream_count_device(uint32_t n_streams, const uint8_t* const* d_in, const size_t* in_len,
+                                  size_t* n_found, void* hip_stream);
+int lzf_frame_stream_decompressed_size_device(uint32_t n_streams, const uint8_t* const* d_in, const size_t* in_len,
+                                              size_t dict_len,
+                                              lzf_stream_frame* const* d_index, const size_t* index_cap,
+                                              uint64_t* d_out_len, uint64_t* d_consumed, int32_t* d_status,
+                                              uint64_t* d_n_frames, uint64_t* d_n_listed,
+                                              void* hip_stream);
+/* Host only, no device: frames [*first, *first + *count) of an index (a host copy of n entries) whose output meets the bytes
+ * [a, b) of the stream's output: out_off < b && out_off + out_len > a, among the entries without LZF_SFRAME_BEHIND_STOP.  A
+ * binary search.  a >= b, or no frame meets the range (n == 0, a range wholly behind the output): *count = 0.  The first and
+ * the last frame of the result have bytes in the range: frames of zero length are never at its edges.  Byte ranges stay out of
+ * the ABI: decode the frames, slice the output.  LZF_OK, or LZF_E_INVALID for a NULL argument. */
+int lzf_stream_index_locate(const lzf_stream_frame* index, size_t n, uint64_t a, uint64_t b, size_t* first, size_t* count);
+
 /* lzf_frame_compress_stream_device: input s becomes max(1, ceil(in_len[s] / frame_bytes)) frames, written back to back into
  * d_out[s]: the bytes are the concatenation of lzf_frame_compress_many's output for each piece of frame_bytes bytes (the last
  * one shorter) with the same settings and dictionary.  With s->has_content_size every frame's header carries its own piece's

@@ -24,6 +24,9 @@
 // length, lzf_stream_place_kernel gives every frame its place and the room left in its stream's output, and at the end
 // lzf_stream_fold_kernel folds the frames' results into the streams'.  Compress: the pieces of every input are frames of the
 // compress call above (compress_frames); lzf_stream_pack_kernel, in front of the assembly, puts each frame behind the one before.
+// lzf_frame_stream_decompressed_size_device: the stream scan, the size query over every frame it lists (size_frames, the body of
+// lzf_frame_decompressed_size_device), the decode's fold, and lzf_stream_index_kernel (lzf_stream_index.h's rules, one wavefront
+// per stream) for the frame index; lzf_stream_index_locate is that header's locate on the host.
 //
 // One copy of each rule.  The walk is lzf_frame_scan.h's (the host driver runs the same header).  The passes of the memory budget
 // are frame_jobs.h's split_passes, for all four *_many drivers.  The decode plan is plan_frames (the scan's summaries and table
@@ -37,6 +40,7 @@
 #include "../../include/lzfear_frame.h"
 #include "lzf_frame_scan.h"
 #include "lzf_stream_walk.h"
+#include "lzf_stream_index.h"
 #include "frame_jobs.h"
 #include "lzf_frame_layout.h"
 #include "lzf_chain_step.h"
@@ -448,7 +452,7 @@ struct Meta {
         if (zero_scratch && scratch) DEV_TRY(hipMemsetAsync(scr<uint8_t>(0), 0, scratch, st));
         return LZF_OK;
     }
-    int wait() { DEV_TRY(hipEventSynchronize(uploaded)); return LZF_OK; }
+    int wait() { if (uploaded) DEV_TRY(hipEventSynchronize(uploaded)); return LZF_OK; }     // (nothing uploaded: nothing to wait for)
 };
 
 // lzf_frame_set_memory_budget's value, or half of the free device memory
@@ -726,20 +730,29 @@ int decode_frames(const uint32_t n, const uint8_t* const* d_in, const size_t* in
     return meta.wait();
 }
 
-// The stream scan of n streams: the frames of every stream back on the host (two waits: the counts, then the starts).  Stream s
-// is frames [first[s], first[s + 1]); frame f is f_in[f][0, f_len[f]): everything from its start to the end of its stream, as the
-// reader of the frame sees it.
-int scan_streams(uint32_t n, const uint8_t* const* d_in, const size_t* in_len, hipStream_t st, std::vector<uint64_t>& first,
-                 std::vector<const uint8_t*>& f_in, std::vector<size_t>& f_len) {
-    PoolAlloc args(st);
-    if (!args.get(32 * (size_t)n)) return LZF_E_HIP;             // [ptrs | lens | counts | first]
-    std::vector<uint64_t> h(2 * (size_t)n), counts(n);
+// The stream scan's first launch: the frame count of every stream back on the host (one wait).  `args` keeps
+// [ptrs | lens | counts | first] on the device for the second launch.
+int count_streams(uint32_t n, const uint8_t* const* d_in, const size_t* in_len, hipStream_t st, PoolAlloc& args, std::vector<uint64_t>& counts) {
+    if (!args.get(32 * (size_t)n)) return LZF_E_HIP;
+    std::vector<uint64_t> h(2 * (size_t)n);
+    counts.resize(n);
     for (uint32_t s = 0; s < n; ++s) { h[s] = reinterpret_cast<uintptr_t>(d_in[s]); h[n + s] = in_len[s]; }
     DEV_TRY(hipMemcpyAsync(args.p, h.data(), 16 * (size_t)n, hipMemcpyHostToDevice, st));
     KERNEL(lzf_stream_scan_kernel, dim3((n + 63u) / 64u), dim3(64), 0, st, args.at<const uint8_t* const>(0), args.at<const uint64_t>(8 * (size_t)n), n,
            args.at<uint64_t>(16 * (size_t)n), (const uint64_t*)nullptr, (uint64_t*)nullptr);
     DEV_TRY(hipMemcpyAsync(counts.data(), args.at<uint64_t>(16 * (size_t)n), 8 * (size_t)n, hipMemcpyDeviceToHost, st));
     DEV_TRY(hipStreamSynchronize(st));
+    return LZF_OK;
+}
+
+// The stream scan of n streams: the frames of every stream back on the host (two waits: the counts, then the starts).  Stream s
+// is frames [first[s], first[s + 1]); frame f is f_in[f][0, f_len[f]): everything from its start to the end of its stream, as the
+// reader of the frame sees it.
+int scan_streams(uint32_t n, const uint8_t* const* d_in, const size_t* in_len, hipStream_t st, std::vector<uint64_t>& first,
+                 std::vector<const uint8_t*>& f_in, std::vector<size_t>& f_len) {
+    PoolAlloc args(st);
+    std::vector<uint64_t> counts;
+    if (const int rc = count_streams(n, d_in, in_len, st, args, counts)) return rc;
     first.assign((size_t)n + 1, 0);
     for (uint32_t s = 0; s < n; ++s) first[s + 1] = first[s] + counts[s];
     const uint64_t total = first[n];
@@ -768,6 +781,86 @@ __global__ __launch_bounds__(256) void lzf_stream_empty_kernel(uint32_t n, int32
     if (s >= n) return;
     d_status[s] = LZF_OK; d_out_len[s] = 0; d_consumed[s] = 0;
     if (d_n_frames) d_n_frames[s] = 0;
+}
+
+// The frame index of a stream (lzf_frame_stream_decompressed_size_device), one wavefront per stream, 64 frames per round: stream
+// s is frames [first[s], first[s + 1]) of the call, frame f starts at in[s] + in_off[f], and f_status / f_len / f_consumed hold
+// what the size query found for it.  The exclusive prefix of the lengths, behind the stream's running length, is every frame's
+// out_off; the first frame that ends the stream (lzf_stream_index.h's ends_stream, the fold's predicate) still gets its place
+// and adds its length, every frame behind it gets the stream's length and LZF_SFRAME_BEHIND_STOP.  The running length and the
+// stop carry from round to round.  Lane i writes entry i of the round, 48 bytes, if the caller's room holds it.
+__global__ __launch_bounds__(64) void lzf_stream_index_kernel(const uint8_t* const* __restrict__ in, const uint64_t* __restrict__ first,
+                                                              const uint64_t* __restrict__ in_off, const uint32_t* __restrict__ f_flags,
+                                                              const int32_t* __restrict__ f_status, const uint64_t* __restrict__ f_len,
+                                                              const uint64_t* __restrict__ f_consumed, const uint64_t* __restrict__ f_full,
+                                                              lzf_stream_frame* const* __restrict__ index, const uint64_t* __restrict__ cap,
+                                                              uint64_t* __restrict__ d_n_listed) {
+    const uint32_t s = blockIdx.x, lane = threadIdx.x;
+    const uint64_t a = first[s], b = first[s + 1];
+    lzf_stream_frame* const out = index ? index[s] : nullptr;
+    const uint64_t room = out ? cap[s] : 0ull;
+    const uint8_t* const src = in[s];
+    uint64_t run = 0;
+    bool stopped = false;
+    for (uint64_t base = a; base < b; base += 64u) {
+        const uint64_t f = base + lane;
+        const bool act = f < b;
+        const uint64_t n = act ? f_len[f] : 0ull, c = act ? f_consumed[f] : 0ull, full = act ? f_full[f] : 0ull;
+        const int code = act ? f_status[f] : LZF_OK;
+        const uint64_t incl = wave_incl_scan(n, lane);
+        const uint64_t stops = __ballot(act && lzf_sindex::ends_stream(code, c, full));
+        const uint32_t stop_at = stops ? (uint32_t)__builtin_ctzll(stops) : 64u;
+        // the stream's length once a frame of this round ends it: everything up to and including that frame
+        const uint64_t total = stopped ? run : run + __shfl(incl, (int)(stop_at & 63u), 64);
+        if (act && f - a < room) {
+            const bool behind = stopped || lane > stop_at;
+            const uint32_t fl = f_flags[f];
+            out[f - a] = lzf_sindex::fill_entry(src + in_off[f], (fl & kLive) != 0, fl, in_off[f], code, n, c, full,
+                                                behind ? total : run + (incl - n), behind);
+        }
+        if (!stopped) {
+            if (stops) { run = total; stopped = true; }
+            else run += __shfl(incl, 63, 64);
+        }
+    }
+    if (lane == 0 && d_n_listed) d_n_listed[s] = b - a;
+}
+
+// The size query of n frames (lzf_frame_decompressed_size_device's body, and the per-frame half of the stream size query): the
+// decode call's scan (two waits), its plan with sizes_only (plan_frames, plan_pass: jobs' lengths and descriptors, no addresses),
+// block checksums (they decide where delivery stops), lzf_decompressed_size_batch for the decode (linked frames in lock-step,
+// lzf_chain_size_step_kernel between the steps), lzf_frame_size_deliver_kernel for the delivery.  No output slots, hence one pass
+// whatever the memory budget is.  `more(sc)` puts what the caller's own kernels behind this need into the call's image before
+// its one upload; the caller ends with meta.wait().  Where every header failed and `more` added nothing, nothing is uploaded:
+// the scan kernel wrote the results.
+template <class More>
+int size_frames(uint32_t n, const uint8_t* const* d_in, const size_t* in_len, size_t dict_len, uint64_t* d_out_len, uint64_t* d_consumed,
+                int32_t* d_status, hipStream_t st, Scan& sc, Meta& meta, More&& more) {
+    // ---- scan: summaries (wait 1), block table (wait 2)
+    RC_TRY(scan_summaries(n, d_in, in_len, st, sc, d_status, d_out_len, d_consumed));
+    RC_TRY(scan_table(n, st, sc));
+    // ---- the decode's plan with sizes_only; the content checksum needs the content: not verified
+    Pass P; P.f0 = 0; P.f1 = n;
+    plan_frames(P, d_in, sc);
+    if (!P.jf.empty()) RC_TRY(plan_pass(P, sc, DecodeCall{true, nullptr, nullptr, dict_len, nullptr, nullptr, nullptr}, meta));
+    more(sc);
+    if (meta.image.empty() && !meta.scratch) return LZF_OK;
+    RC_TRY(meta.upload(true));
+    if (P.jf.empty()) return LZF_OK;
+    lzf_decompress_job* const d_jobs = meta.img<lzf_decompress_job>(P.i_jobs);
+    lzf_job_result* const d_res = meta.scr<lzf_job_result>(P.s_res);
+    uint32_t* const d_sums = meta.scr<uint32_t>(P.s_sums);
+    const lzf_frame_jobs::Plan& pl = P.plan;
+    if (P.n_sums) RC_TRY(lzf_xxh32_batch(meta.img<const uint8_t* const>(P.i_sptr), meta.img<const uint64_t>(P.i_slen), d_sums, P.n_sums, st));
+    for (size_t k = 0; k < pl.n_steps; ++k) {
+        if (pl.n_chain) KERNEL(lzf_chain_size_step_kernel, dim3(pl.n_chain), dim3(256), 0, st, meta.img<const lzf_chain_step>(P.i_steps) + k * pl.n_chain,
+                               meta.scr<lzf_chain_state>(P.s_state), pl.n_chain, d_jobs, (const lzf_job_result*)d_res);
+        const size_t a = pl.step_off[k], c = pl.step_off[k + 1] - a;
+        if (c) RC_TRY(lzf_decompressed_size_batch(d_jobs + a, d_res + a, (uint32_t)c, lzf_frame_jobs::step_max_input(pl, k), st));
+    }
+    KERNEL(lzf_frame_size_deliver_kernel, dim3(P.n_frames), dim3(64), 0, st, meta.img<const DFrameDesc>(P.i_frames), meta.img<const DBlkDesc>(P.i_blks),
+           (const lzf_decompress_job*)d_jobs, (const lzf_job_result*)d_res, (const uint32_t*)d_sums, d_status, d_out_len, d_consumed);
+    return LZF_OK;
 }
 
 }  // namespace
@@ -847,44 +940,97 @@ int lzf_frame_decompress_stream_device(uint32_t n_streams, const uint8_t* const*
                          per.at<uint64_t>(o_len), per.at<uint64_t>(o_cons), per.at<int32_t>(0), st, &sx);
 }
 
-// The decode call's scan, jobs and stop rules with lengths in the place of bytes: block checksums (they decide where delivery
-// stops), lzf_decompressed_size_batch for the decode (linked streams in lock-step, lzf_chain_size_step_kernel between the
-// steps), lzf_frame_size_deliver_kernel for the delivery.  No output slots, hence one pass whatever the memory budget is.
+// The size query: size_frames over the caller's frames (the decode call's scan, jobs and stop rules with lengths in the place
+// of bytes).
 int lzf_frame_decompressed_size_device(uint32_t n_frames, const uint8_t* const* d_in, const size_t* in_len, size_t dict_len,
                                        uint64_t* d_out_len, uint64_t* d_consumed, int32_t* d_status, void* hip_stream) {
     if (n_frames && (!d_in || !in_len || !d_out_len || !d_status)) return LZF_E_INVALID;
     if (n_frames == 0) return LZF_OK;
     if (usable_device() != LZF_OK) return LZF_E_NO_DEVICE;
-    const uint32_t n = n_frames;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     PoolAlloc own_consumed(st);                      // the kernels write `consumed` of every frame; a caller who passes NULL does not get it
-    if (!d_consumed) { if (!own_consumed.get(8 * (size_t)n)) return LZF_E_HIP; d_consumed = own_consumed.at<uint64_t>(0); }
-    // ---- scan: summaries (wait 1), block table (wait 2)
+    if (!d_consumed) { if (!own_consumed.get(8 * (size_t)n_frames)) return LZF_E_HIP; d_consumed = own_consumed.at<uint64_t>(0); }
     Scan sc(st);
-    RC_TRY(scan_summaries(n, d_in, in_len, st, sc, d_status, d_out_len, d_consumed));
-    RC_TRY(scan_table(n, st, sc));
-    // ---- the decode's plan with sizes_only: its jobs' lengths and its descriptors, no addresses; the content checksum needs the
-    //      content: not verified
-    Pass P; P.f0 = 0; P.f1 = n;
-    plan_frames(P, d_in, sc);
-    if (P.jf.empty()) return LZF_OK;                 // every header failed: the scan kernel wrote the results
     Meta meta(st);
-    RC_TRY(plan_pass(P, sc, DecodeCall{true, nullptr, nullptr, dict_len, nullptr, nullptr, nullptr}, meta));
-    RC_TRY(meta.upload(true));
-    lzf_decompress_job* const d_jobs = meta.img<lzf_decompress_job>(P.i_jobs);
-    lzf_job_result* const d_res = meta.scr<lzf_job_result>(P.s_res);
-    uint32_t* const d_sums = meta.scr<uint32_t>(P.s_sums);
-    const lzf_frame_jobs::Plan& pl = P.plan;
-    if (P.n_sums) RC_TRY(lzf_xxh32_batch(meta.img<const uint8_t* const>(P.i_sptr), meta.img<const uint64_t>(P.i_slen), d_sums, P.n_sums, st));
-    for (size_t k = 0; k < pl.n_steps; ++k) {
-        if (pl.n_chain) KERNEL(lzf_chain_size_step_kernel, dim3(pl.n_chain), dim3(256), 0, st, meta.img<const lzf_chain_step>(P.i_steps) + k * pl.n_chain,
-                               meta.scr<lzf_chain_state>(P.s_state), pl.n_chain, d_jobs, (const lzf_job_result*)d_res);
-        const size_t a = pl.step_off[k], c = pl.step_off[k + 1] - a;
-        if (c) RC_TRY(lzf_decompressed_size_batch(d_jobs + a, d_res + a, (uint32_t)c, lzf_frame_jobs::step_max_input(pl, k), st));
-    }
-    KERNEL(lzf_frame_size_deliver_kernel, dim3(P.n_frames), dim3(64), 0, st, meta.img<const DFrameDesc>(P.i_frames), meta.img<const DBlkDesc>(P.i_blks),
-           (const lzf_decompress_job*)d_jobs, (const lzf_job_result*)d_res, (const uint32_t*)d_sums, d_status, d_out_len, d_consumed);
+    RC_TRY(size_frames(n_frames, d_in, in_len, dict_len, d_out_len, d_consumed, d_status, st, sc, meta, [](const Scan&) {}));
     return meta.wait();                              // the image has left host memory; the kernels run on
+}
+
+int lzf_frame_stream_count_device(uint32_t n_streams, const uint8_t* const* d_in, const size_t* in_len, size_t* n_found, void* hip_stream) {
+    if (n_streams && (!d_in || !in_len || !n_found)) return LZF_E_INVALID;
+    if (usable_device() != LZF_OK) return LZF_E_NO_DEVICE;
+    if (n_streams == 0) return LZF_OK;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    PoolAlloc args(st);
+    std::vector<uint64_t> counts;
+    RC_TRY(count_streams(n_streams, d_in, in_len, st, args, counts));
+    for (uint32_t s = 0; s < n_streams; ++s) n_found[s] = (size_t)counts[s];
+    return LZF_OK;
+}
+
+// The stream scan lists the frames (two waits); size_frames finds every frame's results, the frames behind a stop included (two
+// more waits); lzf_stream_fold_kernel, the decode call's, folds them into the streams' results, and lzf_stream_index_kernel
+// writes the entries.  What the two kernels read travels in size_frames' image: one upload.
+int lzf_frame_stream_decompressed_size_device(uint32_t n_streams, const uint8_t* const* d_in, const size_t* in_len, size_t dict_len,
+                                              lzf_stream_frame* const* d_index, const size_t* index_cap,
+                                              uint64_t* d_out_len, uint64_t* d_consumed, int32_t* d_status,
+                                              uint64_t* d_n_frames, uint64_t* d_n_listed, void* hip_stream) {
+    if (n_streams && (!d_in || !in_len || !d_out_len || !d_consumed || !d_status)) return LZF_E_INVALID;
+    if ((d_index == nullptr) != (index_cap == nullptr)) return LZF_E_INVALID;
+    if (usable_device() != LZF_OK) return LZF_E_NO_DEVICE;
+    if (n_streams == 0) return LZF_OK;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    std::vector<uint64_t> first;
+    std::vector<const uint8_t*> f_in; std::vector<size_t> f_len;
+    RC_TRY(scan_streams(n_streams, d_in, in_len, st, first, f_in, f_len));
+    const size_t n = f_in.size();
+    if (n == 0) {
+        KERNEL(lzf_stream_empty_kernel, dim3((n_streams + 255u) / 256u), dim3(256), 0, st, n_streams, d_status, d_out_len, d_consumed, d_n_frames);
+        if (d_n_listed) DEV_TRY(hipMemsetAsync(d_n_listed, 0, 8 * (size_t)n_streams, st));
+        return LZF_OK;
+    }
+    const size_t o_len = up256(4 * n), o_cons = o_len + up256(8 * n);
+    PoolAlloc per(st);                               // the frames' own status, length and consumed: scratch
+    if (!per.get(o_cons + 8 * n)) return LZF_E_HIP;
+    int32_t* const f_status = per.at<int32_t>(0);
+    uint64_t* const f_out_len = per.at<uint64_t>(o_len);
+    uint64_t* const f_consumed = per.at<uint64_t>(o_cons);
+    Scan sc(st);
+    Meta meta(st);
+    size_t i_in = 0, i_first = 0, i_off = 0, i_flags = 0, i_full = 0, i_index = 0, i_cap = 0;
+    const auto more = [&](const Scan& got) {            // what the fold and the index kernel read
+        std::vector<uint64_t> full(n), off(n);
+        std::vector<uint32_t> flags(n);
+        for (uint32_t s = 0; s < n_streams; ++s)
+            for (uint64_t f = first[s]; f < first[s + 1]; ++f) off[(size_t)f] = (uint64_t)(f_in[(size_t)f] - d_in[s]);
+        for (uint32_t f = 0; f < n; ++f) {              // (full: decode_frames' rule for the fold)
+            full[f] = got.live(f) && got.sum[f].status == LZF_OK ? got.sum[f].consumed : ~0ull;
+            flags[f] = got.sum[f].flags;
+        }
+        i_in = meta.add(d_in, sizeof(void*) * (size_t)n_streams); i_first = meta.add(first);
+        i_off = meta.add(off); i_flags = meta.add(flags); i_full = meta.add(full);
+        if (d_index) {
+            const std::vector<uint64_t> cap(index_cap, index_cap + n_streams);
+            i_index = meta.add(d_index, sizeof(void*) * (size_t)n_streams); i_cap = meta.add(cap);
+        }
+    };
+    RC_TRY(size_frames((uint32_t)n, f_in.data(), f_len.data(), dict_len, f_out_len, f_consumed, f_status, st, sc, meta, more));
+    KERNEL(lzf_stream_fold_kernel, dim3(n_streams), dim3(64), 0, st, meta.img<const uint64_t>(i_first), (const int32_t*)f_status,
+           (const uint64_t*)f_out_len, (const uint64_t*)f_consumed, meta.img<const uint64_t>(i_full), d_status, d_out_len, d_consumed, d_n_frames);
+    KERNEL(lzf_stream_index_kernel, dim3(n_streams), dim3(64), 0, st, meta.img<const uint8_t* const>(i_in), meta.img<const uint64_t>(i_first),
+           meta.img<const uint64_t>(i_off), meta.img<const uint32_t>(i_flags), (const int32_t*)f_status, (const uint64_t*)f_out_len,
+           (const uint64_t*)f_consumed, meta.img<const uint64_t>(i_full),
+           d_index ? meta.img<lzf_stream_frame* const>(i_index) : (lzf_stream_frame* const*)nullptr,
+           d_index ? meta.img<const uint64_t>(i_cap) : (const uint64_t*)nullptr, d_n_listed);
+    return meta.wait();                              // the image has left host memory; the kernels run on
+}
+
+int lzf_stream_index_locate(const lzf_stream_frame* index, size_t n, uint64_t a, uint64_t b, size_t* first, size_t* count) {
+    if (!first || !count || (n && !index)) return LZF_E_INVALID;
+    uint64_t lo = 0, cnt = 0;
+    lzf_sindex::locate(index, n, a, b, &lo, &cnt);
+    *first = (size_t)lo; *count = (size_t)cnt;
+    return LZF_OK;
 }
 
 }  // extern "C"

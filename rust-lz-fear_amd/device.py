@@ -13,7 +13,9 @@ CJOB = np.dtype([("input", "<u8"), ("input_len", "<u8"), ("cursor", "<u8"), ("ou
 DJOB = np.dtype([("input", "<u8"), ("input_len", "<u8"), ("prefix", "<u8"), ("prefix_len", "<u8"),
                  ("out", "<u8"), ("out_existing_len", "<u8"), ("out_cap", "<u8"), ("output_limit", "<u8")])
 RES = np.dtype([("out_len", "<u8"), ("status", "<i4"), ("reserved", "<u4")])
-assert CJOB.itemsize == 56 and DJOB.itemsize == 64 and RES.itemsize == 16
+SFRAME = np.dtype([("in_off", "<u8"), ("consumed", "<u8"), ("out_off", "<u8"), ("out_len", "<u8"), ("content_size", "<u8"),
+                   ("status", "<i4"), ("flags", "<u4")])          # lzf_stream_frame
+assert CJOB.itemsize == 56 and DJOB.itemsize == 64 and RES.itemsize == 16 and SFRAME.itemsize == 48
 
 
 def to_device(arr, device):
@@ -224,6 +226,60 @@ def stream_decompress(streams, outs, dictionary=None, stream=None):
     ffi.check(ffi.lib().lzf_frame_decompress_stream_device(n, ptrs, lens, dptr, dlen, optr, caps, out_len.data_ptr(), consumed.data_ptr(),
                                                            status.data_ptr(), n_frames.data_ptr(), s.cuda_stream))
     return status, out_len, consumed, n_frames
+
+
+def stream_count(streams, stream=None):
+    """lzf_frame_stream_count_device: per stream the frames the walk finds (the failing last one included).  Synchronous."""
+    n, ptrs, lens = _frame_args(streams)
+    if n == 0:
+        return []
+    found = (C.c_size_t * n)()
+    ffi.check(ffi.lib().lzf_frame_stream_count_device(n, ptrs, lens, found, _stream_ptr(stream)))
+    return list(found)
+
+
+def stream_decompressed_size(streams, dictionary_len=0, index=None, stream=None):
+    """lzf_frame_stream_decompressed_size_device: per stream what stream_decompress would report with unlimited outputs and a
+    dictionary of `dictionary_len` bytes, found without decoding, and, with `index` (one uint8 CUDA tensor per stream, room for
+    numel() // 48 entries, 8-byte aligned), the frames of every stream.  Returns (status int32, out_len int64, consumed int64,
+    n_frames int64, n_listed int64) as CUDA tensors, written in order on `stream`.  The content checksum is not verified."""
+    n, ptrs, lens = _frame_args(streams)
+    dev = streams[0].device if n else torch.device("cuda", torch.cuda.current_device())
+    status = torch.empty(n, dtype=torch.int32, device=dev)         # (empty: the call writes every entry)
+    out_len, consumed, n_frames, n_listed = (torch.empty(n, dtype=torch.int64, device=dev) for _ in range(4))
+    if n == 0:
+        return status, out_len, consumed, n_frames, n_listed
+    iptr = icap = None
+    if index is not None:
+        assert len(index) == n
+        for t in index:
+            assert t.dtype == torch.uint8 and t.is_cuda and t.dim() == 1 and t.is_contiguous() and t.data_ptr() % 8 == 0, \
+                "index: 1-D contiguous uint8 CUDA tensors at 8-byte aligned addresses"
+        iptr = (C.c_void_p * n)(*[t.data_ptr() for t in index])
+        icap = (C.c_size_t * n)(*[t.numel() // SFRAME.itemsize for t in index])
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    for t in (status, out_len, consumed, n_frames, n_listed):
+        t.record_stream(s)
+    ffi.check(ffi.lib().lzf_frame_stream_decompressed_size_device(n, ptrs, lens, int(dictionary_len), iptr, icap, out_len.data_ptr(),
+                                                                  consumed.data_ptr(), status.data_ptr(), n_frames.data_ptr(),
+                                                                  n_listed.data_ptr(), s.cuda_stream))
+    return status, out_len, consumed, n_frames, n_listed
+
+
+def stream_index(streams, dictionary_len=0, stream=None):
+    """The frame index of every stream: counts the frames (lzf_frame_stream_count_device), allocates one entry tensor per stream and
+    runs stream_decompressed_size.  Returns (status, out_len, consumed, n_frames, n_listed, entries): CUDA tensors as above and
+    a list of uint8 CUDA tensors of 48 bytes per frame found (view them as SFRAME on the host)."""
+    streams = list(streams)
+    if not streams:
+        return stream_decompressed_size([], dictionary_len=dictionary_len, stream=stream) + ([],)
+    dev = streams[0].device
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    found = stream_count(streams, stream=s)
+    entries = [torch.empty(k * SFRAME.itemsize, dtype=torch.uint8, device=dev) for k in found]
+    for e in entries:
+        e.record_stream(s)
+    return stream_decompressed_size(streams, dictionary_len=dictionary_len, index=entries, stream=s) + (entries,)
 
 
 def stream_compress(settings, frame_bytes, tensors, outs, dictionary=None, stream=None):

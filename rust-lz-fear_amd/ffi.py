@@ -82,7 +82,19 @@ FRAME_EXPORTS = [
     "lzf_frame_set_pinned_limit", "lzf_frame_decompress_bound_device", "lzf_frame_decompress_device_many",
     "lzf_frame_compress_device_many", "lzf_frame_decompressed_size_device",
     "lzf_frame_stream_bound_device", "lzf_frame_decompress_stream_device", "lzf_frame_compress_stream_bound", "lzf_frame_compress_stream_device",
+    "lzf_frame_stream_count_device", "lzf_frame_stream_decompressed_size_device", "lzf_stream_index_locate",
 ]
+
+
+class StreamFrame(C.Structure):
+    """lzf_stream_frame: one entry of a stream's frame index (lzf_frame_stream_decompressed_size_device)"""
+    _fields_ = [("in_off", C.c_uint64), ("consumed", C.c_uint64), ("out_off", C.c_uint64), ("out_len", C.c_uint64),
+                ("content_size", C.c_uint64), ("status", C.c_int32), ("flags", C.c_uint32)]
+
+
+assert C.sizeof(StreamFrame) == 48
+STREAM_NO_CONTENT_SIZE = (1 << 64) - 1
+SFRAME_COMPLETE, SFRAME_BEHIND_STOP = 1, 2
 
 
 class FrameStats(C.Structure):
@@ -190,6 +202,11 @@ def lib():
         L.lzf_frame_compress_stream_device.argtypes = [C.POINTER(Settings), C.c_size_t, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                                                        C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p,
                                                        C.c_void_p]
+        L.lzf_frame_stream_count_device.argtypes = [C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_void_p]
+        L.lzf_frame_stream_decompressed_size_device.argtypes = [C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t,
+                                                                C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                                C.c_void_p, C.c_void_p, C.c_void_p]
+        L.lzf_stream_index_locate.argtypes = [C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint64, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
         _lib = L
     return _lib
 

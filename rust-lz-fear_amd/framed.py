@@ -2,6 +2,7 @@
 `CompressionSettings` with the reference's builder methods (src/framed/compress.rs:56-157) and
 `decompress_frame` (src/framed/decompress.rs:284-288).  Thin Python over the C++ frame layer —
 every block is compressed / decompressed by the HIP kernels."""
+import collections
 import ctypes as C
 
 from . import ffi
@@ -340,10 +341,12 @@ def decompress_frames_device(frames, dictionary=None, caps=None, stream=None, ex
     return [(st[f], outs[f][:ol[f]], co[f]) for f in range(len(frames))]
 
 
-def decompress_streams_device(streams, dictionary=None, caps=None, stream=None):
+def decompress_streams_device(streams, dictionary=None, caps=None, stream=None, exact=False):
     """Streams of back-to-back frames that live on the device (1-D uint8 CUDA tensors), every stream decoded on the device into
     one contiguous tensor (lzf_frame_decompress_stream_device).  Outputs are sized from lzf_frame_stream_bound_device when `caps`
-    is None.  Returns [(status, out_tensor[:out_len], consumed, n_frames)] once `stream` (default: the current stream) has
+    is None — or, with `exact=True`, from lzf_frame_stream_decompressed_size_device: each output is as long as its stream decodes
+    to, not as long as its blocks could at worst.
+    Returns [(status, out_tensor[:out_len], consumed, n_frames)] once `stream` (default: the current stream) has
     finished the call: the status that ended the stream (0: every byte was read), the bytes of its frames up to there, the
     input bytes read and the number of frames that ended at their EndMark."""
     import torch
@@ -353,7 +356,13 @@ def decompress_streams_device(streams, dictionary=None, caps=None, stream=None):
         return []
     dev = streams[0].device
     s = stream if stream is not None else torch.cuda.current_stream(dev)
-    if caps is None:
+    if caps is None and exact:
+        dlen = dictionary.numel() if dictionary is not None else 0
+        with torch.cuda.stream(s):
+            sizes = device.stream_decompressed_size(streams, dictionary_len=dlen, stream=s)[1]
+        s.synchronize()
+        caps = sizes.cpu().tolist()
+    elif caps is None:
         caps = device.stream_decompress_bound(streams, stream=s)
     outs = [torch.empty(int(c), dtype=torch.uint8, device=dev) for c in caps]
     with torch.cuda.stream(s):
@@ -361,6 +370,70 @@ def decompress_streams_device(streams, dictionary=None, caps=None, stream=None):
     s.synchronize()
     st, ol, co, nf = status.cpu().tolist(), out_len.cpu().tolist(), consumed.cpu().tolist(), n_frames.cpu().tolist()
     return [(st[f], outs[f][:ol[f]], co[f], nf[f]) for f in range(len(streams))]
+
+
+StreamIndex = collections.namedtuple("StreamIndex", "status out_len consumed n_frames frames")
+StreamIndex.__doc__ = """What lzf_frame_stream_decompressed_size_device says about one stream: `status`, `out_len`, `consumed` and
+`n_frames` as decompress_streams_device would report them (the content checksums not verified), and `frames`, a numpy structured
+array with the fields of lzf_stream_frame (in_off, consumed, out_off, out_len, content_size, status, flags), one entry per
+frame the walk finds."""
+
+
+def stream_index_device(streams, dictionary_len=0, stream=None):
+    """Exact sizes and the frame index of streams of back-to-back frames that live on the device (1-D uint8 CUDA tensors), found
+    without decoding and without output memory (lzf_frame_stream_count_device, lzf_frame_stream_decompressed_size_device).
+    Returns [StreamIndex] once `stream` has finished the call.  `dictionary_len`: the length of the dictionary the streams
+    will be decoded with."""
+    import numpy as np
+    import torch
+    from . import device
+    streams = list(streams)
+    if not streams:
+        return []
+    s = stream if stream is not None else torch.cuda.current_stream(streams[0].device)
+    with torch.cuda.stream(s):
+        status, out_len, consumed, n_frames, _, entries = device.stream_index(streams, dictionary_len=dictionary_len, stream=s)
+    s.synchronize()
+    st, ol, co, nf = status.cpu().tolist(), out_len.cpu().tolist(), consumed.cpu().tolist(), n_frames.cpu().tolist()
+    frames = [np.ascontiguousarray(e.cpu().numpy()).view(device.SFRAME) for e in entries]
+    return [StreamIndex(st[k], ol[k], co[k], nf[k], frames[k]) for k in range(len(streams))]
+
+
+def locate_frames(index, start, stop):
+    """lzf_stream_index_locate: (first, count) of the frames of `index` (a StreamIndex or its `frames`) whose output meets the
+    bytes [start, stop) of the stream's output; count 0 where none does.  Host only."""
+    import numpy as np
+    frames = np.ascontiguousarray(getattr(index, "frames", index))
+    first, count = C.c_size_t(0), C.c_size_t(0)
+    ffi.check(ffi.lib().lzf_stream_index_locate(frames.ctypes.data if len(frames) else None, len(frames), max(int(start), 0),
+                                                max(int(stop), 0), C.byref(first), C.byref(count)))
+    return first.value, count.value
+
+
+def read_stream_range_device(stream_tensor, index, start, stop, dictionary=None, stream=None):
+    """Bytes [start, min(stop, index.out_len)) of the output of one stream of back-to-back frames (a 1-D uint8 CUDA tensor) with
+    `index`, its StreamIndex: only the frames that hold the range are decoded.  lzf_stream_index_locate finds them; a run of
+    whole frames is itself a stream, so stream_tensor[in_off of the first : in_off + consumed of the last] goes through
+    decompress_streams_device, with an output of exactly those frames' lengths.  Returns a view of that output.
+    Raises FrameError when the decode of those frames does not end as the index says: with the decode's status where it is not 0
+    (a damaged frame in the range: its error, also where the index lists it with that error; a content checksum, which the
+    index never verifies), with InputError where the lengths differ (the index is not of these bytes).  A range read verifies the
+    content checksums only of the frames it decodes: damage in the frames it skips goes unnoticed."""
+    import torch
+    frames = index.frames
+    start, stop = max(int(start), 0), min(int(stop), int(index.out_len))
+    first, count = locate_frames(frames, start, stop) if start < stop else (0, 0)
+    if count == 0:
+        return torch.empty(0, dtype=torch.uint8, device=stream_tensor.device)
+    a, b = frames[first], frames[first + count - 1]
+    lo, hi = int(a["in_off"]), int(b["in_off"]) + int(b["consumed"])
+    base, total = int(a["out_off"]), int(b["out_off"]) + int(b["out_len"]) - int(a["out_off"])
+    (st, out, used, _), = decompress_streams_device([stream_tensor[lo:hi]], dictionary=dictionary, caps=[total], stream=stream)
+    if st != 0:
+        raise FrameError(st)
+    if out.numel() != total or used != hi - lo:
+        raise FrameError(16)
+    return out[start - base:stop - base]
 
 
 class FrameBlockReader:
