@@ -27,62 +27,8 @@ SPAN_MAX = 4096 // 3  # output bytes one batch may produce
 BS = 4 << 20
 
 
-# ---------------------------------------------------------------------------------------------------- raw blocks, sequence by sequence
-def _lsic(v):
-    return b"\xff" * (v // 255) + bytes([v % 255])
-
-
-def _seq(lit, off, mlen):
-    """One sequence (off None: the last literals, no match)."""
-    L = len(lit)
-    b = bytearray([(min(L, 15) << 4) | (0 if off is None else min(mlen - 4, 15))])
-    if L >= 15:
-        b += _lsic(L - 15)
-    b += lit
-    if off is not None:
-        b += off.to_bytes(2, "little")
-        if mlen - 4 >= 15:
-            b += _lsic(mlen - 19)
-    return bytes(b)
-
-
-def _block(seqs, tail=b"tail"):
-    """seqs: (L, M) pairs -> a valid block (offsets inside the output so far) + the last literals."""
-    rng = np.random.default_rng(len(seqs))
-    out_len, blk = 0, bytearray()
-    for L, M in seqs:
-        lit = bytes(rng.integers(0, 256, L, dtype=np.uint8))
-        out_len += L
-        off = int(rng.integers(1, min(out_len, 3000) + 1)) if out_len else 1
-        assert out_len >= 1, "a match needs output before it"
-        blk += _seq(lit, off, M)
-        out_len += M
-    blk += _seq(tail, None, 0)
-    return bytes(blk)
-
-
-def _walk(blk):
-    """The tokens of a valid block: (position, L, M, position of the length byte that follows the match offset or None)."""
-    toks, p, n = [], 0, len(blk)
-    while p < n:
-        t = blk[p]; q = p + 1; L = t >> 4
-        if L == 15:
-            while True:
-                b = blk[q]; q += 1; L += b
-                if b != 255:
-                    break
-        q += L
-        if n - q < 2:
-            toks.append((p, L, 0, None)); break
-        q += 2; M = (t & 15) + 4; mb = None
-        if (t & 15) == 15:
-            mb = q
-            while True:
-                b = blk[q]; q += 1; M += b
-                if b != 255:
-                    break
-        toks.append((p, L, M, mb)); p = q
-    return toks
+# raw blocks, sequence by sequence: the builder lives in seg_stage_cases.py (test_gpu_parse_staging.py takes _block / _walk from here)
+from seg_stage_cases import _lsic, _seq, _block, _walk  # noqa: E402,F401
 
 
 def _batches(blk):

@@ -1,6 +1,6 @@
 """Stage-by-stage check of the segmented decompress pipeline (lz4_decompress_seg.hip) against a host parse of the same
-blocks: token bit maps after the seam stage, token / output totals after the scan, records after the record stage, the
-validity of the dependency levels, and the decoded bytes.  Needs the ANALYSIS library (lzf_debug_seg is not in the product):
+blocks: token bit maps after the seam stage, token / output totals after the scan, every record after the record stage (sub-batch,
+class, flags and dependency level included: the model of tests/seg_stage_cases.py), and the decoded bytes.  Needs the ANALYSIS library (lzf_debug_seg is not in the product):
     LZF_LIB_PATH=rust-lz-fear_amd/liblzfear_hip_analysis.so python tools/seg_debug.py [--big N] [--small]
 ANALYSIS TOOL: uses the oracle as the checker."""
 import argparse
@@ -19,39 +19,10 @@ import oracle_ffi as o  # noqa: E402
 import rust_lz_fear_amd  # noqa: E402,F401
 from rust_lz_fear_amd import ffi, device, synth  # noqa: E402
 
-CHUNK, OVERLAP, TILE = 16384, 2048, 2048
-STRIDE = CHUNK - OVERLAP
-SEGJOB = np.dtype([("eligible", "<u4"), ("failed", "<u4"), ("done", "<u4"), ("nch", "<u4"), ("ntile", "<u4"), ("ntok", "<u4"),
-                   ("outb", "<u4"), ("pad", "<u4"), ("rec_off", "<u8"), ("pad2", "<u8")])
+import seg_stage_cases as S  # noqa: E402  (tests/: the host parse, the slot layout and the record check)
 
-
-def host_parse(c):
-    """[(pos, L, M, off, src)] of a valid block (decompress.rs:61-74)."""
-    out = []
-    p, n = 0, len(c)
-    while p < n:
-        pos = p
-        tok = c[p]; p += 1
-        L = tok >> 4
-        if L == 15:
-            while True:
-                b = c[p]; p += 1; L += b
-                if b != 255:
-                    break
-        src = p
-        p += L
-        if n - p < 2:
-            out.append((pos, L, 0, 0, src))
-            break
-        off = c[p] | (c[p + 1] << 8); p += 2
-        M = tok & 15
-        if M == 15:
-            while True:
-                b = c[p]; p += 1; M += b
-                if b != 255:
-                    break
-        out.append((pos, L, M + 4, off, src))
-    return out
+CHUNK, STRIDE, SEGJOB = S.CHUNK, S.STRIDE, S.SEGJOB
+host_parse = S.host_parse
 
 
 def run(blocks, min_in, upto, verbose=True):
@@ -117,35 +88,16 @@ def run(blocks, min_in, upto, verbose=True):
             msgs.append(f"nch {nch} != {exp_nch}")
         if upto >= 3 and not s["failed"]:
             # the true token set against the stitched bit maps
-            truth = np.zeros(len(cdat) + 64, np.uint8)
-            for t in toks:
-                truth[t[0]] = 1
-            got = np.zeros(len(cdat) + 64, np.uint8)
-            for h in range(nch):
-                base = h * STRIDE
-                o0 = 0 if h == 0 else base + OVERLAP
-                o1 = min(base + CHUNK, len(cdat)) if h < nch - 1 else len(cdat)
-                vf = int(vfrom[i, h])
-                if vf == 0xFFFFFFFF or o1 <= o0:
-                    continue
-                row = np.unpackbits(bits[i, h].view(np.uint8), bitorder="little")
-                a = max(o0, vf)
-                if a < o1:
-                    got[a:o1] = row[a - base:o1 - base]
-            diff = np.nonzero(truth[:len(cdat)] != got[:len(cdat)])[0]
+            truth = np.zeros(len(cdat), bool)
+            truth[[t[0] for t in toks]] = True
+            got = S.device_token_map(len(cdat), nch, vfrom[i], bits[i])
+            diff = np.nonzero(truth != got)[0]
             if len(diff):
                 p = int(diff[0]); h = 0 if p < CHUNK else 1 + (p - CHUNK) // STRIDE
-                msgs.append(f"token map differs at {len(diff)} positions, first {p} (truth {truth[p]}, chunk {h}, vfrom {vfrom[i, h]:#x}, x[h-1] {xexit[i, h - 1] if h else 0})")
-        # records live in batches of 64 that never span 2 KiB tiles of the input: a tile's tokens, then padding
-        slots = []                                   # index into toks, or None (padding)
-        k0 = 0
-        ntile = (len(cdat) + TILE - 1) // TILE
-        for t in range(ntile):
-            k1 = k0
-            while k1 < len(toks) and toks[k1][0] < (t + 1) * TILE:
-                k1 += 1
-            slots.extend(range(k0, k1)); slots.extend([None] * ((-(k1 - k0)) % 64))
-            k0 = k1
+                msgs.append(f"token map differs at {len(diff)} positions, first {p} (truth {int(truth[p])}, chunk {h}, vfrom {vfrom[i, h]:#x}, x[h-1] {xexit[i, h - 1] if h else 0})")
+        # records live in batches of 64 that never span 2 KiB tiles of the input: a tile's tokens, then padding (the model's slot layout)
+        ly = S.Layout(len(cdat), toks)
+        slots = ly.tok                               # index into toks, or -1 (padding)
         if upto >= 5 and not s["failed"]:
             if int(s["ntok"]) != len(slots):
                 msgs.append(f"padded record count {s['ntok']} != {len(slots)}")
@@ -154,42 +106,17 @@ def run(blocks, min_in, upto, verbose=True):
         if upto >= 6 and not s["failed"] and int(s["ntok"]) == len(slots):
             r = recs[int(s["rec_off"]):int(s["rec_off"]) + len(slots)]
             rbias = (int(dout.data_ptr()) + int(out_off[i])) & 15
-            lo = 0
-            exp = np.zeros((len(slots), 3), np.int64)     # mo, M, off of every slot (padding: the end so far, 0, 0)
-            for q, k in enumerate(slots):
-                if k is None:
-                    exp[q] = (lo, 0, 0)
-                else:
-                    _, L, M, off, _ = toks[k]
-                    exp[q] = (lo + L, M, off); lo += L + M
-            got = np.stack([r[:, 1].astype(np.int64) - rbias, r[:, 0], r[:, 3] & 0xFFFF], axis=1)
-            bad = np.nonzero((got != exp).any(axis=1))[0]
-            if len(bad):
-                q = int(bad[0])
-                msgs.append(f"{len(bad)} records differ, first slot #{q}: got {got[q].tolist()} exp {exp[q].tolist()}")
-            else:
-                # levels: a match's level must exceed the level of every match of its batch whose destination it reads
+            # every word, sub-batch, class, flags and level against the model, for the ring the library classed the records for (LZF_SEG_RING,
+            # or the one of the three the records agree with)
+            rings = [int(os.environ["LZF_SEG_RING"])] if os.environ.get("LZF_SEG_RING") else list(S.RINGS)[::-1]
+            found = [S.check_records(ly, r, R, rbias)[0] for R in rings]
+            bad = min(found, key=len)
+            if bad:
+                msgs += bad
+            elif verbose:
                 lv = (r[:, 2] >> 16) & 0xFF
-                nbad = 0
-                for b0 in range(0, len(slots), 64):
-                    for q in range(b0, b0 + 64):
-                        mo, M, off = (int(x) for x in exp[q])
-                        if not M:
-                            continue
-                        if lv[q] < 1:
-                            nbad += 1; continue
-                        s0 = mo - off; e0 = s0 + min(M, off)
-                        for q2 in range(b0, q):
-                            qmo, qM = int(exp[q2][0]), int(exp[q2][1])
-                            if qM and qmo < e0 and qmo + qM > s0 and lv[q2] >= lv[q]:
-                                nbad += 1
-                                if nbad < 4:
-                                    msgs.append(f"level order broken: slot {q} (lvl {lv[q]}) reads slot {q2} (lvl {lv[q2]})")
-                if nbad:
-                    msgs.append(f"{nbad} level violations")
-                elif verbose:
-                    mx = [int(lv[b0:b0 + 64].max()) for b0 in range(0, len(slots), 64)]
-                    print(f"  [{name}] levels ok, mean max level per batch {sum(mx) / max(1, len(mx)):.2f}, {len(slots) - len(toks)} padding slots for {len(toks)} tokens")
+                mx = [int(lv[b0:b0 + 64].max()) for b0 in range(0, len(slots), 64)]
+                print(f"  [{name}] levels ok, mean max level per batch {sum(mx) / max(1, len(mx)):.2f}, {len(slots) - len(toks)} padding slots for {len(toks)} tokens")
         if upto >= 8:
             got = hout[int(out_off[i]):int(out_off[i]) + len(d)].tobytes()
             if s["failed"] or not s["done"]:
