@@ -112,6 +112,7 @@ extern "C" {
     pub fn lzf_decompressed_size_batch(d_jobs: *const lzf_decompress_job, d_results: *mut lzf_job_result, n_jobs: u32, max_input_len: u64, hip_stream: *mut c_void) -> c_int;
     pub fn lzf_decompressed_size_batch_host(jobs: *const lzf_decompress_job, results: *mut lzf_job_result, n_jobs: u32) -> c_int;
     pub fn lzf_last_decompress_launch() -> *const c_char;
+    pub fn lzf_last_size_launch() -> *const c_char;
     pub fn lzf_last_compress_launch() -> *const c_char;
     // EncoderTable::replace / ::offset on host tables (src/raw/compress/mod.rs:64-74, :88-99)
     pub fn lzf_table_replace_host(table: *mut c_void, table_kind: u32, input: *const u8, input_len: u64, pos: u64, previous: *mut u64) -> c_int;

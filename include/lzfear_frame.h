@@ -226,8 +226,10 @@ int lzf_frame_decompress_device_many(uint32_t n_frames, const uint8_t* const* d_
  * Only the dictionary's length matters (every block's decode may reach dict_len bytes behind its output); no dictionary bytes
  * are passed.  The host waits twice, as for the decode (scan summary, block table), then enqueues block checksums
  * (lzf_xxh32_batch), lzf_decompressed_size_batch over the blocks (linked frames in lock-step, history carried as a length) and
- * the decode's stop rules, waits for its own upload of job lists and returns.  Scratch (jobs, results, 24 bytes per block) comes
- * from the stream-ordered pool and does not depend on the decoded sizes. */
+ * the decode's stop rules, waits for its own upload of job lists and returns.  Scratch (jobs, results, 24 bytes per block, and what
+ * lzf_decompressed_size_batch takes for a call of few large blocks: about 1.2 bits per compressed byte of the largest block x blocks,
+ * which a pool that is short of memory may refuse without changing any result) comes from the stream-ordered pool and does not
+ * depend on the decoded sizes. */
 int lzf_frame_decompressed_size_device(uint32_t n_frames, const uint8_t* const* d_in, const size_t* in_len,
                                        size_t dict_len,
                                        uint64_t* d_out_len, uint64_t* d_consumed, int32_t* d_status,

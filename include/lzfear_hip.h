@@ -155,16 +155,29 @@ int lzf_decompress_batch_sized(const lzf_decompress_job* d_jobs, lzf_job_result*
  *            limit-checked).  LZF_CONTRACT where the decoder refuses the job: input_len, out_existing_len or prefix_len of 2 GiB - 256 or more.
  *   out_len  on LZF_OK output.len(), out_existing_len included; unspecified on an error.  The decoder stops at 2 GiB of
  *            output; this call does not: a block that decodes to more (LZ4 expands up to 255 x) gets its true 64-bit length.
- *   reserved kilo-cycles, as for the decoder.
- * max_input_len: as for lzf_decompress_batch_sized (~0 = unknown); it may size scratch only.  Scratch (a job counter, and 4
- * bytes per job for the launch order of batches larger than the device holds at once) is independent of the decoded sizes and
- * comes from the stream-ordered pool, freed in stream order.  The call enqueues its kernels and returns; no host wait.  One
- * wavefront per job. */
+ *   reserved a diagnostic: kilo-cycles, as for the decoder, for a job the one-wave kernel answered; the number of 2 KiB tiles of the
+ *            input for a job the latency class answered.
+ * Two classes, picked by the call's size alone (lzf_last_size_launch says which ran); results are the same either way:
+ *   * a call of up to 16 jobs per compute unit (4 096 on MI355X) whose max_input_len is 64 KiB or more takes the LATENCY CLASS
+ *     first: a block is summed up by many wavefronts (the segmented pipeline's plan, parse and seam, then one wavefront per 2 KiB of
+ *     input and one per job), which answers every job of 64 KiB .. 4 MiB + 32 KiB of input that decodes cleanly;
+ *   * always last, one wavefront per job over the whole call, skipping what the class answered: every error status, every other size.
+ * max_input_len: as for lzf_decompress_batch_sized (~0 = unknown: 4 MiB blocks at their worst case); it sizes the latency class's
+ * scratch — bit maps, chunk exits and 16 bytes per tile: about 1.2 bits per byte of max_input_len and job, at most 3 GiB, 0.61 MiB
+ * per job of unknown size.  A caller of many SMALL blocks should pass its bound: with ~0 a call of up to 16 jobs per CU enters the class
+ * whatever its inputs are, takes that scratch and runs the class's front over jobs that are all below its window before the one-wave kernel
+ * answers them (4 096 blocks of 500 bytes: 0.31 ms instead of 0.13, 2.4 GiB of pool memory; with the bound, 0.13 ms and a job counter).  The one-wave kernel's scratch is a job counter, and 4 bytes per job for the launch order of batches
+ * larger than the device holds at once.  All of it is independent of the decoded sizes, comes from the stream-ordered pool and is
+ * freed in stream order; a pool that refuses the class's scratch is no error — the one-wave kernel then answers the whole call.  The
+ * call enqueues its kernels and returns; no host wait. */
 int lzf_decompressed_size_batch(const lzf_decompress_job* d_jobs, lzf_job_result* d_results,
                                 uint32_t n_jobs, uint64_t max_input_len, void* hip_stream);
 /* Diagnostic: the kernels the calling thread's last lzf_decompress_batch launched (the batch size picks them: the
  * segmented pipeline — one block decoded by many wavefronts — up to four blocks per CU, one workgroup per block beyond). */
 const char* lzf_last_decompress_launch(void);
+/* The same for the calling thread's last lzf_decompressed_size_batch: "latency: ..." when the latency class ran in front of the
+ * one-wave kernel, the one-wave kernel's name alone otherwise (larger calls, small inputs, no scratch from the pool). */
+const char* lzf_last_size_launch(void);
 /* The same for the calling thread's last lzf_compress_batch: "lzf_compress_team_kernel" (the latency class: no more jobs than
  * compute units, a team of three wavefronts and a CU's LDS per block) or "lzf_compress_compact_kernel" (one wavefront per
  * block, 18 per CU), plus the general kernels that ran beside it for U16 / writable-table jobs. */

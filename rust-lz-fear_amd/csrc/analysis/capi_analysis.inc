@@ -65,6 +65,11 @@ static const KnobRow kKnobRows[] = {
     {"LZF_FED_SLOTS", &d::Knobs::fed_slots, knob_in<1, 0x7FFFFFFFL>, nullptr},   // slots per CU
     {"LZF_FED_PAD_LDS", &d::Knobs::fed_pad_lds, knob_any, nullptr},              // bytes of unused LDS per wavefront (residency experiment)
     {"LZF_FED_CARRY", &d::Knobs::fed_carry, knob_in<0, 63>, nullptr},            // the longest last batch of a window that is left for the next window (0: never; A/B)
+    // the size call's latency class: force = every call that fits its scratch / off = none; its smallest input; LZF_SIZE_FORCE=1 its scratch
+    // refused, 2 no one-wave kernel behind it (tests/test_gpu_size_latency.py: what the class finished itself)
+    {"LZF_SIZE_SEG", nullptr, nullptr, [](const char* e, d::Knobs& k) { k.size_seg = !strcmp(e, "force") ? d::kForced : !strcmp(e, "off") ? d::kOff : d::kByRule; }},
+    {"LZF_SIZE_SEG_MIN_IN", &d::Knobs::size_seg_min_in, knob_any, nullptr},
+    {"LZF_SIZE_FORCE", &d::Knobs::size_force, knob_in<0, 2>, nullptr},
     {"LZF_FED_VERBOSE", nullptr, nullptr, [](const char*, d::Knobs& k) { k.fed_verbose = true; }},
 };
 static d::Knobs analysis_knobs() {

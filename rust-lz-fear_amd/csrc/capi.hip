@@ -14,6 +14,7 @@ thread_local std::string g_last_error;
 namespace {
 thread_local const char* g_last_decompress = "";      // what the last lzf_decompress_batch of this thread launched (lzf_last_decompress_launch)
 thread_local const char* g_last_compress = "";        // ... and the last lzf_compress_batch
+thread_local const char* g_last_size = "";            // ... and the last lzf_decompressed_size_batch
 }
 
 int ensure_device() {
@@ -109,7 +110,8 @@ constexpr auto k_compact = lzf::lzf_compress_compact_kernel<false>;
 constexpr auto k_compact_dry = lzf::lzf_compress_compact_kernel<true>;
 constexpr auto k_general_u32 = lzf::lzf_compress_wave_kernel<LZF_TABLE_U32>;
 constexpr auto k_general_u16 = lzf::lzf_compress_wave_kernel<LZF_TABLE_U16>;
-constexpr auto k_size = lzf::lzf_decoded_size_kernel<48, 768>;
+constexpr auto k_size = lzf::lzf_decoded_size_kernel<48, 768, false>;
+constexpr auto k_size_skip = lzf::lzf_decoded_size_kernel<48, 768, true>;      // behind the latency class: skips what that finished
 
 // the launches of lzf_compress_batch: the cost probe and the order when the plan wants them and the pool has room, then the kernels
 int compress_launches(const d::CompressPlan& p, const lzf_compress_job* d_jobs, lzf_job_result* d_results, uint32_t n_jobs, AsyncScratch& scratch, hipStream_t st) {
@@ -210,6 +212,7 @@ int lzf_abi_version(void) { return LZFEAR_ABI_VERSION; }
 const char* lzf_last_error(void) { return g_last_error.c_str(); }
 const char* lzf_last_decompress_launch(void) { return g_last_decompress; }
 const char* lzf_last_compress_launch(void) { return g_last_compress; }
+const char* lzf_last_size_launch(void) { return g_last_size; }
 int lzf_device_count(void) { return ensure_device(); }
 
 // Launch order (both batch calls): a batch of more jobs than the chip holds at once runs longest job first, or the launch
@@ -247,11 +250,15 @@ int lzf_decompress_batch_sized(const lzf_decompress_job* d_jobs, lzf_job_result*
     return rc;
 }
 
-// decompress_raw's status and output.len() of every job, nothing decoded (lz4_decoded_size.hip).  One wavefront per job; as many
-// workgroups as the device holds at once draw jobs from a 4-byte counter; with more jobs than that, in the order of their input
-// lengths, longest first (4 bytes per job).  That is all the scratch there is.
+// decompress_raw's status and output.len() of every job, nothing decoded.  The call executes lzf_dispatch.h's size_plan:
+//   * few large blocks (the latency class): plan, parse and seam of the segmented pipeline, the tiles summed up, every job's tiles
+//     added up and checked (lz4_decoded_size_seg.inc) — scratch from the stream-ordered pool, about 1.2 bits per byte of
+//     max_input_len x n_jobs, freed in stream order; a pool that refuses it only sends the call down the other way;
+//   * always last: lzf_decoded_size_kernel (lz4_decoded_size.hip), one wavefront per job, over the whole call; behind the class it skips
+//     the jobs that finished there.  As many workgroups as the device holds at once draw jobs from a 4-byte counter; with more jobs
+//     than that, in the order of their input lengths, longest first (4 bytes per job).
+// Enqueue only: no host wait.
 int lzf_decompressed_size_batch(const lzf_decompress_job* d_jobs, lzf_job_result* d_results, uint32_t n_jobs, uint64_t max_input_len, void* hip_stream) {
-    (void)max_input_len;               // (sizes no scratch today: the counter and the launch order depend on n_jobs alone)
     if (n_jobs == 0) return LZF_OK;
     if (!d_jobs || !d_results) { g_last_error = "lzf_decompressed_size_batch: NULL job/result array"; return LZF_E_INVALID; }
     int rc = ensure_device();
@@ -259,6 +266,12 @@ int lzf_decompressed_size_batch(const lzf_decompress_job* d_jobs, lzf_job_result
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     Device& dv = device();
     keep_pool_memory(dv);
+    const d::SizePlan plan = d::size_plan(dv.geo, knobs(), n_jobs, max_input_len);
+    AsyncScratch seg_mem(st);
+    const lzf::seg_job* done = nullptr;
+    if (plan.try_seg && (rc = size_seg_front(dv, d_jobs, d_results, n_jobs, plan, seg_mem, st, &done, max_input_len)) != LZF_OK) return rc;
+    g_last_size = done ? plan.seg_launch : plan.last_launch;
+    if (done && !plan.last) { HIP_TRY(seg_mem.release()); return LZF_OK; }
     uint32_t resident = 0;             // workgroups of the kernel per CU
     {
         std::lock_guard<std::mutex> lk(device_mutex());
@@ -277,8 +290,10 @@ int lzf_decompressed_size_batch(const lzf_decompress_job* d_jobs, lzf_job_result
     uint32_t* const perm = ordered ? static_cast<uint32_t*>(ticket.p) + 64 : nullptr;
     if (ordered) LAUNCH(lzf::lzf_order_by_input_len_kernel, dim3(1), dim3(1024), 0, st, d_jobs, perm, n_jobs);
     const uint32_t grid = n_jobs < room ? n_jobs : (uint32_t)room;
-    LAUNCH(k_size, dim3(grid), dim3(64), 0, st, d_jobs, d_results, n_jobs, static_cast<uint32_t*>(ticket.p), (const uint32_t*)perm);
+    if (done) LAUNCH(k_size_skip, dim3(grid), dim3(64), 0, st, d_jobs, d_results, n_jobs, static_cast<uint32_t*>(ticket.p), (const uint32_t*)perm, done);
+    else LAUNCH(k_size, dim3(grid), dim3(64), 0, st, d_jobs, d_results, n_jobs, static_cast<uint32_t*>(ticket.p), (const uint32_t*)perm, (const lzf::seg_job*)nullptr);
     HIP_TRY(ticket.release());
+    HIP_TRY(seg_mem.release());
     return LZF_OK;
 }
 

@@ -1,5 +1,5 @@
 // capi_drivers.hip — the host drivers of the two multi-launch decompress paths: the segmented pipeline (lz4_decompress_seg.hip) and
-// the bitmap-fed kernel behind its plan + parse stages (lz4_decompress_fed.hip).  They execute a plan of lzf_dispatch.h; whether a
+// the bitmap-fed kernel behind its plan + parse stages (lz4_decompress_fed.hip), and the front of the size call's latency class.  They execute a plan of lzf_dispatch.h; whether a
 // call comes here at all, with which ring and in which groups, is decided there.
 #include "capi_internal.h"
 #include "kernels.h"
@@ -159,6 +159,34 @@ int seg_decompress(Device& dv, const lzf_decompress_job* d_jobs, lzf_job_result*
     if (rc == LZF_OK) LAUNCH_RC(rc, k_paired48, dim3(n), dim3(128), 0, st, d_jobs, d_results, n, (const uint32_t*)nullptr, (const lzf::seg_job*)s.ctx.st);
     if (s.mem.release() != hipSuccess && rc == LZF_OK) rc = LZF_E_HIP;
     if (rc != LZF_OK) g_last_error = "segmented decompress: launch failed";
+    return rc;
+}
+
+// ---- the size call's latency class (lz4_decoded_size_seg.inc) -------------------------------------------------------------------
+// plan, parse and seam of the pipeline over the whole call — `out` is not needed, prefix and existing output are lengths — then the
+// tiles summed up and every job's tiles added up and checked.  Enqueue only; the scratch stays with the caller until the one-wave
+// kernel behind this has looked at the state array.
+int size_seg_front(Device& dv, const lzf_decompress_job* d_jobs, lzf_job_result* d_results, uint32_t n, const d::SizePlan& plan, AsyncScratch& mem, hipStream_t st,
+                   const lzf::seg_job** done, uint64_t max_in_hint) {
+    *done = nullptr;
+    const d::SizeLayout l = d::size_layout(n, max_in_hint);
+    if (knobs().size_force == 1u || !mem.alloc(l.total)) return LZF_OK;      // (no scratch — or the analysis library's forced refusal: the one-wave kernel takes the call as it always did)
+    lzf::seg_ctx c{};
+    c.jobs = d_jobs; c.results = d_results; c.n_jobs = n;
+    c.max_in = l.d.max_in; c.min_in = plan.min_in; c.maxch = l.d.maxch; c.maxtile = l.d.maxtile;
+    c.st = area<lzf::seg_job>(mem, l.o_st);
+    c.xexit = area<uint32_t>(mem, l.o_xexit);
+    c.vfrom = area<uint32_t>(mem, l.o_vfrom);
+    c.tile_sum = area<lzf::u32x4>(mem, l.o_tile_sum);
+    c.bits = area<uint32_t>(mem, l.o_bits);
+    c.by_len = plan.by_len ? area<uint32_t>(mem, l.o_by_len) : nullptr;
+    c.n_cu = dv.geo.cu; c.g_off = 0u; c.g_n = n; c.size_only = 1u;
+    int rc = seg_launch_prep(c, st);
+    if (rc == LZF_OK) rc = seg_launch_front(c, 3u, st);           // parse, seam
+    if (rc == LZF_OK) LAUNCH_RC(rc, lzf::lzf_size_tile_kernel, dim3(seg_grid(seg_tile_target(c), n, c.maxtile), n), dim3(64), 0, st, c);
+    if (rc == LZF_OK) LAUNCH_RC(rc, lzf::lzf_size_finish_kernel, dim3(n), dim3(64), 0, st, c);
+    if (rc != LZF_OK) g_last_error = "decoded sizes, latency class: launch failed";
+    *done = c.st;
     return rc;
 }
 

@@ -9,6 +9,8 @@
 #include "lzfear_hip.h"
 #include "lzf_dispatch.h"
 
+namespace lzf { struct seg_job; }
+
 // (hidden: the library exports the C entry points of lzfear_hip.h and nothing of this)
 namespace lzf_capi __attribute__((visibility("hidden"))) {
 
@@ -85,5 +87,9 @@ SegLanes* seg_lanes(Device& dv);     // null when the streams could not be made
 // capi_drivers.hip.  *used = false: the path declined the call and launched nothing.
 int seg_decompress(Device& dv, const lzf_decompress_job* d_jobs, lzf_job_result* d_results, uint32_t n, const lzf_dispatch::DecompressPlan& plan, hipStream_t st, bool* used, uint64_t max_in_hint);
 int fed_decompress(Device& dv, const lzf_decompress_job* d_jobs, lzf_job_result* d_results, uint32_t n, uint32_t* perm, uint32_t* est, hipStream_t st, bool* used, uint64_t max_in_hint);
+// the front of the size call's latency class: scratch into `mem` (the caller frees it behind the one-wave kernel), plan .. finish.
+// *done = the state array the one-wave kernel skips by, or null: the pool refused the scratch and nothing was launched.
+int size_seg_front(Device& dv, const lzf_decompress_job* d_jobs, lzf_job_result* d_results, uint32_t n, const lzf_dispatch::SizePlan& plan, AsyncScratch& mem, hipStream_t st,
+                   const lzf::seg_job** done, uint64_t max_in_hint);
 
 }  // namespace lzf_capi

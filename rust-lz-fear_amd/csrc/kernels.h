@@ -37,11 +37,15 @@ LZF_DECOMPRESS_VARIANTS(LZF_EXT)
 // lz4_decoded_size.hip: decompress_raw's status and output.len() per job without decoding (one wavefront per job, jobs drawn from
 // *ticket, which starts at 0, in the order of perm when given); S = region bytes, TOKCAP = token-list entries of the shared parse
 // (48-byte regions, 3 KiB per parse: 71 / 52 / 49 ms for 16 / 32 / 48 on the bench's 11 769 blocks, profiles/decoded_size.txt)
-template <int S, int TOKCAP>
-__global__ __launch_bounds__(64) void lzf_decoded_size_kernel(const lzf_decompress_job* __restrict__ jobs, lzf_job_result* __restrict__ results,
-                                                              uint32_t n_jobs, uint32_t* __restrict__ ticket, const uint32_t* __restrict__ perm);
-extern template __global__ void lzf_decoded_size_kernel<48, 768>(const lzf_decompress_job*, lzf_job_result*, uint32_t, uint32_t*, const uint32_t*);
 struct seg_job;
+// SKIP: behind the size call's latency class (below) — `done` is its state array, and a job it finished (done[jid].done != 0) is
+// skipped.  A call outside that class launches the SKIP = false form, which never looks at `done`: the kernel as it was before the class.
+template <int S, int TOKCAP, bool SKIP>
+__global__ __launch_bounds__(64) void lzf_decoded_size_kernel(const lzf_decompress_job* __restrict__ jobs, lzf_job_result* __restrict__ results,
+                                                              uint32_t n_jobs, uint32_t* __restrict__ ticket, const uint32_t* __restrict__ perm,
+                                                              const seg_job* __restrict__ done);
+extern template __global__ void lzf_decoded_size_kernel<48, 768, false>(const lzf_decompress_job*, lzf_job_result*, uint32_t, uint32_t*, const uint32_t*, const seg_job*);
+extern template __global__ void lzf_decoded_size_kernel<48, 768, true>(const lzf_decompress_job*, lzf_job_result*, uint32_t, uint32_t*, const uint32_t*, const seg_job*);
 // done (optional): state array of the segmented pipeline; a job it finished (done[jid].done != 0) is skipped
 template <int RING, int S, int TOKCAP>
 __global__ __launch_bounds__(128) void lzf_decompress_paired_kernel(const lzf_decompress_job* __restrict__ jobs, lzf_job_result* __restrict__ results, uint32_t n_jobs,
@@ -118,6 +122,11 @@ struct seg_ctx {
     // length for a job the map does not cover) and counted up by the parse (every chunk adds the tokens it owns).  null: no order asked for
     uint32_t* est;
     uint32_t len_shift;
+    // the size call's latency class (lz4_decoded_size_seg.inc): plan, parse and seam serve lzf_size_tile_kernel / lzf_size_finish_kernel.
+    // Nothing is decoded, so `out` may be NULL and prefix / existing output do not make a job ineligible (they enter the finish kernel's
+    // checks); an empty input is a job of no chunk and no tile.  No arena: rec_top, recs, tile_tok and tile_out are NULL.
+    uint32_t size_only;
+    u32x4* tile_sum;             // [n_jobs][maxtile]      lzf_size::TileSum of every tile
 };
 // ---------------------------------------------------------------------------------------------------------------------
 // Bitmap-fed decompress (lz4_decompress_fed.hip): batches beyond what the chip holds at once.  plan + parse of the segmented
@@ -187,6 +196,12 @@ __global__ void lzf_seg_seam_kernel(seg_ctx c);
 __global__ void lzf_seg_tilesum_kernel(seg_ctx c);
 __global__ void lzf_seg_scan_kernel(seg_ctx c);
 __global__ void lzf_seg_records_kernel(seg_ctx c);
+// The size call for few large blocks (lzf_dispatch.h: size_plan): behind plan, parse and seam, one wavefront per 2 KiB tile sums up
+// the tile's sequences relative to its first token (lzf_size_rules.h: TileSum), then one wavefront per job adds the tiles up and
+// runs the position checks per tile.  A job that comes out clean gets its result and done = 1; every other job — any DecodeError,
+// a length beyond the clamp, sizes outside the window — is left, untouched, to lzf_decoded_size_kernel, which runs last.
+__global__ void lzf_size_tile_kernel(seg_ctx c);
+__global__ void lzf_size_finish_kernel(seg_ctx c);
 template <int R>
 __global__ __launch_bounds__(128) void lzf_seg_resolve_pair_kernel(seg_ctx c);
 extern template __global__ void lzf_seg_resolve_pair_kernel<32768>(seg_ctx);

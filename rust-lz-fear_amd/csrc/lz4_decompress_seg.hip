@@ -18,6 +18,7 @@
 #include "kernels.h"
 #include "lzf_dispatch.h"
 #include "lzf_copy_helpers.h"
+#include "lzf_size_rules.h"
 #include <type_traits>
 
 namespace lzf {
@@ -146,15 +147,18 @@ __device__ __forceinline__ uint64_t lds_ld64u(uint32_t a) {
 // =====================================================================================================================
 __global__ __launch_bounds__(256) void lzf_seg_plan_kernel(seg_ctx c) {
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j == 0u) *c.rec_top = 0ull;
+    if (j == 0u && c.rec_top) *c.rec_top = 0ull;
     if (j >= c.n_jobs) return;
     const lzf_decompress_job job = c.jobs[j];
     seg_job s;
     s.failed = 0; s.done = 0; s.ntok = 0; s.outb = 0; s.pad = 0; s.rec_off = 0; s.pad2 = 0;
-    s.eligible = ((c.fed || (job.prefix_len == 0 && job.out_existing_len == 0)) && job.input_len >= c.min_in && job.input_len <= c.max_in &&
-                  job.input != nullptr && job.out != nullptr) ? 1u : 0u;
+    const bool in_window = job.input_len >= c.min_in && job.input_len <= c.max_in;
+    if (c.size_only)     // nothing is decoded: no `out`, prefix and existing output are lengths (beyond 2 GiB: the one-wave kernel's LZF_CONTRACT); an empty input has no bytes to point at
+        s.eligible = (in_window && (job.input != nullptr || job.input_len == 0) && job.prefix_len < kMaxPosB && job.out_existing_len < kMaxPosB) ? 1u : 0u;
+    else
+        s.eligible = ((c.fed || (job.prefix_len == 0 && job.out_existing_len == 0)) && in_window && job.input != nullptr && job.out != nullptr) ? 1u : 0u;
     const uint32_t len = s.eligible ? (uint32_t)job.input_len : 0u;
-    s.nch = s.eligible ? seg_nch(len) : 0u;
+    s.nch = s.eligible && !(c.size_only && len == 0u) ? seg_nch(len) : 0u;
     s.ntile = (len + kSegTile - 1u) / kSegTile;
     if (s.nch > c.maxch || s.ntile > c.maxtile) { s.eligible = 0; s.nch = 0; s.ntile = 0; }
     c.st[j] = s;
@@ -759,6 +763,11 @@ __global__ __launch_bounds__(64) void lzf_seg_scan_kernel(seg_ctx c) {
         else { c.st[j].ntok = (uint32_t)ctok; c.st[j].outb = (uint32_t)cout; c.st[j].rec_off = off; }
     }
 }
+
+// =====================================================================================================================
+// the size call's latency class: the tiles summed up, nothing decoded (lzf_size_tile_kernel, lzf_size_finish_kernel)
+// =====================================================================================================================
+#include "lz4_decoded_size_seg.inc"
 
 // =====================================================================================================================
 // records + literals + levels: everything the resolve stage needs to know about a sequence, so that its two wavefronts

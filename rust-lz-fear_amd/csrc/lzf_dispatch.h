@@ -6,7 +6,8 @@
 //   Knobs            every tuning value; the defaults ARE the product (the analysis library fills them from the environment, once)
 //   decompress_plan  order wanted?  pipeline tried (window, ring, groups)?  fed path tried?  which pair / staged kernel last?
 //   compress_plan    team / compact / general, fresh-only, probe order wanted?
-//   seg_layout / fed_layout   the areas of the two scratch allocations
+//   size_plan        the size call: the latency class (a block summed up by many wavefronts) tried?  which form of the one-wave kernel last?
+//   seg_layout / fed_layout / size_layout   the areas of the scratch allocations
 #ifndef LZF_DISPATCH_H
 #define LZF_DISPATCH_H
 
@@ -79,6 +80,10 @@ struct Knobs {
     uint32_t fed_pad_lds = 0u;                       // unused LDS per wavefront
     uint32_t fed_carry = (uint32_t)kFedwCarry;
     bool fed_verbose = false;
+    // the size call's latency class
+    uint32_t size_seg = kByRule;
+    uint32_t size_seg_min_in = kSegMinIn;
+    uint32_t size_force = 0u;                        // 1: its scratch refused, where the pool would refuse it (capi_drivers.hip); 2: no one-wave kernel behind it (tests: what the class finished itself)
     // compress
     uint32_t compress_kernel = kCompressByRule;
     long team_max = -1;                              // jobs per call the team kernel takes (-1: one per CU)
@@ -99,6 +104,10 @@ constexpr const char* launch_seg(uint32_t ring) {
          : ring == 65536u ? "segmented: lzf_seg_resolve_pair_kernel<65536> + lzf_decompress_paired_kernel<4096,48,640>"
                           : "segmented: lzf_seg_resolve_pair_kernel<32768> + lzf_decompress_paired_kernel<4096,48,640>";
 }
+
+// lzf_last_size_launch: the latency class in front of the one-wave kernel / the one-wave kernel alone
+constexpr const char* kLaunchSizeSeg = "latency: lzf_seg_parse_kernel + lzf_size_tile_kernel + lzf_size_finish_kernel + lzf_decoded_size_kernel<48,768>";
+constexpr const char* kLaunchSizeWave = "lzf_decoded_size_kernel<48,768>";
 
 // ---- segmented pipeline: batch limit, ring, ranks, groups ----------------------------------------------------------------------------
 constexpr uint32_t seg_blocks_per_cu(const Geometry& g, uint32_t ring) { return per_cu(g, ring + kSegRingSlack); }
@@ -183,6 +192,55 @@ inline FedLayout fed_layout(uint32_t n, uint64_t max_in_hint) {
     l.o_state = c.take((uint64_t)kFedStateBytes * n);
     l.total = c.off;
     return l;
+}
+
+// The size call's latency class: the pipeline's front (state, exits, vfrom, bit maps) and 16 bytes per tile in place of
+// tile_tok / tile_out; no arena, no arena top, no resolve order.
+struct SizeLayout { SegDims d; uint64_t o_st, o_xexit, o_vfrom, o_tile_sum, o_bits, o_by_len, total; };
+inline SizeLayout size_layout(uint32_t n, uint64_t max_in_hint) {
+    SizeLayout l{}; Carver c;
+    l.d = seg_dims(max_in_hint);
+    l.o_st = c.take((uint64_t)kSegJobBytes * n);
+    l.o_xexit = c.take(4ull * n * l.d.maxch);
+    l.o_vfrom = c.take(4ull * n * l.d.maxch);
+    l.o_tile_sum = c.take(16ull * n * l.d.maxtile);
+    l.o_bits = c.take(4ull * n * l.d.maxch * kSegChunkWords);
+    l.o_by_len = c.take(4ull * n);
+    l.total = c.off;
+    return l;
+}
+
+// ---- the size call -------------------------------------------------------------------------------------------------------------------
+// lzf_decoded_size_kernel is one wavefront per job: a 4 MiB block takes it about 20 ms whatever the batch, and it fills the chip
+// from 16 x 256 jobs on.  A call that leaves the chip mostly empty therefore goes through the LATENCY CLASS first: the pipeline's
+// plan, parse and seam, then lzf_size_tile_kernel and lzf_size_finish_kernel, which finish every job that decodes cleanly; the
+// one-wave kernel runs last over the whole call and skips those.  The class is every call of up to 16 jobs per CU (4 096 on MI355X: where
+// the one-wave kernel begins to fill the chip, and the last count of the sweep at which every run of the class was shorter than every
+// run of the one-wave kernel: profiles/size_latency_class.txt) with at least one input of size_seg_min_in bytes by the caller's bound.
+constexpr uint32_t kSizeJobsPerCu = 16u;
+constexpr uint32_t size_seg_max_jobs(const Geometry& g) { return kSizeJobsPerCu * g.cu; }
+// The scratch is about 1.2 bits per compressed byte of the largest job x jobs (4 096 jobs at kSegMaxIn: 2.5 GiB).  3 GiB holds the
+// whole class of an MI355X at the largest input — an eighth of what the bitmap-fed path may take (kFedMaxScratch); a larger device's or
+// a forced class of more jobs gets it only with a caller's bound that keeps it below.
+constexpr uint64_t kSizeMaxScratch = 3ull << 30;
+constexpr uint32_t kSizeMaxJobs = 65535u;            // (the chunk / tile stages' grids have one row per job)
+struct SizePlan {
+    bool try_seg;            // the latency class in front (it may still decline: no scratch from the pool — never an error)
+    uint32_t min_in;
+    bool by_len;             // its chunk / tile stages take the jobs longest input first
+    bool last;               // the one-wave kernel behind it (always, but for size_force == 2)
+    const char* seg_launch; const char* last_launch;
+};
+inline SizePlan size_plan(const Geometry& g, const Knobs& k, uint32_t n_jobs, uint64_t max_input_len) {
+    SizePlan p{};
+    const bool in_class = k.size_seg == kForced || (k.size_seg == kByRule && n_jobs <= size_seg_max_jobs(g));
+    p.min_in = k.size_seg_min_in;
+    p.try_seg = in_class && n_jobs <= kSizeMaxJobs && max_input_len >= p.min_in &&
+                size_layout(n_jobs, max_input_len).total <= kSizeMaxScratch;
+    p.by_len = seg_ranks(g, n_jobs).by_len;
+    p.last = k.size_force != 2u;
+    p.seg_launch = kLaunchSizeSeg; p.last_launch = kLaunchSizeWave;
+    return p;
 }
 
 // ---- the decompress call -----------------------------------------------------------------------------------------------------------

@@ -10,9 +10,10 @@
 // Positions are 64-bit: a block below the decoder's input limit (2 GiB) decodes to up to 255 x that, and callers pass
 // 2^63 - 1 as "no limit".
 //
-// Follow-up (one block over many wavefronts): chunk sums compose.  A chunk's run of sequences is summarised by its length
-// sum and, for the two position checks, by the largest M + L-prefix against the limit and the largest "offset minus
-// position" — both relative to the chunk's start — so a later pass that knows the start position finishes the checks.
+// One block over many wavefronts (lzf_size_tile_kernel / lzf_size_finish_kernel, lz4_decoded_size_seg.inc): sums compose.  The true
+// tokens that start in a tile of compressed bytes are summarised RELATIVE to the tile's first token (TileSum, summarise); a second
+// pass that knows every tile's base position finishes the three checks (clean).  That path only says "clean, and this long" or
+// nothing: which error a job has, and where, stays with the token-by-token walk above.
 #ifndef LZF_SIZE_RULES_H
 #define LZF_SIZE_RULES_H
 
@@ -93,6 +94,51 @@ LZF_SIZE_HD int check(uint64_t mo, uint64_t M, uint32_t off, uint64_t prefix_len
 
 // The carry from sequence to sequence (and from round to round of the kernel): output.len().
 LZF_SIZE_HD uint64_t advance(uint64_t pos, const Seq& s) { return pos + s.L + s.M; }
+
+// ---- tiles -----------------------------------------------------------------------------------------------------------------------
+// What the sequences of one tile come to, relative to output position 0 at the tile's first token:
+//   sum    the position behind the tile's last sequence (the sum of L + M); at most kTileSumMax
+//   end    the largest mo_rel + M over the sequences with a match — their ends rise, so the last match's end; 0: no match
+//   need   the largest off - mo_rel (0 where the offset stays inside the tile) over the sequences with a match: how much output the
+//          tile wants in front of itself; at most 65 535
+//   flags  kTileZeroOffset: a match with offset 0;  kTileUnsummarised: a token that could not be decoded, a length beyond kTileLenClamp
+//          or a sum beyond kTileSumMax
+// Every field only grows, so summaries of parts of a tile that share its origin combine field by field (max, max, max, or): the
+// tile kernel summarises 64 sequences at once, one per lane, and reduces with three wave maxima and a ballot.
+struct TileSum { uint32_t sum, end, need, flags; };
+enum : uint32_t { kTileZeroOffset = 1u, kTileUnsummarised = 2u };
+constexpr uint32_t kTileLenClamp = 1u << 26;          // (the segmented pipeline's kLenClamp: longer literals / matches are the one-wave kernel's)
+constexpr uint64_t kTileSumMax = 0x7FFFFFFFull;
+
+// One sequence whose first literal sits at tile-relative position `rel` into the running summary; decoded = decode_token's (or the
+// tile decoder's) verdict.  Serial use: rel = t.sum.
+LZF_SIZE_HD void summarise(TileSum& t, uint64_t rel, const Seq& s, bool decoded) {
+    if (!decoded || s.L > kTileLenClamp || s.M > (uint64_t)kTileLenClamp + 4u) { t.flags |= kTileUnsummarised; return; }
+    const uint64_t mo = rel + s.L, behind = mo + s.M;
+    if (behind > kTileSumMax) { t.flags |= kTileUnsummarised; return; }
+    if (behind > t.sum) t.sum = (uint32_t)behind;
+    if (!s.has) return;
+    if (s.off == 0u) t.flags |= kTileZeroOffset;
+    if (behind > t.end) t.end = (uint32_t)behind;
+    const uint32_t need = (uint64_t)s.off > mo ? (uint32_t)((uint64_t)s.off - mo) : 0u;
+    if (need > t.need) t.need = need;
+}
+// check()'s three tests over a tile whose first token sits at output position `base` (existing output included; 64 bits).
+// Literals are not limit-checked, as in the reference (:63-67).
+LZF_SIZE_HD bool clean(const TileSum& t, uint64_t base, uint64_t prefix_len, uint64_t output_limit) {
+    if (t.flags) return false;
+    if (t.end && base + t.end > output_limit) return false;       // :72-74
+    return (uint64_t)t.need <= base + prefix_len;                  // :83-89
+}
+// The carry from tile to tile, and a job's verdict: clean with out_existing_len + the sums — or not this path's business.
+struct Fold { uint64_t base; bool clean; };
+LZF_SIZE_HD Fold fold_begin(uint64_t existing) { return Fold{existing, true}; }
+LZF_SIZE_HD void fold(Fold& f, const TileSum& t, uint64_t prefix_len, uint64_t output_limit) {
+    f.clean = f.clean && clean(t, f.base, prefix_len, output_limit);
+    f.base += t.sum;
+}
+// (a job whose total does not fit 32 bits is left to the one-wave kernel as well)
+LZF_SIZE_HD bool fold_end(const Fold& f, uint64_t existing) { return f.clean && f.base - existing <= 0xFFFFFFFFull; }
 
 }  // namespace lzf_size
 

@@ -50,9 +50,16 @@ def decompress_batch(d_jobs, d_res, n, stream=None, max_input_len=None):
 
 def decompressed_size_batch(d_jobs, d_res, n, stream=None, max_input_len=None):
     """lzf_decompressed_size_batch: status and output.len() of every decode job without decoding it.  The same job array as
-    decompress_batch; prefix, out and out_cap of the jobs are not looked at."""
+    decompress_batch; prefix, out and out_cap of the jobs are not looked at.  max_input_len: an upper bound of the jobs' input_len; a
+    call of many small blocks should give it — without one a call of up to 16 jobs per CU takes the latency class's scratch (sized for
+    4 MiB blocks) and front stages whatever its inputs are."""
     bound = (1 << 64) - 1 if max_input_len is None else int(max_input_len)
     ffi.check(ffi.lib().lzf_decompressed_size_batch(d_jobs.data_ptr(), d_res.data_ptr(), n, bound, _stream_ptr(stream)))
+
+
+def last_size_launch():
+    """lzf_last_size_launch: what this thread's last decompressed_size_batch launched ("latency: ..." = the class of few large blocks)."""
+    return ffi.lib().lzf_last_size_launch().decode()
 
 
 def xxh32_batch(d_ptrs, d_lens, d_out, n, stream=None):

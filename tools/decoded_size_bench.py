@@ -6,14 +6,27 @@ One process on one MI355X, HIP events around every call, the calls of a pair alt
   2  the same pair over the first 20 / 4 / 1 copies (980 / 196 / 49 blocks: the README's small-call rows)
   3  --frames frames of ~10 KB of text with default settings (4 MiB blocks): lzf_frame_decompressed_size_device wall time, and
      the bytes decompress_frames_device allocates with exact=False (the bound; computed, not allocated) and exact=True
+  4  the latency class against the parent commit's library: the size call and the decode call at --counts blocks of the bench's
+     (49,196,980,2048,4096,11769), one "SWEEP" line per count with every call's time.  One process measures ONE library — the one
+     LZF_LIB_PATH names, this tree's otherwise; `--ab PARENT_LIB --runs 5` starts such processes in turns, this tree's library and
+     the parent's (built from a `git worktree` of the parent commit), and prints per count every run of both and whether every run of
+     this tree's is shorter than every run of the parent's
+  5  the class's smallest input: 256 blocks of 16, 64 and 256 KiB (text cut to size), the size call through the product's rule
+     (the class from 64 KiB on) — `--ab` alternates it with the parent's library, which has the one-wave kernel alone, and
+     `--class0 ANALYSIS_LIB` adds processes of the analysis library with LZF_SIZE_SEG_MIN_IN=0: the class at every size
+  6  a call the class cannot help: 4 096 blocks of ~500 bytes, with no bound of the inputs (max_input_len unknown: the class's front
+     runs over jobs that are all below its window, its scratch sized for 4 MiB blocks) and with the caller's bound (one-wave kernel alone)
 Under `rocprofv3 --kernel-trace --stats -- python tools/decoded_size_bench.py --cases 1` the same process gives the size kernel's
 time next to the decode's parse and seam kernels.
 
   python tools/decoded_size_bench.py [--cases 123] [--pairs 5] [--copies 240] [--distinct 12] [--frames 100000]
+  python tools/decoded_size_bench.py --cases 45 --ab /path/to/parent/liblzfear_hip.so [--runs 5] [--counts 49,196,980,2048,4096,11769]
 """
 import argparse
+import json
 import os
 import statistics
+import subprocess
 import sys
 import time
 
@@ -26,6 +39,35 @@ import torch  # noqa: E402
 
 import rust_lz_fear_amd  # noqa: E402,F401
 from rust_lz_fear_amd import device, ffi, framed, synth  # noqa: E402
+
+import ctypes  # noqa: E402
+
+
+class _OlderLibrary(ctypes.CDLL):
+    """--ab loads the parent commit's library by LZF_LIB_PATH; it has no lzf_last_size_launch, which ffi.lib() declares."""
+
+    def __getattr__(self, name):
+        try:
+            return super().__getattr__(name)
+        except AttributeError:
+            if name != "lzf_last_size_launch":
+                raise
+
+            def absent():
+                return b"(a library without lzf_last_size_launch)"
+            setattr(self, name, absent)
+            return absent
+
+
+def _load_library():
+    loader, ctypes.CDLL = ctypes.CDLL, _OlderLibrary               # (only while ffi.lib() loads and declares the library)
+    try:
+        ffi.lib()
+    finally:
+        ctypes.CDLL = loader
+
+
+_load_library()
 
 DEV = torch.device("cuda", 0)
 BS = 4 << 20
@@ -122,6 +164,125 @@ def pair_case(B, n, pairs, label):
     return max(ts) < min(td)
 
 
+def size_launch():
+    return ffi.lib().lzf_last_size_launch().decode()
+
+
+def sweep_case(B, counts, pairs):
+    """One SWEEP line per count: every timed size and decode call of this process's library."""
+    for n in counts:
+        n = min(n, B["n"])
+        d_rs = torch.zeros(n * 16, dtype=torch.uint8, device=DEV)
+        d_rd = torch.zeros(n * 16, dtype=torch.uint8, device=DEV)
+
+        def size():
+            device.decompressed_size_batch(B["jobs"], d_rs, n)
+
+        def decode():
+            device.decompress_batch(B["jobs"], d_rd, n)
+        for _ in range(2):
+            event_ms(size); event_ms(decode)
+        ts, td = [], []
+        for _ in range(pairs):
+            ts.append(event_ms(size)); td.append(event_ms(decode))
+        rs = device.results_to_host(d_rs, n)
+        assert (rs["status"] == 0).all() and np.array_equal(rs["out_len"], B["lens"][:n])
+        print("SWEEP " + json.dumps(dict(n=n, size_ms=[round(t, 3) for t in ts], decode_ms=[round(t, 3) for t in td], launch=size_launch())), flush=True)
+
+
+def min_in_case(pairs):
+    """256 blocks of 16 / 64 / 256 KiB: one MINSWEEP line each."""
+    text = synth.gen_text_zipf(23, 256 * (256 << 10)).tobytes()
+    for kib in (16, 64, 256):
+        bs = kib << 10
+        plains = [text[k * bs:(k + 1) * bs] for k in range(256)]
+        comp = ffi.compress_blocks_host([dict(input=p, out_cap=len(p)) for p in plains])
+        assert all(rc == 0 for rc, _ in comp)
+        blobs = [c for _, c in comp]
+        offs = np.cumsum([0] + [len(b) + 64 for b in blobs])
+        h = np.zeros(int(offs[-1]), dtype=np.uint8)
+        for b, a in zip(blobs, offs):
+            h[a:a + len(b)] = np.frombuffer(b, dtype=np.uint8)
+        d_in = torch.from_numpy(h).to(DEV)
+        j = np.zeros(256, dtype=device.DJOB)
+        j["input"] = np.uint64(d_in.data_ptr()) + offs[:-1].astype(np.uint64)
+        j["input_len"] = [len(b) for b in blobs]
+        j["output_limit"] = bs
+        d_j = device.to_device(j, DEV)
+        d_rs = torch.zeros(256 * 16, dtype=torch.uint8, device=DEV)
+        bound = max(len(b) for b in blobs)
+
+        def size():
+            device.decompressed_size_batch(d_j, d_rs, 256, max_input_len=bound)
+        for _ in range(2):
+            event_ms(size)
+        ts = [event_ms(size) for _ in range(pairs)]
+        rs = device.results_to_host(d_rs, 256)
+        assert (rs["status"] == 0).all() and (rs["out_len"] == bs).all()
+        print("MINSWEEP " + json.dumps(dict(block_kib=kib, max_input=bound, min_input=min(len(b) for b in blobs), size_ms=[round(t, 3) for t in ts], launch=size_launch())), flush=True)
+
+
+def tiny_case(pairs):
+    """4 096 blocks of ~500 bytes: one TINY line for the call without a bound of its inputs, one for the call with it."""
+    text = synth.gen_text_zipf(29, 4096 * 500).tobytes()
+    comp = ffi.compress_blocks_host([dict(input=text[k * 500:(k + 1) * 500], out_cap=500) for k in range(4096)])
+    blobs = [c if rc == 0 else b"\x00" for rc, c in comp]
+    offs = np.cumsum([0] + [len(b) + 16 for b in blobs])
+    h = np.zeros(int(offs[-1]), dtype=np.uint8)
+    for b, a in zip(blobs, offs):
+        h[a:a + len(b)] = np.frombuffer(b, dtype=np.uint8)
+    d_in = torch.from_numpy(h).to(DEV)
+    j = np.zeros(4096, dtype=device.DJOB)
+    j["input"] = np.uint64(d_in.data_ptr()) + offs[:-1].astype(np.uint64)
+    j["input_len"] = [len(b) for b in blobs]
+    j["output_limit"] = 500
+    d_j = device.to_device(j, DEV)
+    d_rs = torch.zeros(4096 * 16, dtype=torch.uint8, device=DEV)
+    for label, bound in (("unknown", None), ("bound", max(len(b) for b in blobs))):
+        def size():
+            device.decompressed_size_batch(d_j, d_rs, 4096, max_input_len=bound)
+        first = event_ms(size)                                     # (the first call allocates the scratch from the device)
+        event_ms(size)
+        ts = [event_ms(size) for _ in range(pairs)]
+        assert (device.results_to_host(d_rs, 4096)["status"] == 0).all()
+        print("TINY " + json.dumps(dict(block_kib=label, first_ms=round(first, 3), size_ms=[round(t, 3) for t in ts], launch=size_launch())), flush=True)
+
+
+def ab_driver(args):
+    """Processes of this tree's library and the parent's in turns; every SWEEP / MINSWEEP line collected, the verdict per count."""
+    mine = os.environ.get("LZF_LIB_PATH") or ffi.lib_path()
+    rows = {}
+    for run in range(args.runs):
+        for who, lib, extra in [("new", mine, {}), ("parent", args.ab, {})] + ([("class0", args.class0, {"LZF_SIZE_SEG_MIN_IN": "0"})] if args.class0 else []):
+            cmd = [sys.executable, os.path.abspath(__file__), "--cases", args.cases, "--pairs", str(args.pairs), "--copies", str(args.copies),
+                   "--distinct", str(args.distinct), "--counts", args.counts]
+            r = subprocess.run(cmd, env=dict(os.environ, LZF_LIB_PATH=lib, **extra), capture_output=True, text=True, timeout=args.run_timeout)
+            if r.returncode != 0:
+                print(r.stdout[-2000:] + r.stderr[-3000:])
+                sys.exit(f"run {run} of {who} failed ({r.returncode}): nothing more is started")
+            for ln in r.stdout.splitlines():
+                if ln.startswith(("SWEEP ", "MINSWEEP ", "TINY ")):
+                    kind, d = ln.split(" ", 1)
+                    d = json.loads(d)
+                    key = (kind, d.get("n", d.get("block_kib")))
+                    rows.setdefault(key, {}).setdefault(who, []).append(d)
+            print(f"run {run} {who}: done", flush=True)
+    for (kind, k), by in sorted(rows.items(), key=lambda kv: (kv[0][0], str(kv[0][1]).zfill(8))):
+        new = [t for d in by["new"] for t in d["size_ms"]]; par = [t for d in by["parent"] for t in d["size_ms"]]
+        print(f"{kind} {k}: [{by['new'][0]['launch']}]")
+        for who in by:
+            print(f"    {who:6s} size ms per run: {[d['size_ms'] for d in by[who]]}" + (f"   first call of each process: {[d['first_ms'] for d in by[who]]}" if kind == "TINY" else ""))
+        if "class0" in by:
+            c0 = [t for d in by["class0"] for t in d["size_ms"]]
+            print(f"    class0 (analysis library, LZF_SIZE_SEG_MIN_IN=0) [{by['class0'][0]['launch']}] median {statistics.median(c0):.3f}  every run shorter than every run of parent: {max(c0) < min(par)}")
+        if kind == "SWEEP":
+            print(f"    decode ms per run (new): {[d['decode_ms'] for d in by['new']]}")
+            print(f"    decode ms per run (parent): {[d['decode_ms'] for d in by['parent']]}")
+            dec = [t for d in by["new"] for t in d["decode_ms"]]
+            print(f"    size (new) median {statistics.median(new):.3f}  decode median {statistics.median(dec):.3f}  every size call shorter than every decode call: {max(new) < min(dec)}")
+        print(f"    new median {statistics.median(new):.3f}  parent median {statistics.median(par):.3f}  every run of new shorter than every run of parent: {max(new) < min(par)}", flush=True)
+
+
 def frames_case(n_frames):
     text = synth.gen_text_zipf(11, 64 << 20).tobytes()
     distinct = 4000                                            # distinct shards; the frame slots alias them
@@ -159,11 +320,24 @@ def main():
     ap.add_argument("--copies", type=int, default=240)
     ap.add_argument("--distinct", type=int, default=12)
     ap.add_argument("--frames", type=int, default=100000)
+    ap.add_argument("--counts", default="49,196,980,2048,4096,11769")
+    ap.add_argument("--ab", default=None, help="the parent commit's liblzfear_hip.so: alternate processes of the two libraries")
+    ap.add_argument("--class0", default=None, help="the analysis library: with --ab, a third kind of process with LZF_SIZE_SEG_MIN_IN=0")
+    ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--run-timeout", type=int, default=600)
     args = ap.parse_args()
+    if args.ab:
+        return ab_driver(args)
     torch.cuda.set_device(0)
     ok = True
-    if "1" in args.cases or "2" in args.cases:
+    if "5" in args.cases:
+        min_in_case(args.pairs)
+    if "6" in args.cases:
+        tiny_case(args.pairs)
+    if any(c in args.cases for c in "124"):
         B = bench_blocks(args.copies, args.distinct)
+        if "4" in args.cases:
+            sweep_case(B, [int(x) for x in args.counts.split(",")], args.pairs)
         if "1" in args.cases:
             ok = pair_case(B, B["n"], args.pairs, "1") and ok
         if "2" in args.cases:
