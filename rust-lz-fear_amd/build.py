@@ -88,7 +88,7 @@ def build_library(force=False, verbose=False, defines=(), out=None, analysis=Fal
         subprocess.check_call(cmd)
 
     if todo:
-        with ThreadPoolExecutor(max_workers=min(len(todo), os.cpu_count() or 4)) as ex:
+        with ThreadPoolExecutor(max_workers=min(len(todo), int(os.environ.get("MAX_JOBS", 0)) or os.cpu_count() or 4)) as ex:      # (MAX_JOBS: a machine that shares its CPUs)
             list(ex.map(compile_one, todo))
     objs = [o for _, o, _ in jobs]
     if todo or not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(o) for o in objs):
@@ -128,6 +128,11 @@ def build_dist_library(force=False, verbose=False):
 
 def build_analysis_library(force=False, verbose=False):
     return build_library(force=force, verbose=verbose, analysis=True)
+
+
+# The counters tests/test_gpu_copy_stage.py reads from results[].reserved: the pair kernel's match rounds with the fed kernel's batches, and the
+# pair kernel's batches.  Two instrumented analysis builds, made with the others so that the GPU tests find them built.
+COUNTER_BUILDS = (("LZF_DBG_ROUNDS=1", "LZF_DBG_FED_COUNT=0"), ("LZF_DBG_ROUNDS=2",))
 
 
 if __name__ == "__main__":

@@ -48,6 +48,14 @@ def main():
     comp = o.compress2(dic + payload, cursor=len(dic))[1]
     r = ffi.decompress_blocks_host([dict(input=comp, prefix=dic, limit=len(payload)), dict(input=comp, existing=dic, limit=len(d))])
     assert r[0] == (0, payload) and r[1] == (0, d)
+    # ... and two built blocks of the copy stage's census (copy_stage_cases.py): prefix matches of every kind, once in front of an empty output,
+    # once behind existing output one byte longer than the ring
+    import copy_stage_cases as K
+    built = {c["name"]: c for c in K.cases("paired48", 0)}
+    for name in ("prefix: existing_len 0", "prefix: existing_len 4097"):
+        c = built[name]
+        (rc, got), = ffi.decompress_blocks_host([dict(input=c["input"], prefix=c["prefix"], existing=c["existing"], limit=c["limit"], out_cap=c["cap"])])
+        assert rc == 0 and got == c["output"], (name, rc)
     # handcrafted streams (rare kernel paths)
     for seed, n, prof in [(11, 4000, "dense"), (12, 2000, "mixed"), (13, 200, "long"), (14, 1500, "rle")]:
         blk, out = vectors.synth_stream(seed, n, prof)
