@@ -6,6 +6,7 @@
 #include "capi_internal.h"
 #include <cstdlib>
 #include "kernels.h"
+#include "capi_order.h"
 
 namespace lzf_capi __attribute__((visibility("hidden"))) {
 namespace d = lzf_dispatch;
@@ -130,9 +131,9 @@ int compress_launches(const d::CompressPlan& p, const lzf_compress_job* d_jobs, 
         lzf_compress_job* probes = reinterpret_cast<lzf_compress_job*>(scratch.at(probes_off));
         lzf_job_result* pres = reinterpret_cast<lzf_job_result*>(scratch.at(res_off));
         perm = reinterpret_cast<uint32_t*>(scratch.at(perm_off));
-        LAUNCH(lzf::lzf_cost_probe_jobs_kernel, dim3((uint32_t)((n_probes + 255u) / 256u)), dim3(256), 0, st, d_jobs, probes, n_jobs, piece, parts);
-        LAUNCH(k_compact_dry, dim3((uint32_t)n_probes), dim3(64), 0, st, probes, pres, (uint32_t)n_probes, (const uint32_t*)nullptr, 0u);
-        LAUNCH(lzf::lzf_order_by_cost_kernel, dim3(1), dim3(1024), 0, st, d_jobs, pres, perm, n_jobs, piece, parts);
+        int rc = launch_cost_probes(d_jobs, probes, pres, n_jobs, piece, parts, st);
+        if (rc == LZF_OK) rc = launch_order_by_cost(d_jobs, pres, perm, n_jobs, piece, parts, st);
+        if (rc != LZF_OK) return rc;
     }
     const uint32_t alone = p.fresh_only ? 1u : 0u;
     if (p.kinds & LZF_KINDS_U32) {
@@ -168,9 +169,8 @@ int decompress_launches(Device& dv, const d::DecompressPlan& p, const lzf_decomp
     auto order_by_sampling = [&]() -> int {
         if (!perm || ordered) return LZF_OK;
         ordered = true;
-        LAUNCH(lzf::lzf_decompress_cost_kernel, dim3(n_jobs), dim3(64), 0, st, d_jobs, n_jobs, est, kn.order_len_shift);
-        LAUNCH(lzf::lzf_order_by_estimate_kernel, dim3(1), dim3(1024), 0, st, (const uint32_t*)est, perm, n_jobs);
-        return LZF_OK;
+        const int rc = launch_decompress_cost(d_jobs, n_jobs, est, kn.order_len_shift, st);
+        return rc == LZF_OK ? launch_order_by_estimate(est, perm, n_jobs, st) : rc;
     };
     const uint32_t* const cperm = perm;
     int rc = LZF_OK;
@@ -288,7 +288,7 @@ int lzf_decompressed_size_batch(const lzf_decompress_job* d_jobs, lzf_job_result
     HIP_TRY(hipMallocAsync(&ticket.p, 256 + (ordered ? sizeof(uint32_t) * (size_t)n_jobs : 0u), st));
     HIP_TRY(hipMemsetAsync(ticket.p, 0, 4, st));
     uint32_t* const perm = ordered ? static_cast<uint32_t*>(ticket.p) + 64 : nullptr;
-    if (ordered) LAUNCH(lzf::lzf_order_by_input_len_kernel, dim3(1), dim3(1024), 0, st, d_jobs, perm, n_jobs);
+    if (ordered && (rc = launch_order_by_input_len(d_jobs, perm, n_jobs, st)) != LZF_OK) return rc;
     const uint32_t grid = n_jobs < room ? n_jobs : (uint32_t)room;
     if (done) LAUNCH(k_size_skip, dim3(grid), dim3(64), 0, st, d_jobs, d_results, n_jobs, static_cast<uint32_t*>(ticket.p), (const uint32_t*)perm, done);
     else LAUNCH(k_size, dim3(grid), dim3(64), 0, st, d_jobs, d_results, n_jobs, static_cast<uint32_t*>(ticket.p), (const uint32_t*)perm, (const lzf::seg_job*)nullptr);

@@ -3,6 +3,7 @@
 // call comes here at all, with which ring and in which groups, is decided there.
 #include "capi_internal.h"
 #include "kernels.h"
+#include "capi_order.h"
 
 namespace lzf_capi __attribute__((visibility("hidden"))) {
 namespace {
@@ -237,19 +238,31 @@ FedCensus fed_census(Device& dev, hipStream_t st) {
 }
 }  // namespace
 
+// The front of a fed call, in the scratch `mem` holds: plan + parse over the whole batch and, when an order is asked for (est not
+// null), the launch order from the estimates the two stages leave in est[].  *ctx = the context the stages ran with.
+int fed_front(const d::Geometry& geo, const lzf_decompress_job* d_jobs, lzf_job_result* d_results, uint32_t n, const d::FedLayout& l, const AsyncScratch& mem,
+              uint32_t min_in, uint32_t len_shift, uint32_t* perm, uint32_t* est, hipStream_t st, lzf::seg_ctx* ctx) {
+    lzf::seg_ctx& c = *ctx;
+    c = seg_ctx_of(geo, d_jobs, d_results, n, l.d, min_in, mem, l.o_st, l.o_top, l.o_bits);
+    c.fed = 1u; c.est = perm ? est : nullptr; c.len_shift = len_shift;
+    int rc = seg_launch(c, 2u, st);                              // plan, parse
+    if (rc == LZF_OK && c.est) rc = launch_order_by_estimate(est, perm, n, st);
+    return rc;
+}
+
 // scratch, plan + parse, the launch order, reset, the fed kernel, the pair kernel, scratch back.
 // perm + est (both or neither): the launch order is wanted and nobody has worked it out yet — est[] is filled here, by the plan stage
-// (the bytes' share) and the parse (the sequences: exact, where lzf_decompress_cost_kernel samples), and perm[] ordered by it.
+// (the bytes' share) and the parse (the sequences: counted, where lzf_decompress_cost_kernel samples — the block's exact number when every
+// chunk's chain falls in step with the block's inside its overlap, marks off the chain included otherwise: tests/launch_order_cases.py), and
+// perm[] ordered by it.
 int fed_decompress(Device& dv, const lzf_decompress_job* d_jobs, lzf_job_result* d_results, uint32_t n, uint32_t* perm, uint32_t* est, hipStream_t st, bool* used, uint64_t max_in_hint) {
     const d::Knobs& kn = knobs();
     const d::FedLayout l = d::fed_layout(n, max_in_hint);
     AsyncScratch mem(st);
     *used = mem.alloc(l.total);
     if (!*used) return LZF_OK;                                   // (no room for the bit maps: the pair kernel takes the call, the order is still to make)
-    lzf::seg_ctx c = seg_ctx_of(dv.geo, d_jobs, d_results, n, l.d, kn.fed_min_in, mem, l.o_st, l.o_top, l.o_bits);
-    c.fed = 1u; c.est = perm ? est : nullptr; c.len_shift = kn.order_len_shift;
-    int rc = seg_launch(c, 2u, st);                              // plan, parse
-    if (rc == LZF_OK && c.est) LAUNCH_RC(rc, lzf::lzf_order_by_estimate_kernel, dim3(1), dim3(1024), 0, st, (const uint32_t*)est, perm, n);
+    lzf::seg_ctx c{};
+    int rc = fed_front(dv.geo, d_jobs, d_results, n, l, mem, kn.fed_min_in, kn.order_len_shift, perm, est, st, &c);
     if (rc == LZF_OK) {
         // The kernel runs as one wavefront per SLOT — as many as the device holds at once — and the slots share the jobs out in pieces
         // (lz4_decompress_fed.hip): a call with more jobs than slots cuts every job into 16 (measured at 2.2 jobs per slot: 107.4 ms whole,
@@ -296,5 +309,66 @@ int lzf_debug_seg(const lzf_decompress_job* d_jobs, lzf_job_result* d_results, u
     if (h_recs) { uint64_t nb = sizeof(lzf::u32x4) * c.rec_cap; if (nb > recs_bytes) nb = recs_bytes; HIP_TRY(hipMemcpy(h_recs, c.recs, nb, hipMemcpyDeviceToHost)); }
     HIP_TRY(s.mem.release());
     return rc;
+}
+
+// Analysis only: one piece of the launch-order stage on its own, on the default stream, through the launch lines the batch calls use
+// (capi_order.h, fed_front above); the results are copied to host buffers.  d_jobs is a device array of n jobs, h_* are host buffers.
+//   what 0  lzf_order_by_estimate_kernel over h_in = est[n]                                         -> h_perm[n]
+//        1  lzf_order_by_input_len_kernel over d_jobs (decompress jobs; only input_len is read)      -> h_perm[n]
+//        2  lzf_order_by_cost_kernel over d_jobs (compress jobs), h_in = lzf_job_result[n * b],
+//           a = piece, b = parts                                                                     -> h_perm[n]
+//        3  lzf_decompress_cost_kernel over d_jobs, a = len_shift                                    -> h_est[n]
+//        4  the front of fed_decompress over d_jobs: scratch, plan + parse with fed = 1 and est set,
+//           a = min_in, b = len_shift, then the order; no fed kernel, no pair kernel                 -> h_est[n], h_perm[n]
+//        5  lzf_cost_probe_jobs_kernel over d_jobs (compress jobs) and the dry run of the probes,
+//           a = piece, b = parts                     -> h_probes = lzf_compress_job[n * b], h_probe_results = lzf_job_result[n * b]
+extern "C"
+int lzf_debug_order(uint32_t what, const void* d_jobs, uint32_t n, const void* h_in, uint32_t a, uint32_t b,
+                    uint32_t* h_est, uint32_t* h_perm, void* h_probes, void* h_probe_results) {
+    int rc = ensure_device();
+    if (rc < 0) return rc;
+    if (n == 0 || what > 5u || (what >= 1u && !d_jobs) || ((what == 0u || what == 2u) && !h_in) || ((what == 2u || what == 5u) && (!a || !b))) return LZF_E_INVALID;
+    const size_t n_probes = (size_t)n * (what == 2u || what == 5u ? b : 0u);
+    // [est or the caller's est][perm][probe jobs][probe results][results of the fed front]
+    d::Carver cv;
+    const uint64_t o_est = cv.take(4ull * n), o_perm = cv.take(4ull * n), o_probes = cv.take(sizeof(lzf_compress_job) * n_probes),
+                   o_pres = cv.take(sizeof(lzf_job_result) * n_probes), o_res = cv.take(sizeof(lzf_job_result) * (what == 4u ? n : 0u));
+    AsyncScratch buf(nullptr), fed_mem(nullptr);
+    if (!buf.alloc(cv.off + 256u)) return LZF_E_HIP;
+    uint32_t* const est = area<uint32_t>(buf, o_est);
+    uint32_t* const perm = area<uint32_t>(buf, o_perm);
+    lzf_compress_job* const probes = area<lzf_compress_job>(buf, o_probes);
+    lzf_job_result* const pres = area<lzf_job_result>(buf, o_pres);
+    const lzf_decompress_job* const dj = static_cast<const lzf_decompress_job*>(d_jobs);
+    const lzf_compress_job* const cj = static_cast<const lzf_compress_job*>(d_jobs);
+    hipStream_t st = nullptr;
+    rc = LZF_OK;
+    if (what == 0u) {
+        HIP_TRY(hipMemcpy(est, h_in, 4ull * n, hipMemcpyHostToDevice));
+        rc = launch_order_by_estimate(est, perm, n, st);
+    } else if (what == 1u) {
+        rc = launch_order_by_input_len(dj, perm, n, st);
+    } else if (what == 2u) {
+        HIP_TRY(hipMemcpy(pres, h_in, sizeof(lzf_job_result) * n_probes, hipMemcpyHostToDevice));
+        rc = launch_order_by_cost(cj, pres, perm, n, a, b, st);
+    } else if (what == 3u) {
+        rc = launch_decompress_cost(dj, n, est, a, st);
+    } else if (what == 4u) {
+        const d::FedLayout l = d::fed_layout(n, ~0ull);
+        if (!fed_mem.alloc(l.total)) return LZF_E_HIP;
+        lzf::seg_ctx c{};
+        rc = fed_front(device().geo, dj, area<lzf_job_result>(buf, o_res), n, l, fed_mem, a, b, perm, est, st, &c);
+    } else {
+        rc = launch_cost_probes(cj, probes, pres, n, a, b, st);
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    if (rc != LZF_OK) return rc;
+    if (h_est && (what == 3u || what == 4u)) HIP_TRY(hipMemcpy(h_est, est, 4ull * n, hipMemcpyDeviceToHost));
+    if (h_perm && what != 3u && what != 5u) HIP_TRY(hipMemcpy(h_perm, perm, 4ull * n, hipMemcpyDeviceToHost));
+    if (h_probes && what == 5u) HIP_TRY(hipMemcpy(h_probes, probes, sizeof(lzf_compress_job) * n_probes, hipMemcpyDeviceToHost));
+    if (h_probe_results && what == 5u) HIP_TRY(hipMemcpy(h_probe_results, pres, sizeof(lzf_job_result) * n_probes, hipMemcpyDeviceToHost));
+    HIP_TRY(fed_mem.release());
+    HIP_TRY(buf.release());
+    return LZF_OK;
 }
 #endif

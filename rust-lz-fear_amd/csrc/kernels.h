@@ -118,8 +118,8 @@ struct seg_ctx {
     uint32_t g_off, g_n, grouped;
     uint32_t res_prio;           // the resolve stage's wavefronts raise their issue priority (grouped calls: they share their SIMDs with the next group's records stage)
     uint32_t fed;                // the plan / parse stages serve the bitmap-fed kernel: prefix and existing output do not make a job ineligible, no xexit is stored
-    // the launch order of a fed call (capi_drivers.hip): est[j] = the job's cost, written by the plan stage (input_len >> len_shift; a guess by
-    // length for a job the map does not cover) and counted up by the parse (every chunk adds the tokens it owns).  null: no order asked for
+    // the launch order of a fed call (capi_drivers.hip): est[j] = the job's cost, written by the plan stage (input_len >> len_shift; plus a guess by
+    // length, input_len >> 4, for a job the map does not cover) and counted up by the parse (every chunk adds the tokens it owns).  null: no order asked for
     uint32_t* est;
     uint32_t len_shift;
     // the size call's latency class (lz4_decoded_size_seg.inc): plan, parse and seam serve lzf_size_tile_kernel / lzf_size_finish_kernel.

@@ -163,7 +163,9 @@ __global__ __launch_bounds__(256) void lzf_seg_plan_kernel(seg_ctx c) {
     if (s.nch > c.maxch || s.ntile > c.maxtile) { s.eligible = 0; s.nch = 0; s.ntile = 0; }
     c.st[j] = s;
     // the launch order of a fed call: the bytes' share of the job's cost; the parse adds the sequences, chunk by chunk.  A job the
-    // map does not cover gets a guess by its length (what lzf_decompress_cost_kernel says of an input too short to sample).
+    // map does not cover gets a guess by its length in their place: input_len >> 4, the guess lzf_decompress_cost_kernel makes for an
+    // input too short to sample — here WITH the bytes' share on top, as every other job of the call has it (that kernel's short path
+    // leaves the share out: tests/launch_order_cases.py models both as they are).
     if (c.est) {
         const uint32_t l31 = job.input_len > 0x7FFFFFFFull ? 0x7FFFFFFFu : (uint32_t)job.input_len;
         c.est[j] = (s.eligible ? 0u : l31 >> 4) + (c.len_shift < 32u ? l31 >> c.len_shift : 0u);
