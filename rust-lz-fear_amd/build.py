@@ -133,6 +133,9 @@ def build_analysis_library(force=False, verbose=False):
 # The counters tests/test_gpu_copy_stage.py reads from results[].reserved: the pair kernel's match rounds with the fed kernel's batches, and the
 # pair kernel's batches.  Two instrumented analysis builds, made with the others so that the GPU tests find them built.
 COUNTER_BUILDS = (("LZF_DBG_ROUNDS=1", "LZF_DBG_FED_COUNT=0"), ("LZF_DBG_ROUNDS=2",))
+# The analysis flavour with the parse kernel's plain-hop loop in C++ instead of hand-written assembly: tests/test_gpu_parse_hop.py
+# compares its bit maps with the product loop's, word for word.
+PARSE_TWIN_BUILD = ("LZF_ANALYSIS", "LZF_SEG_NOASM")
 
 
 if __name__ == "__main__":

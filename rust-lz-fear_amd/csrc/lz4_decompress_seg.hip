@@ -185,19 +185,25 @@ __global__ __launch_bounds__(256) void lzf_seg_plan_kernel(seg_ctx c) {
 // first literal-length extension byte, ...].  Tokens a plain hop cannot express (0xFF length bytes, the last 24 bytes of
 // the input) go through the general routine.
 // -DLZF_DBG_PARSE_TIME (analysis): cycles of a parse wave by section, summed over the launch — 0 staging (loads issued and waited for,
-// LDS stores), 1 pass 0, 2 the fixed-point passes, 3 the rows written out; [4] chunks, [5] workgroups that had one.
+// LDS stores), 1 pass 0, 2 the fixed-point passes, 3 the rows written out; [4] chunks, [5] workgroups that had one; [6] / [7] the hops the
+// wave made in the plain-hop loop (one per half of a trip: a count kept by the scalar unit inside the loop) in pass 0 / in the fixed-point passes.
 // lzf_debug_parse_timers() reads (and clears) the sums: tools/parse_staging.py.
 #ifdef LZF_DBG_PARSE_TIME
-__device__ unsigned long long lzf_dbg_parse_cycles[6];
-#define PT_START() long long pt_t = clock64(); unsigned long long pt[4] = {0, 0, 0, 0}; uint32_t pt_n = 0
+__device__ unsigned long long lzf_dbg_parse_cycles[8];
+#define PT_START() long long pt_t = clock64(); unsigned long long pt[4] = {0, 0, 0, 0}; uint32_t pt_n = 0, pt_hops[2] = {0, 0}
 #define PT_MARK(i) do { const long long tn_ = clock64(); pt[i] += (unsigned long long)(tn_ - pt_t); pt_t = tn_; } while (0)
 #define PT_CHUNK() (++pt_n)
+#define PT_HOP_ASM "s_add_u32 %[nh], %[nh], 1\n\t"
+#define PT_HOPS(mode, n) (pt_hops[mode] += (n))
 #define PT_REPORT() do { if (lane == 0u && pt_n) { for (int i_ = 0; i_ < 4; ++i_) atomicAdd(&lzf_dbg_parse_cycles[i_], pt[i_]); \
-                                                     atomicAdd(&lzf_dbg_parse_cycles[4], (unsigned long long)pt_n); atomicAdd(&lzf_dbg_parse_cycles[5], 1ull); } } while (0)
+                                                     atomicAdd(&lzf_dbg_parse_cycles[4], (unsigned long long)pt_n); atomicAdd(&lzf_dbg_parse_cycles[5], 1ull); \
+                                                     atomicAdd(&lzf_dbg_parse_cycles[6], (unsigned long long)pt_hops[0]); atomicAdd(&lzf_dbg_parse_cycles[7], (unsigned long long)pt_hops[1]); } } while (0)
 #else
 #define PT_START() do { } while (0)
 #define PT_MARK(i) do { } while (0)
 #define PT_CHUNK() do { } while (0)
+#define PT_HOP_ASM ""
+#define PT_HOPS(mode, n) do { } while (0)
 #define PT_REPORT() do { } while (0)
 #endif
 __global__ __launch_bounds__(64) void lzf_seg_parse_kernel(seg_ctx c) {
@@ -272,133 +278,166 @@ __global__ __launch_bounds__(64) void lzf_seg_parse_kernel(seg_ctx c) {
                 // ---- plain hops, hand-scheduled (the walks are chains of dependent instructions: every one counts; hipcc's version of
                 //      this loop spends ~20 scalar instructions per hop on lane masks).  A lane is in the loop while it is in EXEC and leaves it
                 //      for good when its hop is not a plain one: past the stop position, parked for the general routine, on a token marked in
-                //      row A (mode 1), or because the previous token's match length turned out to go on (0xFF extension byte: r steps back
-                //      to that token, which the general routine then takes).  21 vector instructions per hop (mode 1: 26; 34 / 40 with the
-                //      lanes' state in selects instead of EXEC).  mxp = the byte in front of the token that means "not plain": 0xFF when the
-                //      previous token's match nibble was 15, else 0x100 (no byte has that value).
+                //      row A (mode 1), or because the previous token's match length turned out to go on (0xFF extension byte: the lane steps
+                //      back to that token, which the general routine then takes).
+                //      TWO hops per trip, the halves with the roles of the two position registers swapped: the first half hops from r, with
+                //      the token before it in q, and writes the next position over q; the second half hops from q with r before it and
+                //      writes r.  No register is copied, and every other back-edge is an s_cbranch_execz that is not taken as a rule.
+                //      A lane's position when it leaves is the register its last hop STARTED from: a hop that is not plain does not move, and
+                //      the step back selects the other register into it first.  (The other register is NOT the same position then: the
+                //      next-position add has already written it when the stop compare takes the lane out.)  Which register that is stands
+                //      in bit 16 of mxp: each half writes mxp, with its own bit 16, before the first compare that lets a lane go, so the bit
+                //      always names the register of the half the lane left in.  Behind the loop r is taken from q where the bit is set;
+                //      nothing else of the loop's state is read after it.
+                //      Nothing inside a trip goes through the scalar unit but the wait and the two branches: the step back leaves with the
+                //      stop compare, which sees ~0 in its place.  19 vector + 2 LDS instructions per hop (mode 1: 23 + 3).
+                //      mxp (low half) = the byte in front of the token that means "not plain": 0xFF when the previous token's match
+                //      nibble was 15, else 0x100 (no byte has that value).
                 {
-                    uint32_t mxp = 0x100u, rprev = r, mg = merged ? 1u : 0u;
+                    // (the registers the loop writes are early-clobber: mxp starts as 0x100, and an input of the same value — v100 — would
+                    //  otherwise share its register, which turns the select that writes mxp into "0xFF or what it was")
+                    uint32_t mxp = 0x100u, q = r, mg = merged ? 1u : 0u;
                     const uint32_t stopv = stop;
                     const unsigned long long m0 = __ballot(go && !merged && r < stop);
-                    uint32_t a_, w_, t_, x_, rn_, mk_;
-                    unsigned long long sv, sc;
+                    uint32_t a_, w_, t_, x_, y_, bit_, mk_;
+                    unsigned long long sv, sc, sb;
+                    uint32_t nh = 0;                       // (LZF_DBG_PARSE_TIME: hops of the wave)
                     // row word of position r: rows[(r >> 5) - 8 * lane][lane] = rowsA + ((r >> 5) << 8) + 4 * lane - (lane << 11)  (mod 2^32)
                     const uint32_t rowa2 = lds_addr(rowsA) + lane * 4u - (lane << 11), rowd = lds_addr(rowsB) - lds_addr(rowsA);
-                    const uint32_t vzero = 0u, vff = 0xFFu, v100 = 0x100u;
+                    const uint32_t vzero = 0u, vff = 0xFFu, v100 = 0x100u, vffq = 0x100FFu, v100q = 0x10100u, vf00 = 0xF00u;     // (registers: a literal beside a mask is one constant too many)
+                    // one hop from P with the token before it in Q; the next position goes to Q.  C100 / VFF: the two values of mxp this half writes.
+                    // The match nibble's compare goes to an SGPR pair of its own and the literal nibble's to vcc, each standing between
+                    // the other and its readers: no select reads a mask in the two issue slots behind the compare that wrote it.  The
+                    // mark's address is worked out behind the last compare that writes EXEC, on the way to the branch.
+#define SEG_HOP_STEP_BACK(P, Q, L) \
+                            "s_waitcnt lgkmcnt(0)\n\t" \
+                            "v_cmp_ne_u32_sdwa vcc, %[w], %[mxp] src0_sel:BYTE_0 src1_sel:WORD_0\n\t"   /* no step back */ \
+                            "v_and_b32 %[a], 0xf00, %[w]\n\t" \
+                            "v_bfe_u32 " L ", %[w], 12, 4\n\t" \
+                            "v_cndmask_b32 %[t], -1, " P ", vcc\n\t"                                   /* what the stop compare sees */ \
+                            "v_cndmask_b32 " P ", " Q ", " P ", vcc\n\t"
+#define SEG_HOP_NEXT(P, Q, C100, VFF, L) \
+                            "v_cmp_eq_u32_e64 %[sb], %[a], %[vf00]\n\t"                                /* match nibble 15 */ \
+                            "v_cmp_eq_u32 vcc, 15, " L "\n\t"                                          /* literal nibble 15 */ \
+                            "v_lshlrev_b32 %[bit], " P ", 1\n\t" \
+                            "v_cndmask_b32_e64 %[mxp], " C100 ", " VFF ", %[sb]\n\t" \
+                            "v_addc_co_u32 " Q ", %[sc], 3, " P ", %[sb]\n\t"                          /* token, offset, the match extension byte */ \
+                            "v_cmpx_lt_u32_e64 %[sc], %[t], %[stop]\n\t"                               /* (vcc stays) */
+#define SEG_HOP_LITERALS(Q, L) \
+                            "v_cndmask_b32_sdwa %[a], %[vz], %[w], vcc dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2\n\t" \
+                            "v_addc_co_u32 " L ", vcc, " L ", %[a], vcc\n\t" \
+                            "v_add_u32 " Q ", " Q ", " L "\n\t"
+#define SEG_HOP_PARK(Q) \
+                            "v_cmpx_ne_u32 vcc, 0xff, %[a]\n\t"                                        /* 0xFF extension of the literal length: parked */ \
+                            "v_cmpx_gt_u32 vcc, %[fe], " Q "\n\t"
+#define SEG_HOP0(P, Q, C100, VFF) \
+                            PT_HOP_ASM \
+                            "v_add_u32 %[a], %[cbm1], " P "\n\t" \
+                            "ds_read_b32 %[w], %[a]\n\t" \
+                            SEG_HOP_STEP_BACK(P, Q, "%[x]") \
+                            SEG_HOP_NEXT(P, Q, C100, VFF, "%[x]") \
+                            SEG_HOP_LITERALS(Q, "%[x]") \
+                            SEG_HOP_PARK(Q) \
+                            "v_lshrrev_b32 %[x], 5, " P "\n\t" \
+                            "v_lshl_add_u32 %[x], %[x], 8, %[rowa2]\n\t" \
+                            "ds_or_b32 %[x], %[bit]\n\t"
+#define SEG_HOP1(P, Q, C100, VFF) \
+                            PT_HOP_ASM \
+                            "v_add_u32 %[a], %[cbm1], " P "\n\t" \
+                            "v_lshrrev_b32 %[x], 5, " P "\n\t" \
+                            "ds_read_b32 %[w], %[a]\n\t" \
+                            "v_lshl_add_u32 %[x], %[x], 8, %[rowa2]\n\t" \
+                            "ds_read_b32 %[mk], %[x]\n\t" \
+                            SEG_HOP_STEP_BACK(P, Q, "%[y]") \
+                            "v_bfe_u32 %[mk], %[mk], " P ", 1\n\t" \
+                            SEG_HOP_NEXT(P, Q, C100, VFF, "%[y]") \
+                            "v_or_b32 %[mg], %[mg], %[mk]\n\t"                                         /* below the stop position on a token of the pass-0 chain: merged */ \
+                            SEG_HOP_LITERALS(Q, "%[y]") \
+                            "v_cmpx_eq_u32 vcc, 0, %[mk]\n\t" \
+                            SEG_HOP_PARK(Q) \
+                            "v_add_u32 %[x], %[x], %[rowd]\n\t"                                        /* the same word of row B */ \
+                            "ds_or_b32 %[x], %[bit]\n\t"
                     if (mode == 0) {
                         asm volatile(
                             "s_mov_b64 %[sv], exec\n\t"
                             "s_and_b64 exec, exec, %[m0]\n\t"
                             "s_cbranch_execz Ld%=\n"
                             "Lw%=:\n\t"
-                            "v_add_u32 %[a], %[cbm1], %[r]\n\t"
-                            "ds_read_b32 %[w], %[a]\n\t"
-                            "s_waitcnt lgkmcnt(0)\n\t"
-                            "v_cmp_eq_u32_sdwa vcc, %[w], %[mxp] src0_sel:BYTE_0 src1_sel:DWORD\n\t"
-                            "v_cndmask_b32 %[r], %[r], %[rprev], vcc\n\t"
-                            "s_andn2_b64 exec, exec, vcc\n\t"
-                            "v_cmpx_lt_u32 vcc, %[r], %[stop]\n\t"
-                            "v_bfe_u32 %[x], %[w], 12, 4\n\t"
-                            "v_cmp_eq_u32 vcc, 15, %[x]\n\t"
-                            "v_cndmask_b32_sdwa %[t], %[vz], %[w], vcc dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2\n\t"
-                            "v_addc_co_u32 %[rn], vcc, %[x], %[t], vcc\n\t"
-                            "v_add3_u32 %[rn], %[rn], %[r], 3\n\t"
-                            "v_and_b32 %[t], 0xfff000, %[w]\n\t"
-                            "v_cmpx_ne_u32 vcc, 0xfff000, %[t]\n\t"
-                            "v_and_b32 %[x], 0xf00, %[w]\n\t"
-                            "v_cmp_eq_u32 vcc, 0xf00, %[x]\n\t"
-                            "v_addc_co_u32 %[rn], %[sc], 0, %[rn], vcc\n\t"
-                            "v_cndmask_b32 %[mxp], %[v100], %[vff], vcc\n\t"
-                            "v_cmpx_gt_u32 vcc, %[fe], %[rn]\n\t"
-                            "v_lshrrev_b32 %[x], 5, %[r]\n\t"
-                            "v_lshl_add_u32 %[x], %[x], 8, %[rowa2]\n\t"
-                            "v_lshlrev_b32 %[a], %[r], 1\n\t"
-                            "ds_or_b32 %[x], %[a]\n\t"
-                            "v_mov_b32 %[rprev], %[r]\n\t"
-                            "v_mov_b32 %[r], %[rn]\n\t"
+                            SEG_HOP0("%[r]", "%[q]", "%[v100]", "%[vff]")
+                            "s_cbranch_execz Ld%=\n\t"
+                            SEG_HOP0("%[q]", "%[r]", "%[v100q]", "%[vffq]")
                             "s_cbranch_execnz Lw%=\n"
                             "Ld%=:\n\t"
                             "s_mov_b64 exec, %[sv]"
-                            : [r] "+v"(r), [rprev] "+v"(rprev), [mxp] "+v"(mxp),
-                              [a] "=&v"(a_), [w] "=&v"(w_), [t] "=&v"(t_), [x] "=&v"(x_), [rn] "=&v"(rn_), [sv] "=&s"(sv), [sc] "=&s"(sc)
-                            : [cbm1] "s"(cbuf_a - 1u), [fe] "s"(fe), [stop] "v"(stopv), [rowa2] "v"(rowa2), [vz] "v"(vzero), [vff] "v"(vff), [v100] "v"(v100), [m0] "s"(m0)
-                            : "vcc", "memory");
+                            : [r] "+&v"(r), [q] "+&v"(q), [mxp] "+&v"(mxp),
+                              [a] "=&v"(a_), [w] "=&v"(w_), [t] "=&v"(t_), [x] "=&v"(x_), [bit] "=&v"(bit_), [sv] "=&s"(sv), [sc] "=&s"(sc), [sb] "=&s"(sb), [nh] "+s"(nh)
+                            : [cbm1] "s"(cbuf_a - 1u), [fe] "s"(fe), [stop] "v"(stopv), [rowa2] "v"(rowa2), [vz] "v"(vzero), [vff] "v"(vff), [v100] "v"(v100), [vffq] "v"(vffq), [v100q] "v"(v100q), [vf00] "v"(vf00), [m0] "s"(m0)
+                            : "vcc", "scc", "memory");
                     } else {
                         asm volatile(
                             "s_mov_b64 %[sv], exec\n\t"
                             "s_and_b64 exec, exec, %[m0]\n\t"
                             "s_cbranch_execz Ld%=\n"
                             "Lw%=:\n\t"
-                            "v_add_u32 %[a], %[cbm1], %[r]\n\t"
-                            "v_lshrrev_b32 %[x], 5, %[r]\n\t"
-                            "ds_read_b32 %[w], %[a]\n\t"
-                            "v_lshl_add_u32 %[x], %[x], 8, %[rowa2]\n\t"
-                            "ds_read_b32 %[mk], %[x]\n\t"
-                            "s_waitcnt lgkmcnt(0)\n\t"
-                            "v_cmp_eq_u32_sdwa vcc, %[w], %[mxp] src0_sel:BYTE_0 src1_sel:DWORD\n\t"
-                            "v_cndmask_b32 %[r], %[r], %[rprev], vcc\n\t"
-                            "s_andn2_b64 exec, exec, vcc\n\t"
-                            "v_cmpx_lt_u32 vcc, %[r], %[stop]\n\t"
-                            "v_lshrrev_b32 %[mk], %[r], %[mk]\n\t"
-                            "v_and_b32 %[mk], 1, %[mk]\n\t"
-                            "v_or_b32 %[mg], %[mg], %[mk]\n\t"                 /* on a token of the pass-0 chain: merged */
-                            "v_cmpx_eq_u32 vcc, 0, %[mk]\n\t"
-                            "v_bfe_u32 %[mk], %[w], 12, 4\n\t"
-                            "v_cmp_eq_u32 vcc, 15, %[mk]\n\t"
-                            "v_cndmask_b32_sdwa %[t], %[vz], %[w], vcc dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2\n\t"
-                            "v_addc_co_u32 %[rn], vcc, %[mk], %[t], vcc\n\t"
-                            "v_add3_u32 %[rn], %[rn], %[r], 3\n\t"
-                            "v_and_b32 %[t], 0xfff000, %[w]\n\t"
-                            "v_cmpx_ne_u32 vcc, 0xfff000, %[t]\n\t"
-                            "v_and_b32 %[mk], 0xf00, %[w]\n\t"
-                            "v_cmp_eq_u32 vcc, 0xf00, %[mk]\n\t"
-                            "v_addc_co_u32 %[rn], %[sc], 0, %[rn], vcc\n\t"
-                            "v_cndmask_b32 %[mxp], %[v100], %[vff], vcc\n\t"
-                            "v_cmpx_gt_u32 vcc, %[fe], %[rn]\n\t"
-                            "v_add_u32 %[x], %[x], %[rowd]\n\t"                 /* the same word of row B */
-                            "v_lshlrev_b32 %[a], %[r], 1\n\t"
-                            "ds_or_b32 %[x], %[a]\n\t"
-                            "v_mov_b32 %[rprev], %[r]\n\t"
-                            "v_mov_b32 %[r], %[rn]\n\t"
+                            SEG_HOP1("%[r]", "%[q]", "%[v100]", "%[vff]")
+                            "s_cbranch_execz Ld%=\n\t"
+                            SEG_HOP1("%[q]", "%[r]", "%[v100q]", "%[vffq]")
                             "s_cbranch_execnz Lw%=\n"
                             "Ld%=:\n\t"
                             "s_mov_b64 exec, %[sv]"
-                            : [r] "+v"(r), [rprev] "+v"(rprev), [mxp] "+v"(mxp), [mg] "+v"(mg),
-                              [a] "=&v"(a_), [w] "=&v"(w_), [t] "=&v"(t_), [x] "=&v"(x_), [rn] "=&v"(rn_), [mk] "=&v"(mk_), [sv] "=&s"(sv), [sc] "=&s"(sc)
-                            : [cbm1] "s"(cbuf_a - 1u), [fe] "s"(fe), [stop] "v"(stopv), [rowa2] "v"(rowa2), [rowd] "v"(rowd), [vz] "v"(vzero), [vff] "v"(vff), [v100] "v"(v100), [m0] "s"(m0)
-                            : "vcc", "memory");
+                            : [r] "+&v"(r), [q] "+&v"(q), [mxp] "+&v"(mxp), [mg] "+&v"(mg),
+                              [a] "=&v"(a_), [w] "=&v"(w_), [t] "=&v"(t_), [x] "=&v"(x_), [y] "=&v"(y_), [bit] "=&v"(bit_), [mk] "=&v"(mk_), [sv] "=&s"(sv), [sc] "=&s"(sc), [sb] "=&s"(sb), [nh] "+s"(nh)
+                            : [cbm1] "s"(cbuf_a - 1u), [fe] "s"(fe), [stop] "v"(stopv), [rowa2] "v"(rowa2), [rowd] "v"(rowd), [vz] "v"(vzero), [vff] "v"(vff), [v100] "v"(v100), [vffq] "v"(vffq), [v100q] "v"(v100q), [vf00] "v"(vf00), [m0] "s"(m0)
+                            : "vcc", "scc", "memory");
                     }
+#undef SEG_HOP_STEP_BACK
+#undef SEG_HOP_NEXT
+#undef SEG_HOP_LITERALS
+#undef SEG_HOP_PARK
+#undef SEG_HOP0
+#undef SEG_HOP1
+                    if (mxp & 0x10000u) r = q;             // the lane's last hop started in the second half
                     merged = mg != 0u;
+                    PT_HOPS(mode, nh);
                 }
 #else
-                uint32_t mxp = 0, rprev = r;
-                bool act = go && !merged && r < stop;
-                while (__any(act)) {
+                // the same loop in C++: two hops per trip, the second with the two position registers in each other's role
+                uint32_t mxp = 0, q = r;
+                bool act = go && !merged && r < stop, in_q = false;        // in_q: the lane's last hop started from q (the asm: bit 16 of mxp)
+                // one hop from p, the token before it in o; the next position goes to o
+                auto hop = [&](uint32_t& p, uint32_t& o, bool second) {
                     uint32_t lo;
-                    asm volatile("ds_read_b32 %0, %1" : "=v"(lo) : "v"(cbuf_a + (act ? r : 0u) - 1u) : "memory");
+                    asm volatile("ds_read_b32 %0, %1" : "=v"(lo) : "v"(cbuf_a + (act ? p : 0u) - 1u) : "memory");
                     uint32_t mk = 0;
-                    const uint32_t bi = (act ? r : rb0) - rb0;
+                    const uint32_t bi = (act ? p : rb0) - rb0;
                     if (mode == 1) mk = *reinterpret_cast<const volatile uint32_t*>(&ROWA((bi >> 5) & 7u)) >> (bi & 31u);
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                     const uint32_t e0 = lo & 255u;
-                    if (act && mxp != 0u && e0 == 255u) { r = rprev; act = false; }   // the previous token's match length goes on: not plain
-                    if (act && r >= stop) act = false;
+                    if (act && mxp != 0u && e0 == 255u) { p = o; act = false; }       // the previous token's match length goes on: not plain (p == o now)
+                    if (act) in_q = second;
+                    if (act && p >= stop) act = false;
                     if (mode == 1) { if (act && (mk & 1u)) { merged = true; act = false; } }
                     if (act) {
                         const uint32_t L0 = (lo >> 12) & 15u, M0 = (lo >> 8) & 15u, b1 = (lo >> 16) & 255u;
                         const uint32_t isx = L0 == 15u ? 1u : 0u;
                         const uint32_t Lt = L0 + (isx ? b1 : 0u);
                         const uint32_t mx = M0 == 15u ? 1u : 0u;
-                        const uint32_t rn = r + 3u + isx + Lt + mx;
-                        const bool plain = !(isx && b1 == 255u) && rn < fe;
+                        const uint32_t pn = p + 3u + isx + Lt + mx;
+                        const bool plain = !(isx && b1 == 255u) && pn < fe;
                         if (plain) {
                             if (mode == 0) ROWA((bi >> 5) & 7u) |= 1u << (bi & 31u); else ROWB((bi >> 5) & 7u) |= 1u << (bi & 31u);
-                            rprev = r; r = rn; mxp = mx;
+                            o = pn; mxp = mx;
                         } else {
                             act = false;                                  // parked: the general routine takes this token
                         }
                     }
+                };
+                while (__any(act)) {
+                    hop(r, q, false);
+                    if (!__any(act)) break;
+                    hop(q, r, true);
                 }
+                if (in_q) r = q;                                          // a hop that is not plain leaves the lane where it started
 #endif
                 // the general routine serves parked lanes and lanes near the end of the input
                 const uint32_t pa = cstart + r;
@@ -481,6 +520,8 @@ __global__ __launch_bounds__(64) void lzf_seg_parse_kernel(seg_ctx c) {
 #undef PT_START
 #undef PT_MARK
 #undef PT_CHUNK
+#undef PT_HOP_ASM
+#undef PT_HOPS
 #undef PT_REPORT
 
 // =====================================================================================================================
@@ -1706,10 +1747,10 @@ template __global__ void lzf_seg_resolve_pair_kernel<131072>(seg_ctx);
 }  // namespace lzf
 
 #ifdef LZF_DBG_PARSE_TIME
-// Analysis only: the section sums of lzf_seg_parse_kernel since the last call with `reset` (out6 may be NULL).
-extern "C" int lzf_debug_parse_timers(unsigned long long* out6, int reset) {
-    if (out6 && hipMemcpyFromSymbol(out6, HIP_SYMBOL(lzf::lzf_dbg_parse_cycles), sizeof(unsigned long long) * 6u) != hipSuccess) return LZF_E_HIP;
-    const unsigned long long z[6] = {0, 0, 0, 0, 0, 0};
+// Analysis only: the section sums and counts of lzf_seg_parse_kernel since the last call with `reset` (out8 may be NULL).
+extern "C" int lzf_debug_parse_timers(unsigned long long* out8, int reset) {
+    if (out8 && hipMemcpyFromSymbol(out8, HIP_SYMBOL(lzf::lzf_dbg_parse_cycles), sizeof(unsigned long long) * 8u) != hipSuccess) return LZF_E_HIP;
+    const unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (reset && hipMemcpyToSymbol(HIP_SYMBOL(lzf::lzf_dbg_parse_cycles), z, sizeof(z)) != hipSuccess) return LZF_E_HIP;
     return LZF_OK;
 }
