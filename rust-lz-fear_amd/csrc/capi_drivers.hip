@@ -255,27 +255,40 @@ int fed_front(const d::Geometry& geo, const lzf_decompress_job* d_jobs, lzf_job_
 // (the bytes' share) and the parse (the sequences: counted, where lzf_decompress_cost_kernel samples — the block's exact number when every
 // chunk's chain falls in step with the block's inside its overlap, marks off the chain included otherwise: tests/launch_order_cases.py), and
 // perm[] ordered by it.
-int fed_decompress(Device& dv, const lzf_decompress_job* d_jobs, lzf_job_result* d_results, uint32_t n, uint32_t* perm, uint32_t* est, hipStream_t st, bool* used, uint64_t max_in_hint) {
+namespace {
+// what a fed call launched with: the state array of the front, the kernel's arguments and its geometry (lzf_debug_fed reads them back)
+struct FedLaunch { lzf::seg_ctx c{}; lzf::fed_args a{}; uint32_t slots = 0, grid = 0, census_mask = 0; };
+// plan + parse, the launch order, reset, the fed kernel — everything of a fed call in front of the pair kernel, in the scratch `mem` holds.
+// stop_piece: lzf::fed_args::stop_piece (the analysis library's lzf_debug_fed; 0 in every product call).
+int fed_launch(Device& dv, const lzf_decompress_job* d_jobs, lzf_job_result* d_results, uint32_t n, const d::FedLayout& l, const AsyncScratch& mem,
+               uint32_t* perm, uint32_t* est, uint32_t stop_piece, hipStream_t st, FedLaunch* fl) {
     const d::Knobs& kn = knobs();
+    lzf::seg_ctx& c = fl->c;
+    int rc = fed_front(dv.geo, d_jobs, d_results, n, l, mem, kn.fed_min_in, kn.order_len_shift, perm, est, st, &c);
+    if (rc != LZF_OK) return rc;
+    // The kernel runs as one wavefront per SLOT — as many as the device holds at once — and the slots share the jobs out in pieces
+    // (lz4_decompress_fed.hip): a call with more jobs than slots cuts every job into 16 (measured at 2.2 jobs per slot: 107.4 ms whole,
+    // 97.3 / 97.2 / 97.8 / 99.0 / 101.7 ms with 8 / 16 / 32 / 64 / 128 pieces), a smaller one leaves them whole.
+    const FedCensus fc = fed_census(dv, st);
+    const uint32_t slots = kn.fed_slots ? kn.fed_slots * c.n_cu : fc.slots;
+    uint32_t pieces = kn.fed_pieces ? kn.fed_pieces : n > fc.slots ? d::kFedPieces : 1u;
+    if ((uint64_t)n * pieces > 0xFFFFFFF0ull || !fc.xcc_mask) pieces = 1u;       // (no XCD mask: jobs stay whole)
+    fl->a = lzf::fed_args{d_jobs, d_results, c.st, c.bits, perm, area<lzf::fed_state>(mem, l.o_state), area<uint32_t>(mem, l.o_ticket), fc.xcc_mask ? fc.xcc_mask : 1u, n, c.maxch, pieces, kn.fed_carry, nullptr, stop_piece};
+    fl->slots = slots; fl->grid = slots < n ? slots : n; fl->census_mask = fc.xcc_mask;
+    LAUNCH_RC(rc, lzf::lzf_fed_reset_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, fl->a);
+    if (rc == LZF_OK) LAUNCH_RC(rc, k_fed32, dim3(fl->grid), dim3(64), kn.fed_pad_lds, st, fl->a);
+    return rc;
+}
+}  // namespace
+
+int fed_decompress(Device& dv, const lzf_decompress_job* d_jobs, lzf_job_result* d_results, uint32_t n, uint32_t* perm, uint32_t* est, hipStream_t st, bool* used, uint64_t max_in_hint) {
     const d::FedLayout l = d::fed_layout(n, max_in_hint);
     AsyncScratch mem(st);
     *used = mem.alloc(l.total);
     if (!*used) return LZF_OK;                                   // (no room for the bit maps: the pair kernel takes the call, the order is still to make)
-    lzf::seg_ctx c{};
-    int rc = fed_front(dv.geo, d_jobs, d_results, n, l, mem, kn.fed_min_in, kn.order_len_shift, perm, est, st, &c);
-    if (rc == LZF_OK) {
-        // The kernel runs as one wavefront per SLOT — as many as the device holds at once — and the slots share the jobs out in pieces
-        // (lz4_decompress_fed.hip): a call with more jobs than slots cuts every job into 16 (measured at 2.2 jobs per slot: 107.4 ms whole,
-        // 97.3 / 97.2 / 97.8 / 99.0 / 101.7 ms with 8 / 16 / 32 / 64 / 128 pieces), a smaller one leaves them whole.
-        const FedCensus fc = fed_census(dv, st);
-        const uint32_t slots = kn.fed_slots ? kn.fed_slots * c.n_cu : fc.slots;
-        uint32_t pieces = kn.fed_pieces ? kn.fed_pieces : n > fc.slots ? d::kFedPieces : 1u;
-        if ((uint64_t)n * pieces > 0xFFFFFFF0ull || !fc.xcc_mask) pieces = 1u;       // (no XCD mask: jobs stay whole)
-        lzf::fed_args a{d_jobs, d_results, c.st, c.bits, perm, area<lzf::fed_state>(mem, l.o_state), area<uint32_t>(mem, l.o_ticket), fc.xcc_mask ? fc.xcc_mask : 1u, n, c.maxch, pieces, kn.fed_carry, nullptr};
-        LAUNCH_RC(rc, lzf::lzf_fed_reset_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, a);
-        if (rc == LZF_OK) LAUNCH_RC(rc, k_fed32, dim3(slots < n ? slots : n), dim3(64), kn.fed_pad_lds, st, a);
-        if (rc == LZF_OK) LAUNCH_RC(rc, k_paired24, dim3(n), dim3(128), 0, st, d_jobs, d_results, n, (const uint32_t*)perm, (const lzf::seg_job*)c.st);
-    }
+    FedLaunch fl;
+    int rc = fed_launch(dv, d_jobs, d_results, n, l, mem, perm, est, 0u, st, &fl);
+    if (rc == LZF_OK) LAUNCH_RC(rc, k_paired24, dim3(n), dim3(128), 0, st, d_jobs, d_results, n, (const uint32_t*)perm, (const lzf::seg_job*)fl.c.st);
     if (mem.release() != hipSuccess && rc == LZF_OK) rc = LZF_E_HIP;
     if (rc != LZF_OK) g_last_error = "bitmap-fed decompress: launch failed";
     return rc;
@@ -369,6 +382,37 @@ int lzf_debug_order(uint32_t what, const void* d_jobs, uint32_t n, const void* h
     if (h_probe_results && what == 5u) HIP_TRY(hipMemcpy(h_probe_results, pres, sizeof(lzf_job_result) * n_probes, hipMemcpyDeviceToHost));
     HIP_TRY(fed_mem.release());
     HIP_TRY(buf.release());
+    return LZF_OK;
+}
+
+// Analysis only: a fed call WITHOUT the pair kernel behind it, on the default stream: scratch, fed_front, lzf_fed_reset_kernel and the fed kernel through
+// fed_launch — the launch lines of fed_decompress, the census and LZF_FED_PIECES / LZF_FED_SLOTS / LZF_FED_CARRY / LZF_FED_MIN_IN included; the launch
+// order is made as the batch call makes it (LZF_DECOMPRESS_ORDER).  stop_piece as fed_args::stop_piece (0: every ticket is drawn).  Copied to host
+// buffers (NULL = skip): h_state = seg_job[n], h_fed = fed_state[n], h_perm = perm[n] (all ~0 when no order was made),
+// geom[0..3] = pieces used, slots, grid, the census's XCD mask (0: it gave none).  What the kernel did not finish is left as the caller put it: d_results too.
+extern "C"
+int lzf_debug_fed(const lzf_decompress_job* d_jobs, lzf_job_result* d_results, uint32_t n, uint64_t max_input_len, uint32_t stop_piece,
+                  void* h_state, void* h_fed, uint32_t* h_perm, uint32_t* geom) {
+    int rc = ensure_device();
+    if (rc < 0) return rc;
+    if (n == 0 || !d_jobs || !d_results) return LZF_E_INVALID;
+    Device& dv = device();
+    hipStream_t st = nullptr;
+    const d::FedLayout l = d::fed_layout(n, max_input_len ? max_input_len : ~0ull);      // (the caller's bound of its inputs, as lzf_decompress_batch_sized takes it; 0: none)
+    AsyncScratch mem(st), perm_mem(st);
+    if (!mem.alloc(l.total)) return LZF_E_HIP;
+    const bool want_order = d::decompress_plan(dv.geo, knobs(), n, ~0ull).want_order;
+    uint32_t* const perm = want_order && perm_mem.alloc(2u * sizeof(uint32_t) * (size_t)n) ? static_cast<uint32_t*>(perm_mem.p) : nullptr;
+    FedLaunch fl;
+    rc = fed_launch(dv, d_jobs, d_results, n, l, mem, perm, perm ? perm + n : nullptr, stop_piece, st, &fl);
+    HIP_TRY(hipDeviceSynchronize());
+    if (rc != LZF_OK) return rc;
+    if (geom) { geom[0] = fl.a.pieces; geom[1] = fl.slots; geom[2] = fl.grid; geom[3] = fl.census_mask; }
+    if (h_state) HIP_TRY(hipMemcpy(h_state, fl.c.st, sizeof(lzf::seg_job) * n, hipMemcpyDeviceToHost));
+    if (h_fed) HIP_TRY(hipMemcpy(h_fed, fl.a.state, sizeof(lzf::fed_state) * n, hipMemcpyDeviceToHost));
+    if (h_perm) { if (perm) HIP_TRY(hipMemcpy(h_perm, perm, sizeof(uint32_t) * n, hipMemcpyDeviceToHost)); else memset(h_perm, 0xFF, sizeof(uint32_t) * n); }
+    HIP_TRY(perm_mem.release());
+    HIP_TRY(mem.release());
     return LZF_OK;
 }
 #endif

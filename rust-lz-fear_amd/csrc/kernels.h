@@ -153,6 +153,7 @@ struct fed_args {
     uint32_t pieces;             // every job goes through the kernel in this many pieces (1: whole)
     uint32_t carry;              // analysis library (LZF_FED_CARRY): the longest last batch of a window that waits for the next one (the product: kFedwCarry)
     uint32_t* census;            // not null: the launch only counts how many of its workgroups the device holds at once ([0] arrivals, [1] the answer, [2] mask of their XCDs)
+    uint32_t stop_piece;         // analysis library (lzf_debug_fed): not 0: the tickets of pieces >= stop_piece are not drawn, every job stays parked in front of that piece (the product ignores it)
 };
 __global__ void lzf_fed_reset_kernel(fed_args a);
 // X(name, ring bytes, bit-map words per round, token-list entries)

@@ -81,14 +81,18 @@ __global__ LZF_FED_BOUNDS void lzf_decompress_fed_kernel(fed_args a) {      // (
     const uint32_t xcc = xcc_id() & 31u;
     if (pieces > 1u && !((a.xcc_mask >> xcc) & 1u)) return;           // (an XCD the census did not see: no jobs were given to it)
     const uint32_t ng = pieces > 1u ? (uint32_t)__popc(a.xcc_mask) : 1u, g = pieces > 1u ? (uint32_t)__popc(a.xcc_mask & ((1u << xcc) - 1u)) : 0u;
-    const uint32_t n_g = n > g ? (n - g + ng - 1u) / ng : 0u;
+    const uint32_t n_g = lzf_fedw_group_jobs(n, g, ng);
+#ifdef LZF_ANALYSIS
+    const uint32_t n_tickets = n_g * (a.stop_piece && a.stop_piece < pieces ? a.stop_piece : pieces);      // (lzf_debug_fed: the tickets of pieces >= stop_piece are not drawn)
+#else
     const uint32_t n_tickets = n_g * pieces;
+#endif
     for (;;) {
     uint32_t tk = 0;
     if (lane == 0u) tk = __hip_atomic_fetch_add(a.ticket + g * kFedTicketStride, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     tk = __builtin_amdgcn_readfirstlane(tk);
     if (tk >= n_tickets) break;
-    const uint32_t piece = tk / n_g, k = (tk - piece * n_g) * ng + g;
+    const uint32_t piece = lzf_fedw_ticket_piece(tk, n_g), k = lzf_fedw_ticket_rank(tk, piece, n_g, g, ng);
     const uint32_t jid = a.perm ? a.perm[k] : k;
     const seg_job sj = a.st[jid];
     if (!sj.eligible || sj.failed || sj.done) continue;
@@ -115,9 +119,8 @@ __global__ LZF_FED_BOUNDS void lzf_decompress_fed_kernel(fed_args a) {      // (
         uint32_t expect = 0;                 // where the next token of the chain starts (len: the chain has ended)
         uint32_t cstart = 0;
         o = (uint32_t)job.out_existing_len;
-        // this piece: the tokens that start in rounds [piece, piece + 1) * per of the job's input
-        const uint32_t rounds = (jv.len + kRound - 1u) / kRound, per = (rounds + pieces - 1u) / pieces;
-        const uint32_t piece_end = (piece + 1u) * per >= rounds ? jv.len : (piece + 1u) * per * kRound;
+        // this piece: the tokens that start in rounds [piece, piece + 1) * per of the job's input (lzf_fed_window.h)
+        const uint32_t piece_end = lzf_fedw_piece_end(jv.len, pieces, piece);
         if (piece > 0u) {
             // the piece before this one was drawn n tickets ago: as a rule it is done; else wait for it (bounded), then take its state over
             uint32_t f = 0;

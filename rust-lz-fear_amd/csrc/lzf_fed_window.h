@@ -58,4 +58,28 @@ LZF_FEDW_HD int lzf_fedw_carry(uint32_t tc, uint32_t tidx, uint32_t window_end, 
     return tidx > 0u && tc - tidx <= carry && window_end < len;
 }
 
+// ---- the PIECE RULES: a launch of more jobs than resident wavefronts cuts every job into `pieces` stretches and deals (job, piece)
+// tickets out group by group (lz4_decompress_fed.hip; a group is the jobs of one XCD).
+//
+//   lzf_fedw_piece_end     where piece p of a job of `len` compressed bytes ends: the tokens that START below it are the piece's
+//   lzf_fedw_group_jobs    how many of n jobs (ranks g, g + ng, g + 2 ng, ...) group g of ng serves
+//   lzf_fedw_ticket_piece  ticket tk of a group of n_g jobs -> the piece: lap after lap over the group's jobs
+//   lzf_fedw_ticket_rank   ... and the job's rank in launch order; piece p - 1 of a job is drawn n_g tickets before its piece p
+//
+// A job is `rounds` windows' worth of input; every piece but the last is `per` whole rounds, the last ends at len — and so does
+// every piece from the one that reaches the last round on (rounds < pieces: the later pieces are empty).
+LZF_FEDW_HD uint32_t lzf_fedw_piece_end(uint32_t len, uint32_t pieces, uint32_t p) {
+    const uint32_t rounds = (len + (uint32_t)kFedwRound - 1u) / (uint32_t)kFedwRound, per = (rounds + pieces - 1u) / pieces;
+    return (p + 1u) * per >= rounds ? len : (p + 1u) * per * (uint32_t)kFedwRound;
+}
+LZF_FEDW_HD uint32_t lzf_fedw_group_jobs(uint32_t n, uint32_t g, uint32_t ng) {
+    return n > g ? (n - g + ng - 1u) / ng : 0u;
+}
+LZF_FEDW_HD uint32_t lzf_fedw_ticket_piece(uint32_t tk, uint32_t n_g) {
+    return tk / n_g;
+}
+LZF_FEDW_HD uint32_t lzf_fedw_ticket_rank(uint32_t tk, uint32_t piece, uint32_t n_g, uint32_t g, uint32_t ng) {
+    return (tk - piece * n_g) * ng + g;
+}
+
 #endif  // LZF_FED_WINDOW_H
