@@ -43,35 +43,53 @@
 #endif
                 const uint32_t ob0 = o;
                 const uint32_t nb_try = Tc - tidx < kWave ? Tc - tidx : kWave;
+#if defined(LZF_FED_DECODE)
+                // the lanes with a token, as a mask built on the scalar side (nb_try >= 1): the set-up's ballots are compare masks ANDed
+                // with it, its selects take it as their condition — no lane compare feeds a scalar instruction
+                const unsigned long long act0 = lanes_below(nb_try);
+#else
                 const bool act0 = lane < nb_try;
+#endif
                 // ---- re-read the token (decompress.rs:61-71), per lane
                 uint32_t L = 0, M = 0, src = 0;
                 bool has = false;
 #if defined(LZF_FED_DECODE)
-                // Each token is decoded here and nowhere else.  The common token (no 0xFF length byte, its match-length byte staged)
+                // Each token is decoded here and nowhere else.  The common token (no 0xFF length byte, offset and match-length byte staged)
                 // without branches; the rest through the serial routine.  Lanes past nb_try decode lane 0's token again (masked off).
                 uint32_t next;                                     // where the token's successor starts (len: the last literals)
-                const uint32_t pos = toks[act0 ? tidx + lane : tidx];
+                const uint32_t pos = toks[tidx + lane_sel(act0, lane, 0u)];
                 const uint32_t tp = cstart + pos;
                 uint32_t w;                                        // token + first literal-length byte (pos < kRound: staged)
                 asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(w) : "v"(sb.lds + pos) : "memory");
                 const uint32_t l0 = (w >> 4) & 15u, b1 = (w >> 8) & 255u, m0 = w & 15u;
                 const bool lx = l0 == 15u;
-                L = l0 + (lx ? b1 : 0u);
+                const uint32_t lext = lx ? b1 : 0u;
+                L = l0 + lext;
                 src = tp + (lx ? 2u : 1u);
                 const uint32_t q = src + L;                        // the offset (a missing extension byte reads as 0: q > len then)
                 has = q + 2u <= jv.len;                               // :70 read_u16 fails: last literals
                 const bool mx = has && m0 == 15u;
-                const uint32_t r1 = q + 2u - cstart;               // the match-length byte
-                const uint32_t m1 = lds_ld8(sb.lds + (r1 < sb.kCB ? r1 : 0u));
-                M = has ? (mx ? 19u + m1 : m0 + 4u) : 0u;
-                next = has ? q + (mx ? 3u : 2u) : jv.len;
-                bool bad = q > jv.len || (mx && q + 2u >= jv.len);       // :67 read_exact, read_lsic: UnexpectedEnd
-                const bool general = (lx && b1 == 255u) || (mx && (r1 >= sb.kCB || m1 == 255u));
-                if (__ballot(act0 && general)) {
-                    if (general) {                                 // decompress.rs:61-71 without the copies, byte by byte
+                // The offset and the match-length byte behind it in ONE unaligned read (off | m1 << 16), where all four bytes are staged
+                // (rq <= pos + 2 + 270 < 2^16: no wrap).  A lane whose four bytes are not reads position 0 and ignores it: its match length,
+                // if it has an extension, comes from the serial routine (mext = 255 sends it there — also the lane whose byte at q + 2 is
+                // the last staged one, which read it by itself before), its offset from the rare path behind the scan.  `off` stays
+                // in its register across the scan; a lane that ends up without a match or outside the batch never looks at it.
+                uint32_t rq = q - cstart;
+                const bool fit4 = rq + 4u <= sb.kCB;
+                const uint32_t ow = lds_ld32(sb.lds + (fit4 ? rq : 0u));
+                uint32_t off = ow & 0xFFFFu;
+                const uint32_t mext = mx ? (fit4 ? (ow >> 16) & 255u : 255u) : 0u;
+                M = has ? m0 + 4u + mext : 0u;                     // (m0 == 15: 19 + m1)
+                // `need`: how far the token needs the input to reach.  :67 read_exact wants q <= len; with a match, has says q + 2 <= len
+                // already, and read_lsic one byte more when m0 == 15.  need > len: UnexpectedEnd (one compare, below)
+                uint32_t need = has ? q + (mx ? 3u : 2u) : q;
+                next = has ? need : jv.len;
+                const bool general = (lext > mext ? lext : mext) == 255u;       // (lx && b1 == 255) || (mx && (m1 not staged with the offset || m1 == 255))
+                {                                                  // (a lane past nb_try holds lane 0's token: general only if lane 0 is.  The branch around
+                    if (general) {                                 //  a per-lane `if` is the wave-uniform test already)  decompress.rs:61-71 without the copies, byte by byte
                         uint32_t p = tp + 1u, b = 0;
-                        L = l0; M = 0; has = false; next = jv.len; bad = false;
+                        bool bad = false;
+                        L = l0; M = 0; has = false; next = jv.len;
                         if (lx) {
                             do { if (p >= jv.len) { bad = true; break; } b = sb.rdb(p); ++p; L += b; if (L > kMaxPosB) L = kMaxPosB; } while (b == 255u);
                         }
@@ -85,12 +103,13 @@
                             }
                             M += 4u; next = p;
                         }
+                        need = bad ? 0xFFFFFFFFu : 0u;
+                        rq = sb.kCB;                               // (the offset is not where the read above looked: the rare path reads it)
                     }
                 }
                 // the chain: lane 0's token is where the chain goes on, every other lane's token where the lane before it ends (the
                 // batch's last token is checked against its successor as lane 0 of the next batch or round)
-                if (tp != wave_prev(next, expect)) bad = true;
-                if (__ballot(act0 && bad)) { bail = true; break; }
+                if ((__builtin_amdgcn_uicmp(need, jv.len, 34 /* > */) | __builtin_amdgcn_uicmp(tp, wave_prev(next, expect), 33 /* != */)) & act0) { bail = true; break; }
 #else
 #ifdef LZF_TOKEN_WORD
                 // the parser already decoded the lengths of plain tokens (entry = offset | L << 16 | (M - 4) << 24)
@@ -129,19 +148,29 @@
 #endif
                 // ---- output positions
                 uint32_t tot = L + M; if (tot > kTotClamp || tot < L) tot = kTotClamp;
+#if defined(LZF_FED_DECODE)
+                // (first lane over the span, nb and nb - 1 by scalar instructions.  No `& act0`: the lanes past nb_try add 0, so they
+                //  repeat lane nb_try - 1's sum, and min(., nb_try) gives the same lane with or without them)
+                const uint32_t tot0 = lane_sel(act0, tot, 0u);
+                const uint32_t incl = wave_scan_add(tot0);
+                const uint32_t lo = ob0 + (incl - tot0);
+                const uint32_t mo = lo + L;
+                const uint32_t nb = first_lane_min(__builtin_amdgcn_uicmp(incl, kSpanMax, 34 /* > */), nb_try);       // sequences in this batch
+#else
                 const uint32_t incl = wave_scan_add(act0 ? tot : 0u);
                 const uint32_t lo = ob0 + (incl - (act0 ? tot : 0u));
                 const uint32_t mo = lo + L;
                 const uint32_t c = first_lane(__ballot(act0 && incl > kSpanMax));
                 const uint32_t nb = c < nb_try ? c : nb_try;       // sequences in this batch
-#if defined(LZF_FED_DECODE)
-                expect = __builtin_amdgcn_readlane(next, nb ? nb - 1u : 0u);
 #endif
 
                 if (nb == 0u) {
                     // =============================================================
                     // C. solo sequence (larger than a batch): HBM -> HBM, then re-fill the ring
                     // =============================================================
+#if defined(LZF_FED_DECODE)
+                    expect = __builtin_amdgcn_readlane(next, 0);
+#endif
                     const uint32_t s_L = __builtin_amdgcn_readlane(L, 0);
                     const uint32_t s_M = __builtin_amdgcn_readlane(M, 0);
                     const uint32_t s_src = __builtin_amdgcn_readlane(src, 0);
@@ -199,6 +228,24 @@
                     continue;
                 }
 
+#if defined(LZF_FED_DECODE)
+                // the batch's lanes as a scalar mask (nb >= 1 here); a lane of the batch has a match exactly when its M (>= 4) is not 0
+                expect = __builtin_amdgcn_readlane(next, nb - 1u);
+                const unsigned long long act_m = lanes_below(nb);
+                L = lane_sel(act_m, L, 0u); M = lane_sel(act_m, M, 0u);
+                has = M != 0u;
+                const unsigned long long has_m = __builtin_amdgcn_uicmp(M, 0u, 33 /* != */);
+                const bool act = lane < nb;                        // (only the exact error codes below look at it)
+                // the rare path of the offset: a lane with a match whose four bytes were not all staged, or whose token the serial routine decoded
+                if (__builtin_amdgcn_uicmp(rq, sb.kCB - 4u, 34 /* > */) & has_m) {
+                    asm volatile("");      // (keeps hipcc from folding this uniform test into the lanes' own, which puts an EXEC region and its bookkeeping on the common path)
+                    if (has && rq > sb.kCB - 4u) {
+                        if (!sb.kStage) off = ld2(jv.in + src + L);
+                        else if (src + L - cstart + 2u <= sb.kCB) off = lds_ld16(sb.lds + (src + L - cstart));      // (one unaligned 2-byte LDS read)
+                        else off = sb.rdb(src + L) | (sb.rdb(src + L + 1u) << 8);
+                    }
+                }
+#else
                 const bool act = lane < nb;
                 has = has && act;
                 if (!act) { L = 0; M = 0; }
@@ -208,7 +255,29 @@
                     else if (src + L - cstart + 2u <= sb.kCB) off = lds_ld16(sb.lds + (src + L - cstart));      // (one unaligned 2-byte LDS read)
                     else off = sb.rdb(src + L) | (sb.rdb(src + L + 1u) << 8);
                 }
-                // ---- errors, first sequence in stream order wins; inside a sequence the reference's order
+#endif
+#if defined(LZF_FED_DECODE)
+                // ---- errors.  What a valid batch needs is two tests; the exact codes are worked out only when one of them flags something.
+                //  - Uniform, in scalar registers: E = ob0 + incl[nb - 1], where the batch ends (the flush's new `o`).  For a lane j < nb,
+                //    incl[j] <= kSpanMax (nb stops in front of the first lane over it), so tot[j] <= incl[j] < kTotClamp was not clamped
+                //    and did not wrap: tot = L + M exactly, and lo + L + M = ob0 + incl[j] <= E.  ob0 <= cap <= kMaxPosB (every earlier
+                //    batch passed these tests; out_existing_len <= out_cap), so E <= kMaxPosB + kSpanMax < 2^32.  With E <= cap and
+                //    E <= limit neither capacity test nor the limit test can fail in any lane.  E over a bound is NOT an error by
+                //    itself: a valid job may end above `limit` through its last, literals-only token; the codes below decide.
+                //  - Per lane, both offset errors in one compare.  It only has to be right when the uniform test passed (otherwise the codes
+                //    run anyway): then mo <= E <= cap <= kMaxPosB and plen < kMaxPosB (the contract), so mo + plen < 2^32 does not wrap.
+                //    off <= 0xFFFF; off == 0 gives off - 1 = 2^32 - 1 >= anything, and for off >= 1, off - 1 >= mo + plen is
+                //    off > mo + plen, that is off > mo && off - mo > plen.
+                static_assert(kSpanMax < kTotClamp && (uint64_t)kMaxPosB * 2u < (1ull << 32), "the bounds argument above");
+                const uint32_t lim32 = jv.limit > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)jv.limit;
+                const uint32_t fit = jv.cap < lim32 ? jv.cap : lim32;
+                const uint32_t E = ob0 + __builtin_amdgcn_readlane(incl, nb - 1u);
+                // (the uniform test as a compare mask too: as `E > fit ||` hipcc turns both tests into booleans and back, seven scalar instructions)
+                const unsigned long long flagged = (__builtin_amdgcn_uicmp(off - 1u, mo + jv.plen, 35 /* >= */) & has_m) | __builtin_amdgcn_uicmp(E, fit, 34 /* > */);
+                if (flagged) {
+#endif
+                // ---- errors, first sequence in stream order wins; inside a sequence the reference's order  (the pair and batched kernels
+                // work the codes out for every batch: the two tests in front cost them scalar registers, two of them spilled in the batched kernel)
                 int code = LZF_OK;
                 if (act) {
                     if (lo > jv.cap || jv.cap - lo < L) code = LZF_OUT_CAPACITY;                        // our buffer (literals)
@@ -219,6 +288,9 @@
                 }
                 const uint32_t e = first_lane(__ballot(code != LZF_OK));
                 if (e < 64u) { status = __builtin_amdgcn_readlane(code, e); break; }
+#if defined(LZF_FED_DECODE)
+                }
+#endif
                 PHASE(1);
 
                 // ---- matches (copy_overlapping, decompress.rs:80-138)

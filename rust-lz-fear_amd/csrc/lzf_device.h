@@ -45,6 +45,22 @@ __device__ __forceinline__ uint32_t first_lane(unsigned long long m) {
     return m ? (uint32_t)__builtin_ctzll(m) : 64u;
 }
 
+// Lane masks on the scalar side.  A vector compare that feeds a scalar instruction costs a lone wave ~16 cycles (lzf_simt.h), and
+// __ballot of a bool goes through a vector register and back (v_cndmask 0/1, v_cmp_ne 0) on top of it — __builtin_amdgcn_ballot_w64 of
+// a bool that is not one compare's result does the same.  A ballot is therefore written as the compare itself (__builtin_amdgcn_uicmp
+// of two integers: the lane mask is the instruction's result), and masks that depend on uniform values only are built by scalar
+// instructions and applied with lane_sel.
+// lanes 0 .. n - 1, 1 <= n <= 64 (uniform)
+__device__ __forceinline__ unsigned long long lanes_below(uint32_t n) { return ~0ull >> (kWave - n); }
+// per-lane select by a uniform mask
+__device__ __forceinline__ uint32_t lane_sel(unsigned long long m, uint32_t if1, uint32_t if0) {
+    uint32_t r; asm("v_cndmask_b32 %0, %1, %2, %3" : "=v"(r) : "v"(if0), "v"(if1), "s"(m)); return r;
+}
+// first set lane of a mask, at most `bound` (s_ff1 gives 0xFFFFFFFF for an empty mask)
+__device__ __forceinline__ uint32_t first_lane_min(unsigned long long m, uint32_t bound) {
+    uint32_t r; asm("s_ff1_i32_b64 %0, %1\n\ts_min_u32 %0, %0, %2" : "=&s"(r) : "s"(m), "s"(bound) : "scc"); return r;
+}
+
 // Every store this wavefront has issued so far becomes visible to its own later loads
 // (s_waitcnt vmcnt(0); the per-CU L1 is write-through, so same-CU readers see it).
 __device__ __forceinline__ void wave_store_fence() {
@@ -118,6 +134,9 @@ __device__ __forceinline__ void lds_ld16x2(uint32_t a0, uint32_t a1, uint32_t& v
 }
 __device__ __forceinline__ uint32_t lds_ld16(uint32_t a) {
     uint32_t v; asm volatile("ds_read_u16 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(a) : "memory"); return v;
+}
+__device__ __forceinline__ uint32_t lds_ld32(uint32_t a) {
+    uint32_t v; asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(a) : "memory"); return v;
 }
 __device__ __forceinline__ uint32_t lds_ld8(uint32_t a) {
     uint32_t v; asm volatile("ds_read_u8 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(a) : "memory"); return v;
