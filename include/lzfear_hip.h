@@ -139,8 +139,8 @@ int lzf_decompress_batch(const lzf_decompress_job* d_jobs, lzf_job_result* d_res
                          uint32_t n_jobs, void* hip_stream);
 /* The same with what the caller knows about the batch: an upper bound of the jobs' input_len (the job array lives in HBM, the
  * library cannot look; ~0 = unknown, which is what lzf_decompress_batch passes).  Batches of up to four blocks per CU go through the
- * segmented pipeline (a block decoded by many wavefronts; blocks of 64 KiB .. 4 MiB + 32 KiB of input without prefix / existing
- * output), whose stream-ordered scratch — bit maps, tile sums and a 16-byte record per sequence, up to ~0.15 + 1.8 bytes per byte of
+ * segmented pipeline (a block decoded by many wavefronts; blocks of 64 KiB .. 4 MiB + 32 KiB of input, with or without a prefix and
+ * existing output below 2 GiB - 256: the blocks of linked-block and dictionary frames included), whose stream-ordered scratch — bit maps, tile sums and a 16-byte record per sequence, up to ~0.15 + 1.8 bytes per byte of
  * `max_input_len` and job, from the device's default memory pool, freed in stream order — is sized by this bound; with a bound below
  * 64 KiB the pipeline is skipped.  Results are identical either way. */
 int lzf_decompress_batch_sized(const lzf_decompress_job* d_jobs, lzf_job_result* d_results,

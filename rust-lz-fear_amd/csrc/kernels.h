@@ -70,20 +70,22 @@ constexpr auto k_paired24 = lzf_decompress_paired_kernel<4096, 24, 384>;
 // ---------------------------------------------------------------------------------------------------------------------
 // Segmented decompress (lz4_decompress_seg.hip): one block decoded by MANY wavefronts, as a pipeline of launches over the
 // whole batch.  Used for batches that leave the chip mostly empty with one workgroup per block (per-block latency regime).
-//   plan      per job: eligible?  (no prefix, no existing output, size window)  chunk / tile counts
+//   plan      per job: eligible?  (size window; a prefix and existing output in 31-bit positions)  chunk / tile counts
 //   parse     one wave per 16 KiB chunk of compressed bytes (chunks overlap by 2 KiB): speculative region-walk parse from
 //             the chunk's first byte -> bit map "a token of this chunk's chain starts here" + the chain's exit
 //   seam      one wave per job: chunk h's chain is the true one from the position where the true chain (exit of chunk
 //             h - 1) steps on one of its marked tokens; almost always that is the exit itself (the chains met inside the
 //             overlap), otherwise a short walk patches the bit map
 //   tilesum   one wave per 2 KiB tile of compressed bytes: tokens and output bytes of the tile
-//   scan      one wave per job: exclusive sums over the tiles, record space from the arena
+//   scan      one wave per job: exclusive sums over the tiles from the job's existing output on (a job's first output byte
+//             is out_existing_len: every position of the later stages is absolute), record space from the arena
 //   records   one wave per tile: decode every token, absolute output positions, error checks, LITERALS -> out, and per
 //             batch of 64 sequences the dependency level of every match (level k copies only from bytes that are final
 //             once levels < k are done), its sub-batch and length class: one 16-byte record per sequence, final form
 //   resolve   two waves per job, the only serial stage: ring of the recent output in LDS (filled with the literals
 //             already in place by the stager wave, flushed by it with aligned 16-byte stores), per batch one LDS round
-//             per dependency level by the resolver wave (a hand-scheduled loop)
+//             per dependency level by the resolver wave (a hand-scheduled loop).  Existing output is output that is final
+//             before the launch: the stager primes the ring with its tail; sources in the prefix are moved in by the stager
 // A job that is not eligible, or in which any stage meets something it does not handle (every DecodeError, capacity,
 // arena exhausted), is left to the pair kernel, which runs last and skips the jobs the pipeline finished.
 // ---------------------------------------------------------------------------------------------------------------------
@@ -182,6 +184,7 @@ LZF_FED_VARIANTS(LZF_EXTF)
 __device__ __forceinline__ uint32_t seg_job_of(const seg_ctx& c, uint32_t i) { return c.by_len ? c.by_len[i + c.g_off] : i + c.g_off; }
 constexpr uint32_t kSegRegion = 256, kSegChunk = 64u * kSegRegion, kSegOverlap = 2048, kSegStride = kSegChunk - kSegOverlap;
 constexpr uint32_t kSegChunkWords = kSegChunk / 32u, kSegTile = 2048;
+constexpr uint32_t kSegPrefixReach = 65535;     // existing output of this many bytes or more: no offset reaches the prefix (decompress.rs:76 reads a u16)
 static_assert(kSegChunk == (uint32_t)kFedwChunk && kSegOverlap == (uint32_t)kFedwOverlap && kSegStride == (uint32_t)kFedwStride, "lzf_fed_window.h restates the chunk geometry");
 __global__ void lzf_seg_plan_kernel(seg_ctx c);
 // batches of more than one block per CU: which workgroup of the resolve stage takes which job — the jobs ranked by their number of

@@ -11,9 +11,15 @@
 //   * literals go to their final place in `out` from all tiles at once (they depend on nothing);
 //   * the second chain is reduced to what it is: per batch of 64 sequences, one LDS round (read, write) per dependency
 //     level, by a wave that does nothing else — the records it consumes carry positions, lengths and levels.
+// History (decompress.rs:80-99: a match source lies on the virtual stream prefix ++ output): a job's existing output
+// out[0, E) is output that is final before the launch — the tiles' sums start at E, every position is absolute, the
+// resolve stage primes its ring with the tail of out[0, E) and stores nothing below out + E; a source in the prefix is
+// moved in by the stager from `prefix` (class 13), one that starts there and ends in the output stands alone like a
+// sequence larger than a sub-batch (class 8).  So the blocks of a linked frame and of a frame with a dictionary are
+// the pipeline's like any other.
 // Error behaviour: the pipeline only finishes jobs that decode cleanly.  Anything else (every DecodeError, a buffer that
-// is too small, prefix / existing output, sizes outside the window) is left to the pair kernel, launched last, which
-// skips finished jobs — so statuses and partial outputs are exactly the pair kernel's.
+// is too small, sizes outside the window, history beyond 31-bit positions) is left to the pair kernel, launched last,
+// which skips finished jobs — so statuses and partial outputs are exactly the pair kernel's.
 #include "lzf_device.h"
 #include "kernels.h"
 #include "lzf_dispatch.h"
@@ -155,8 +161,13 @@ __global__ __launch_bounds__(256) void lzf_seg_plan_kernel(seg_ctx c) {
     const bool in_window = job.input_len >= c.min_in && job.input_len <= c.max_in;
     if (c.size_only)     // nothing is decoded: no `out`, prefix and existing output are lengths (beyond 2 GiB: the one-wave kernel's LZF_CONTRACT); an empty input has no bytes to point at
         s.eligible = (in_window && (job.input != nullptr || job.input_len == 0) && job.prefix_len < kMaxPosB && job.out_existing_len < kMaxPosB) ? 1u : 0u;
-    else
-        s.eligible = ((c.fed || (job.prefix_len == 0 && job.out_existing_len == 0)) && in_window && job.input != nullptr && job.out != nullptr) ? 1u : 0u;
+    else {
+        // history (a prefix, existing output) in 31-bit positions like everything else; existing output of 65 535 bytes or more hides the
+        // prefix for good (an offset is at most 65 535): such a job is decoded as one without a prefix, whatever its pointer
+        const bool history = job.prefix_len < kMaxPosB && job.out_existing_len < kMaxPosB &&
+                             (job.prefix_len == 0 || job.out_existing_len >= kSegPrefixReach || job.prefix != nullptr);
+        s.eligible = ((c.fed || history) && in_window && job.input != nullptr && job.out != nullptr) ? 1u : 0u;
+    }
     const uint32_t len = s.eligible ? (uint32_t)job.input_len : 0u;
     s.nch = s.eligible && !(c.size_only && len == 0u) ? seg_nch(len) : 0u;
     s.ntile = (len + kSegTile - 1u) / kSegTile;
@@ -771,7 +782,7 @@ __global__ __launch_bounds__(64) void lzf_seg_scan_kernel(seg_ctx c) {
     const lzf_decompress_job job = c.jobs[j];
     LZF_GLOBAL uint32_t* const TT = (LZF_GLOBAL uint32_t*)c.tile_tok + (size_t)j * c.maxtile;
     LZF_GLOBAL uint32_t* const TO = (LZF_GLOBAL uint32_t*)c.tile_out + (size_t)j * c.maxtile;
-    uint64_t ctok = 0, cout = 0;
+    uint64_t ctok = 0, cout = job.out_existing_len;            // the job's first output byte: positions are absolute from here on (the plan stage: below kMaxPosB)
     // (eight steps' loads in flight at once: with one step per round trip to HBM the kernel was 33 dependent loads long, 75 us)
     for (uint32_t t8 = 0; t8 < sj.ntile; t8 += 512u) {
         uint32_t av[8], bv[8];
@@ -826,15 +837,18 @@ __global__ __launch_bounds__(64) void lzf_seg_scan_kernel(seg_ctx c) {
 // Sub-batches: consecutive sequences of the batch whose output spans at most ring / 8 bytes (greedy).
 // Classes: 0 no match | 1: 4..7 bytes | 2: 8..16 | 3: 17..32 | 4: 33..64 (all not overlapping, source inside the ring) |
 //   5 overlapping, <= 64 | 6 whole wave (longer, or wrapping around the ring) | 7 source (partly) older than what the ring
-//   is guaranteed to hold when the sub-batch is resolved: moved by the stager | 8 a sequence larger than a sub-batch.
-__global__ __launch_bounds__(64) void lzf_seg_records_kernel(seg_ctx c) {
-    __shared__ __attribute__((aligned(16))) uint8_t stage[kTileStage];
-    __shared__ uint16_t list[kTileTokMax + 64u];
-    const uint32_t j = (c.rec_by_len || c.grouped) ? seg_job_of(c, blockIdx.y) : blockIdx.y;
-    const seg_job sj = c.st[j];
-    if (!sj.eligible || sj.failed) return;
-    const uint32_t lane = threadIdx.x & 63u;
-    const lzf_decompress_job job = c.jobs[j];
+//   is guaranteed to hold when the sub-batch is resolved: moved by the stager | 8 a sequence that stands alone in its sub-batch:
+//   one larger than a sub-batch, or a match whose source starts in the prefix and ends in the output | 9..12 run-length (offset 1, 2,
+//   4) of the sizes of 1..4 | 13 source wholly in the prefix: moved by the stager from `prefix`.
+// History: positions are absolute (the tiles' sums start at out_existing_len), so a source in the existing output is classed like any
+// other: inside the ring (the stager primes it) or older (class 7).  A job without a prefix gets the records it always got — from the
+// instruction stream it always had: the tiles' loop is compiled twice, HIST = false without a word about prefixes, and the kernel takes a
+// job to one or the other (with one body and a uniform `if (P)` around the additions the 980-block call took 16.3 ms instead of 16.0:
+// profiles/seg_history.txt).
+namespace {
+template <bool HIST>
+__device__ __forceinline__ void seg_records_tiles(const seg_ctx& c, const uint32_t j, const seg_job& sj, const lzf_decompress_job& job, const uint32_t lane,
+                                                  uint8_t* const stage, uint16_t* const list) {
     // (as DecodeJob of lzf_copy_helpers.h has them; the view itself moved three instructions here: profiles/copy_stage_one_ring.txt)
     cgu8* __restrict__ in = as_global(job.input);
     gu8* out = as_global(job.out);
@@ -844,6 +858,8 @@ __global__ __launch_bounds__(64) void lzf_seg_records_kernel(seg_ctx c) {
     LZF_GLOBAL u32x4* const recs = (LZF_GLOBAL u32x4*)c.recs + sj.rec_off;
     const uint32_t R = c.ring_bytes, kSpan = R / 8u, kAheadB = 3u * kSpan + 64u;
     const uint32_t rb = (uint32_t)(reinterpret_cast<uintptr_t>(job.out) & 15u);
+    // the prefix an offset can still reach (decompress.rs:80-99: a source in front of the output continues in the prefix's tail)
+    const uint32_t P = HIST ? __builtin_amdgcn_readfirstlane((uint32_t)job.prefix_len) : 0u;
     for (uint32_t t = blockIdx.x; t < sj.ntile; t += gridDim.x) {
         __syncthreads();
         const uint32_t n = tile_enumerate(c, j, t, lane, len, in, stage, list);
@@ -864,7 +880,7 @@ __global__ __launch_bounds__(64) void lzf_seg_records_kernel(seg_ctx c) {
             bool ok = act && !k.err;
             if (ok) {
                 if (lo > cap || cap - lo < k.L) ok = false;                                   // our buffer (literals)
-                else if (k.M && ((uint64_t)mo + k.M > limit || k.off == 0u || k.off > mo || cap - mo < k.M)) ok = false;   // :72-74, :83, :84-89, our buffer
+                else if (k.M && ((uint64_t)mo + k.M > limit || k.off == 0u || (k.off > mo && k.off - mo > P) || cap - mo < k.M)) ok = false;   // :72-74, :83, :84-89, our buffer
             }
             bad = bad || (act && !ok);
             if (ok) {
@@ -882,7 +898,11 @@ __global__ __launch_bounds__(64) void lzf_seg_records_kernel(seg_ctx c) {
             const uint32_t span = M < off ? M : off;
             const uint32_t s0 = mo - off, e0 = s0 + span;
             uint32_t lvl = has ? 1u : 0u;
-            const bool dep = has && e0 > ob;             // the source reaches into the batch
+            // a source that starts in the prefix (s0 is negative: wrapped) is moved by the stager, which waits for what it needs of the
+            // output: it depends on nothing here.  A source in the existing output is a source like any other, only final already.
+            bool pre = false;
+            if (HIST) pre = has && off > mo;
+            const bool dep = has && !pre && e0 > ob;     // the source reaches into the batch
             // (lane values are exchanged by ds_bpermute: no LDS memory, no address arithmetic — every lane is active here)
             auto from_lane = [](uint32_t l, uint32_t v) -> uint32_t { return (uint32_t)__builtin_amdgcn_ds_bpermute((int)((l & 63u) << 2), (int)v); };
             if (__any(dep)) {
@@ -917,6 +937,9 @@ __global__ __launch_bounds__(64) void lzf_seg_records_kernel(seg_ctx c) {
                 const uint32_t sob = __builtin_amdgcn_readlane(lo, a);
                 const uint32_t bb0 = first_lane(__ballot(lane >= a && lane < nb && endp - sob > kSpan));
                 uint32_t e = bb0 < nb ? bb0 : nb;
+                // a source that starts in the prefix and ends in the output (the few of a job: they cross one byte boundary) stands alone
+                // like a sequence larger than a sub-batch does: the stager copies it once everything in front of it is in HBM
+                if (HIST) { const uint32_t bs = first_lane(__ballot(lane >= a && lane < nb && pre && off - mo < M)); if (bs < e) e = bs; }
                 const bool giant = e == a;
                 if (giant) e = a + 1u;
                 const uint32_t oe = __builtin_amdgcn_readlane(endp, e - 1u);
@@ -930,7 +953,8 @@ __global__ __launch_bounds__(64) void lzf_seg_records_kernel(seg_ctx c) {
                         const uint32_t sy = s0 + rb, dy = mo + rb;
                         const uint32_t di = dy & (R - 1u), si = sy & (R - 1u);
                         const bool wrap = di + M > R || si + M > R;
-                        if (sy < lov) cls = 7u;
+                        if (pre) cls = 13u;
+                        else if (sy < lov) cls = 7u;
                         else if (M > 64u || wrap) cls = 6u;
                         else if (off < M) cls = (off == 1u || off == 2u || off == 4u) ? (M < 8u ? 9u : M <= 16u ? 10u : M <= 32u ? 11u : 12u) : 5u;
                         else cls = M < 8u ? 1u : M <= 16u ? 2u : M <= 32u ? 3u : 4u;
@@ -956,6 +980,21 @@ __global__ __launch_bounds__(64) void lzf_seg_records_kernel(seg_ctx c) {
         }
         if (__ballot(bad) && lane == 0u) c.st[j].failed = 1u;
     }
+}
+}  // namespace
+__global__ __launch_bounds__(64) void lzf_seg_records_kernel(seg_ctx c) {
+    __shared__ __attribute__((aligned(16))) uint8_t stage[kTileStage];
+    __shared__ uint16_t list[kTileTokMax + 64u];
+    const uint32_t j = (c.rec_by_len || c.grouped) ? seg_job_of(c, blockIdx.y) : blockIdx.y;
+    const seg_job sj = c.st[j];
+    if (!sj.eligible || sj.failed) return;
+    const uint32_t lane = threadIdx.x & 63u;
+    const lzf_decompress_job job = c.jobs[j];
+    // a prefix that an offset can still reach?  (existing output of 65 535 bytes or more hides it: the plan stage has the same rule)
+    if (__builtin_amdgcn_readfirstlane((uint32_t)(job.prefix_len != 0 && job.out_existing_len < kSegPrefixReach)))
+        seg_records_tiles<true>(c, j, sj, job, lane, stage, list);
+    else
+        seg_records_tiles<false>(c, j, sj, job, lane, stage, list);
 }
 
 // =====================================================================================================================
@@ -1488,7 +1527,13 @@ __global__ __launch_bounds__(128) void lzf_seg_resolve_pair_kernel(seg_ctx c) {
 #undef RT
     } else {
         // ================================================= STAGER =================================================
-        uint32_t fp = 0, fl = rb, safe = 0;              // filled up to (granule), flushed up to, own stores visible below
+        // History.  E0 = the biased end of the existing output, which is final (and visible) before the launch: nothing below it is ever
+        // stored, so the flush pointer and the previous sequence's end start there, and the head of its granule stays what it is.
+        // P = the prefix an offset can still reach (the records stage has the same rule), moved in from `prefix` by this wave.
+        const uint32_t E0 = __builtin_amdgcn_readfirstlane((uint32_t)job.out_existing_len) + rb;
+        const uint32_t P = __builtin_amdgcn_readfirstlane(job.out_existing_len >= kSegPrefixReach ? 0u : (uint32_t)job.prefix_len);
+        cgu8* const pfx_end = as_global(job.prefix) + P;
+        uint32_t fp = 0, fl = E0, safe = E0;             // filled up to (granule), flushed up to, own stores visible below
         uint32_t ticket = 0;                             // tickets published
         static_assert(NT <= 32, "the ends of the tickets in flight live in the lanes of one register");
         uint32_t endv = rb;                              // lane t % 64: biased end (rounded down to a granule) of published ticket t
@@ -1547,7 +1592,17 @@ __global__ __launch_bounds__(128) void lzf_seg_resolve_pair_kernel(seg_ctx c) {
 #endif
         u32x4 rA = u32x4{0, 0, 0, 0}, rB = u32x4{0, 0, 0, 0};
         if (n) { rA = recs[lane < n ? lane : n - 1u]; rB = recs[64u + lane < n ? 64u + lane : n - 1u]; }
-        uint32_t prev_end = rb;                          // biased end of the previous sequence
+        uint32_t prev_end = E0;                          // biased end of the previous sequence
+        // The ring primed with the tail of the existing output before the first ticket, as after a class-8 sequence: everything a record
+        // may have been classed "inside the ring" for — the records stage takes [fill pointer + fetch-ahead - R, ...) to be held, and the
+        // fill pointer is never below E0's granule — so R - fetch-ahead bytes in front of it.  The last granule holds the block's first
+        // bytes too: literals already in place, holes otherwise.
+        if (E0 != rb) {
+            const uint32_t keep = (uint32_t)R - (NS * kSpan + 64u);
+            const uint32_t g1 = (E0 + 15u) & ~15u;
+            fp = g1 > keep ? (g1 - keep) & ~15u : 0u;
+            fill_to(g1);
+        }
         // Sources older than the ring (class 7) of the NEXT batch's first sub-batch, loaded while this batch is staged: with the small
         // rings every sub-batch of a text block has some (offsets beyond ~20 KiB), and their round trip to HBM sat in the stager's
         // critical path — at four blocks per CU the stager spent 47 % of the block's time there and the resolver a third of its time
@@ -1586,11 +1641,20 @@ __global__ __launch_bounds__(128) void lzf_seg_resolve_pair_kernel(seg_ctx c) {
                     flush_range(fl, prev_end); if (prev_end > fl) fl = prev_end;
                     wave_store_fence();
                     if (g_M) {
-                        gu8* const src = outb + (g_dy - g_off);
-                        uint32_t pos = 0, av = g_off;
+                        // a source that starts in the prefix: its first bytes from there, byte by byte (any alignment); what is left is a
+                        // match at the same offset whose source is out[0 ..]
+                        uint32_t pos = 0;
+                        if (P && g_off + rb > g_dy) {
+                            const uint32_t pp = g_off + rb - g_dy;          // bytes of the source in front of out[0]
+                            pos = pp < g_M ? pp : g_M;
+                            for (uint32_t i = lane; i < pos; i += kWave) outb[g_dy + i] = pfx_end[(int32_t)i - (int32_t)pp];
+                            wave_store_fence();
+                        }
+                        gu8* const src = outb + (g_dy - g_off + pos);       // (32-bit sum: out[0] where the source started in the prefix)
+                        uint32_t av = g_off;
                         while (pos < g_M) {               // the same doubling as ring_match, through HBM
                             const uint32_t cc = av < g_M - pos ? av : g_M - pos;
-                            wave_copy_long(outb + g_dy + pos, src, cc, lane);
+                            wave_copy_long(outb + g_dy + pos, src, cc, lane);     // (cc <= the bytes between src and the destination: apart)
                             pos += cc; av += cc;
                             if (pos < g_M) wave_store_fence();
                         }
@@ -1682,6 +1746,22 @@ __global__ __launch_bounds__(128) void lzf_seg_resolve_pair_kernel(seg_ctx c) {
                             for (uint32_t i = lane; i < qM; i += kWave) {
                                 const uint32_t y = qs + (qo < qM ? i % qo : i);
                                 ring[(qd + i) & kMask] = y < fl ? (uint8_t)outb[y] : ring[y & kMask];
+                            }
+                        }
+                    }
+                    // sources in the prefix (class 13), which is final before the launch: straight into the ring, like the old sources above
+                    if (P) {
+                        const bool pin = sub == s_i && cls == 13u;
+                        if (__ballot(pin)) {
+                            uint32_t M_p = M, off_p = off, dy_p = dy;
+                            asm volatile("" : "+v"(M_p), "+v"(off_p), "+v"(dy_p));
+                            const uint32_t M = M_p, pp = off_p + rb - dy_p, di = dy_p & kMask;      // pp: the source starts this many bytes in front of out[0] (>= M)
+                            const bool own = pin && M <= 64u && di + M <= (uint32_t)R;
+                            if (own) put_small_glb(ring_a + di, pfx_end - pp, M);
+                            for (unsigned long long m = __ballot(pin && !own); m; m &= m - 1ull) {
+                                const uint32_t q = (uint32_t)__builtin_ctzll(m);
+                                const uint32_t qM = __builtin_amdgcn_readlane(M, q), qp = __builtin_amdgcn_readlane(pp, q), qd = __builtin_amdgcn_readlane(dy_p, q);
+                                for (uint32_t i = lane; i < qM; i += kWave) ring[(qd + i) & kMask] = pfx_end[(int32_t)i - (int32_t)qp];
                             }
                         }
                     }
