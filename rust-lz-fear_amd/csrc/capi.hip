@@ -362,6 +362,8 @@ int lzf_xxh32_batch(const uint8_t* const* d_ptrs, const uint64_t* d_lens, uint32
     if (rc < 0) return rc;
     // up to a few thousand buffers (block / content checksums of large blocks): one wave per buffer, streaming loads; beyond
     // that (many small blocks) 16 hashes per wave keep more chains per CU
+    // (8192 is XXH32_WAVE_KERNEL_MAX_N of tests/aux_kernel_cases.py: tests/test_gpu_aux_kernels.py,
+    //  test_xxh32_lane_kernel_on_both_sides_of_the_switch, calls with that many buffers and with one more.  Move both together.)
     if (n <= 8192u) LAUNCH(lzf::lzf_xxh32_wave_kernel, dim3(n), dim3(64), 0, static_cast<hipStream_t>(hip_stream), d_ptrs, d_lens, d_out, n);
     else LAUNCH(lzf::lzf_xxh32_kernel, dim3((n + 15) / 16), dim3(64), 0, static_cast<hipStream_t>(hip_stream), d_ptrs, d_lens, d_out, n);
     return LZF_OK;
