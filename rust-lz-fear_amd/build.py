@@ -133,6 +133,9 @@ def build_analysis_library(force=False, verbose=False):
 # The counters tests/test_gpu_copy_stage.py reads from results[].reserved: the pair kernel's match rounds with the fed kernel's batches, and the
 # pair kernel's batches.  Two instrumented analysis builds, made with the others so that the GPU tests find them built.
 COUNTER_BUILDS = (("LZF_DBG_ROUNDS=1", "LZF_DBG_FED_COUNT=0"), ("LZF_DBG_ROUNDS=2",))
+# The fed kernel's count of the overlapping cooperative matches that took the mask form of the byte loop (lz4_decompress_batch_phase.inc), per job in results[].reserved:
+# tests/test_gpu_fed_periodic.py compares it with a host model.  (A name of its own: COUNTER_BUILDS is a pair, and unpacked as one.)
+FED_PERIODIC_COUNTER_BUILD = ("LZF_DBG_FED_COUNT=4",)
 # The analysis flavour with the parse kernel's plain-hop loop in C++ instead of hand-written assembly: tests/test_gpu_parse_hop.py
 # compares its bit maps with the product loop's, word for word.
 PARSE_TWIN_BUILD = ("LZF_ANALYSIS", "LZF_SEG_NOASM")

@@ -421,6 +421,9 @@
 #if defined(LZF_DBG_ROUNDS) && defined(LZF_DBG_ROUNDS_HERE)   // analysis: iterations of this loop (match rounds + cooperative matches) and batches, per job
                         ++dbg_rounds;
 #endif
+#if defined(LZF_FED_DECODE) && defined(LZF_DBG_FED_COUNT)
+                        ++dbg_fed[3];
+#endif
                         const uint32_t f = (uint32_t)__builtin_ctzll(unresolved);
                         const unsigned long long bit = 1ull << f;
                         if (solo_mask & bit) {
@@ -467,9 +470,25 @@
                                 if (i2 < jm) rg.ring[RIDX(jo + i2)] = b2;
                                 if (i3 < jm) rg.ring[RIDX(jo + i3)] = b3;
                             }
+#if defined(LZF_FED_DECODE)
+                        } else if ((LZF_DBG_SKIP & 64) && joff <= 8u && ((0x116u >> joff) & 1u)) {      // (analysis: what the moves of these matches cost; wrong output)
+#endif
                         } else {                                            // overlapping: period-`offset` addressing
+#if defined(LZF_FED_DECODE) && !defined(LZF_FED_NO_PERIODIC)
+                            // (an offset that is a power of two — 1, 2, 4 and 8 are 95 % of these matches on the Silesia stand-in — needs neither
+                            //  of the two divisions: lane % joff is a mask, and kWave % joff is 0 up to 64 and kWave beyond, the same mask of kWave)
+                            uint32_t rr = lane & (joff - 1u), adv = kWave & (joff - 1u);
+                            if ((joff & (joff - 1u)) != 0u) {
+                                asm volatile("");      // (both divisions stay in here: hipcc otherwise starts them in front of the test)
+                                rr = lane % joff; adv = kWave % joff;
+                            }
+#if defined(LZF_DBG_FED_COUNT)
+                            dbg_fed[4] += (joff & (joff - 1u)) == 0u ? 1u : 0u;
+#endif
+#else
                             uint32_t rr = lane % joff;
                             const uint32_t adv = kWave % joff;
+#endif
                             for (uint32_t i = lane; i < jm; i += kWave) {
                                 rg.ring[RIDX(jo + i)] = rg.ring[RIDX(js + rr)];
                                 rr += adv; if (rr >= joff) rr -= joff;

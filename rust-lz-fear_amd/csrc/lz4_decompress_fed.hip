@@ -107,8 +107,8 @@ __global__ LZF_FED_BOUNDS void lzf_decompress_fed_kernel(fed_args a) {      // (
     bool bailed = false, parked = false;
     uint32_t o = 0;
     PhaseTimers ph;
-#ifdef LZF_DBG_FED_COUNT   // analysis: [0] batches, [1] windows listed from the map, [2] windows walked, of this wave's share of the job (LZF_FED_PIECES=1: the job) -> results[].reserved
-    uint32_t dbg_fed[3] = {0u, 0u, 0u};
+#ifdef LZF_DBG_FED_COUNT   // analysis: [0] batches, [1] windows listed from the map, [2] windows walked, [3] trips of the match-round loop, [4] overlapping cooperative matches whose offset is a power of two (no division), of this wave's share of the job (LZF_FED_PIECES=1: the job) -> results[].reserved
+    uint32_t dbg_fed[5] = {0u, 0u, 0u, 0u, 0u};
 #endif
     if (LZF_DECODE_JOB_OUT_OF_CONTRACT(job)) continue;      // (LZF_CONTRACT: the pair kernel says so)
     {

@@ -6,7 +6,10 @@
 //   exact  a match moves as soon as no unresolved match of the batch writes into its source (dependency levels)
 //   range  a match moves as soon as every match between the sequence that produces its first source byte and the one that produces
 //          its last is resolved (what two binary searches over the batch's output positions give a lane)
-// and the other kinds (far: read back from HBM; cooperative: overlapping or long) per batch.
+//   H+p    the H rule with the short overlapping matches of period 1, 2, 4, 8 (M <= 64) as own-lane matches whose source ends where they
+//          start (profiles/fed_periodic_matches.txt: built, measured slower, not kept)
+// and the other kinds (far: read back from HBM; cooperative: overlapping or long) per batch, with a census of the cooperative ones:
+// overlapping by length, long, and the offsets and lengths of the overlapping ones (a power-of-two offset needs no division in the byte loop).
 //   gcc -O2 -o /tmp/round_rules tools/round_rules.c oracle/lzf_oracle.c && /tmp/round_rules /tmp/silesia_mix.bin
 // ANALYSIS TOOL (links the oracle): not part of the product.
 #include <stdio.h>
@@ -40,6 +43,7 @@ int main(int argc, char** argv) {
     uint8_t* comp = malloc(BS + 65536);
     double batches = 0, nsq = 0, rH = 0, rE = 0, rR = 0, far = 0, coop = 0, solo = 0, nomatch = 0, lvl1 = 0, rH1 = 0;
     double hist[3][17] = {{0}};
+    double rHp = 0, coopHp = 0, ov_short = 0, ov_long = 0, co_long = 0, co_other = 0, ov_off[5] = {0}, ov_pow2 = 0, ov_len[3] = {0};      // ov_off: 1, 2, 4, 8, else
     const uint32_t kSpanMax = RING / 3, kNearHist = RING - kSpanMax;
     for (size_t b = 0; b < nblk; ++b) {
         size_t n = total - b * BS < BS ? total - b * BS : BS, clen = 0;
@@ -60,25 +64,36 @@ int main(int argc, char** argv) {
                 if (!s->M) { kind[j] = 0; ++nomatch; continue; }
                 const uint32_t sp = s->M < s->off ? s->M : s->off, s0 = s->mo - s->off;
                 if (s0 + sp <= near_lo) { kind[j] = 2; ++far; continue; }
-                if (s0 >= near_lo && s->M <= s->off && s->M <= 64) { kind[j] = 1; ++solo; } else { kind[j] = 3; ++coop; }
+                if (s0 >= near_lo && s->M <= s->off && s->M <= 64) { kind[j] = 1; ++solo; continue; }
+                kind[j] = 3; ++coop;
+                if (s0 >= near_lo && s->M > s->off) {             // near, overlapping
+                    const int p8 = s->off == 1 || s->off == 2 || s->off == 4 || s->off == 8;
+                    if (s->M <= 64) ++ov_short; else ++ov_long;
+                    ov_off[s->off == 1 ? 0 : s->off == 2 ? 1 : s->off == 4 ? 2 : s->off == 8 ? 3 : 4] += 1;
+                    if ((s->off & (s->off - 1)) == 0) ++ov_pow2;
+                    if (s->M <= 16) ++ov_len[0]; else if (s->M >= 33 && s->M <= 64) ++ov_len[1]; else if (s->M > 256) ++ov_len[2];
+                    if (p8 && s->M <= 64) kind[j] = 4;            // H+p: an own-lane match (the H rule below counts it as cooperative)
+                } else if (s0 >= near_lo) ++co_long; else ++co_other;
             }
-            // H rule over solo + cooperative (cooperative ones take a round of their own when they are the first unresolved)
-            {
+            // H rule over solo + cooperative (cooperative ones take a round of their own when they are the first unresolved); second pass
+            // (H+p): kind 4 moves like a solo match whose source ends at its own start
+            for (int pass = 0; pass < 2; ++pass) {
                 uint8_t done[64]; int left = 0, r = 0;
-                for (size_t j = 0; j < nb; ++j) { done[j] = !(kind[j] == 1 || kind[j] == 3); left += !done[j]; }
+                for (size_t j = 0; j < nb; ++j) { done[j] = !(kind[j] == 1 || kind[j] >= 3); left += !done[j]; }
                 while (left) {
                     size_t fI = 0; while (done[fI]) ++fI;
-                    if (kind[fI] == 3) { done[fI] = 1; --left; ++r; continue; }
+                    if (kind[fI] == 3 || (kind[fI] == 4 && !pass)) { done[fI] = 1; --left; ++r; if (pass) ++coopHp; continue; }
                     const uint32_t H = seqs[i0 + fI].mo; int moved = 0;
-                    for (size_t j = fI; j < nb; ++j) if (!done[j] && kind[j] == 1) {
+                    for (size_t j = fI; j < nb; ++j) if (!done[j] && (kind[j] == 1 || (kind[j] == 4 && pass))) {
                         const seq_t* s = &seqs[i0 + j];
-                        if (s->mo - s->off + s->M <= H) { done[j] = 2; ++moved; }
+                        if (s->mo - s->off + (s->M < s->off ? s->M : s->off) <= H) { done[j] = 2; ++moved; }
                     }
                     for (size_t j = 0; j < nb; ++j) if (done[j] == 2) done[j] = 1;
                     left -= moved; ++r;
                 }
-                rH += r; hist[0][r > 16 ? 16 : r] += 1;
+                if (pass) rHp += r; else { rH += r; hist[0][r > 16 ? 16 : r] += 1; }
             }
+            for (size_t j = 0; j < nb; ++j) if (kind[j] == 4) kind[j] = 3;
             // exact levels / range levels: level(j) = 1 + max level of the matches of the batch (any kind but far) that write into j's source
             int maxE = 0, maxR = 0;
             for (size_t j = 0; j < nb; ++j) {
@@ -106,6 +121,11 @@ int main(int argc, char** argv) {
     }
     printf("batches %.0f, sequences %.0f (%.1f per batch): no match %.3f, solo %.3f, far %.3f, cooperative %.3f per sequence\n", batches, nsq, nsq / batches, nomatch / nsq, solo / nsq, far / nsq, coop / nsq);
     printf("rounds per batch: H rule %.2f | exact levels %.2f | range levels %.2f ; matches at exact level 1: %.3f of solo + cooperative\n", rH / batches, rE / batches, rR / batches, lvl1 / (solo + coop));
+    printf("H+p (periods 1, 2, 4, 8 with M <= 64 own-lane): %.2f rounds, %.3f cooperative matches per batch\n", rHp / batches, coopHp / batches);
+    printf("cooperative per batch: %.3f = overlapping M <= 64 %.3f + overlapping M > 64 %.3f + long, not overlapping %.3f + straddling or prefix %.3f\n", coop / batches, ov_short / batches, ov_long / batches, co_long / batches, co_other / batches);
+    { const double ov = ov_short + ov_long;
+      printf("overlapping: offset 1 %.1f%%, 2 %.1f%%, 4 %.1f%%, 8 %.1f%%, else %.1f%%; a power of two %.1f%% (%.3f per batch); M <= 16 %.1f%%, 33..64 %.1f%%, > 256 %.1f%%\n", 100 * ov_off[0] / ov, 100 * ov_off[1] / ov,
+             100 * ov_off[2] / ov, 100 * ov_off[3] / ov, 100 * ov_off[4] / ov, 100 * ov_pow2 / ov, ov_pow2 / batches, 100 * ov_len[0] / ov, 100 * ov_len[1] / ov, 100 * ov_len[2] / ov); }
     for (int k = 0; k < 3; ++k) { printf("%s:", k == 0 ? "H    " : k == 1 ? "exact" : "range"); for (int r = 0; r <= 16; ++r) printf(" %5.1f%%", 100.0 * hist[k][r] / batches); printf("\n"); }
     return 0;
 }
