@@ -65,6 +65,20 @@ pub const LZF_STREAM_NO_CONTENT_SIZE: u64 = u64::MAX;
 pub const LZF_SFRAME_COMPLETE: u32 = 1;                // ended at its EndMark with LZF_OK (content checksum not verified)
 pub const LZF_SFRAME_BEHIND_STOP: u32 = 2;             // the stream rule never reaches it: an earlier frame ended the stream
 
+/// One entry of a frame's block index (lzf_frame_block_index_device), 48 bytes.
+#[repr(C)] #[derive(Default, Clone, Copy)]
+pub struct lzf_frame_block {
+    pub in_off: u64, pub out_off: u64, pub out_len: u64,
+    pub in_len: u32, pub want_sum: u32, pub block_maxsize: u32,
+    pub status: i32, pub flags: u32,                   // LZF_FBLOCK_*
+    pub reserved: u32,
+}
+pub const LZF_FBLOCK_STORED: u32 = 1;                  // stored raw: the run decode copies it
+pub const LZF_FBLOCK_HAS_SUM: u32 = 2;                 // a block checksum word follows the payload
+pub const LZF_FBLOCK_LINKED: u32 = 4;                  // linked-block frame: needs the blocks before it
+pub const LZF_FBLOCK_DELIVERED: u32 = 8;               // the reader delivers this block: no stop at it or before it
+pub const LZF_FBLOCK_BEHIND_STOP: u32 = 16;            // an earlier block stopped the frame; out_off = the frame's out_len
+
 #[repr(C)]
 #[derive(Default, Clone, Copy)]
 pub struct lzf_chain_state { pub length: u64, pub dead: u32, pub reserved: u32 }
@@ -158,6 +172,21 @@ extern "C" {
                                                      d_n_frames: *mut u64, d_n_listed: *mut u64, hip_stream: *mut c_void) -> c_int;
     // host only: frames [first, first + count) of an index (host copy) whose output meets the bytes [a, b) of the stream's output
     pub fn lzf_stream_index_locate(index: *const lzf_stream_frame, n: usize, a: u64, b: u64, first: *mut usize, count: *mut usize) -> c_int;
+    // the block index of a frame and the decode of runs of its blocks: lzf_frame_decompressed_size_device's results and, with room for
+    // lzf_frame_block_count_device's number of entries per frame, every block's lzf_frame_block; runs of consecutive DELIVERED entries of
+    // an independent-block frame (host copies) decode straight to their places.  The content checksum is never verified by these calls.
+    pub fn lzf_frame_block_count_device(n_frames: u32, d_in: *const *const u8, in_len: *const usize, n_found: *mut usize,
+                                        hip_stream: *mut c_void) -> c_int;
+    pub fn lzf_frame_block_index_device(n_frames: u32, d_in: *const *const u8, in_len: *const usize, dict_len: usize,
+                                        d_index: *const *mut lzf_frame_block, index_cap: *const usize,
+                                        d_out_len: *mut u64, d_consumed: *mut u64, d_status: *mut i32, d_n_listed: *mut u64,
+                                        hip_stream: *mut c_void) -> c_int;
+    // host only: the delivered blocks [first, first + count) of an index (host copy) whose output meets the bytes [a, b) of the frame's output
+    pub fn lzf_block_index_locate(index: *const lzf_frame_block, n: usize, a: u64, b: u64, first: *mut usize, count: *mut usize) -> c_int;
+    pub fn lzf_frame_decompress_blocks_device(n_runs: u32, d_in: *const *const u8, in_len: *const usize,
+                                              runs: *const *const lzf_frame_block, count: *const usize,
+                                              d_dict: *const u8, dict_len: usize, d_out: *const *mut u8, out_cap: *const usize,
+                                              d_out_len: *mut u64, d_status: *mut i32, hip_stream: *mut c_void) -> c_int;
     pub fn lzf_frame_release_scratch();
     pub fn lzf_frame_set_host_threads(n: u32);
     pub fn lzf_frame_set_memory_budget(bytes: usize);

@@ -356,6 +356,93 @@ int lzf_frame_stream_decompressed_size_device(uint32_t n_streams, const uint8_t*
  * the ABI: decode the frames, slice the output.  LZF_OK, or LZF_E_INVALID for a NULL argument. */
 int lzf_stream_index_locate(const lzf_stream_frame* index, size_t n, uint64_t a, uint64_t b, size_t* first, size_t* count);
 
+/* ---- the block index of a frame, and the decode of runs of its blocks ----------------------------------------------------
+ * The stream index gives random access frame by frame; a frame of independent blocks (what compress writes by default: one
+ * frame of 4 MiB blocks, src/framed/compress.rs:44-55) gives it block by block: every block decodes on its own, behind the
+ * dictionary alone.  lzf_frame_block_index_device is lzf_frame_decompressed_size_device that also lists the blocks;
+ * lzf_block_index_locate finds the blocks that hold a byte range; lzf_frame_decompress_blocks_device decodes runs of
+ * consecutive blocks straight to their places.  Byte ranges stay out of the ABI: decode the blocks, slice the output.
+ *
+ * Entry k of frame f describes block k of the structural walk (lzf_frame_block_count_device's number; truncated input ends the
+ * list where the walk ends; 0 entries for a frame whose header fails):
+ *   in_off, in_len, want_sum, block_maxsize   where the payload lies in the frame, the checksum word behind it, the header's size
+ *   out_off   the sum of out_len over the blocks before it: where the decode puts its output.
+ *   out_len   the block's exact decoded length, a dictionary of dict_len bytes behind it (a stored block: in_len).  Unspecified
+ *             where status is a codec error or LZF_F_BLOCK_CHECKSUM_FAIL, and behind a stop in a linked-block frame.
+ *   status    what the block does to the reader on its own: LZF_OK, a codec error 1..4, LZF_F_BLOCK_CHECKSUM_FAIL, or
+ *             LZF_F_BLOCK_SIZE_OVERFLOW (it decodes past block_maxsize).
+ *   flags     LZF_FBLOCK_DELIVERED: the reader delivers the block: neither it nor a block before it stops the frame.  The first
+ *             block without it is the stopping one (a status other than LZF_OK, or the empty block at which the Read adapter
+ *             stops, which is LZF_OK): its status is the frame's, its out_off the frame's out_len.  Every block behind it has
+ *             LZF_FBLOCK_BEHIND_STOP and out_off = the frame's out_len.  Every block of a linked-block frame has
+ *             LZF_FBLOCK_LINKED: its sizes come from the size query's lock-step chain, and it decodes only behind the blocks
+ *             before it.
+ * Conventions of lzf_frame_decompressed_size_device: d_in / in_len are HOST arrays, d_in[f] a DEVICE address.  d_index /
+ * index_cap: HOST arrays of n_frames entries, d_index[f] the DEVICE address (8-byte aligned) of room for index_cap[f] entries;
+ * at most index_cap[f] entries are written and nothing behind them; both NULL: sizes only.  d_out_len, d_consumed (may be NULL)
+ * and d_status are exactly what lzf_frame_decompressed_size_device reports for the same bytes and dict_len — its one exception
+ * included: the content checksum is not verified; d_n_listed (may be NULL): the blocks found, whatever the capacity.  All four are
+ * DEVICE arrays written in stream order.  The host waits as the size query does (scan summary, block table) and no more; behind
+ * the size query's own work one more kernel, one wavefront per frame, runs the delivery's stop rules again and writes the
+ * entries.  Not graph-capturable. */
+#define LZF_FBLOCK_STORED      1u   /* stored raw: the run decode copies it */
+#define LZF_FBLOCK_HAS_SUM     2u   /* a block checksum word follows the payload */
+#define LZF_FBLOCK_LINKED      4u   /* linked-block frame: needs the blocks before it */
+#define LZF_FBLOCK_DELIVERED   8u   /* the reader delivers this block: no stop at it or before it */
+#define LZF_FBLOCK_BEHIND_STOP 16u  /* an earlier block stopped the frame; out_off = the frame's out_len */
+typedef struct lzf_frame_block {    /* 48 bytes */
+    uint64_t in_off;        /* payload start in the frame (behind the length word) */
+    uint64_t out_off;       /* where the block's output starts in the frame's output */
+    uint64_t out_len;       /* exact decoded length (stored: in_len); unspecified on a codec error */
+    uint32_t in_len;        /* payload bytes */
+    uint32_t want_sum;      /* the checksum word, 0 without HAS_SUM */
+    uint32_t block_maxsize;
+    int32_t  status;        /* what this block does to the reader: LZF_OK, 1..4, LZF_F_BLOCK_CHECKSUM_FAIL,
+                               LZF_F_BLOCK_SIZE_OVERFLOW; the stopping block carries the frame's status */
+    uint32_t flags;         /* LZF_FBLOCK_* */
+    uint32_t reserved;      /* 0 */
+} lzf_frame_block;
+/* Blocks the structural walk finds per frame (0 for a header that fails): the entries the index call can list.  n_found: a HOST
+ * array.  Synchronous, one wait (the scan summary). */
+int lzf_frame_block_count_device(uint32_t n_frames, const uint8_t* const* d_in, const size_t* in_len,
+                                 size_t* n_found, void* hip_stream);
+int lzf_frame_block_index_device(uint32_t n_frames, const uint8_t* const* d_in, const size_t* in_len, size_t dict_len,
+                                 lzf_frame_block* const* d_index, const size_t* index_cap,
+                                 uint64_t* d_out_len, uint64_t* d_consumed, int32_t* d_status, uint64_t* d_n_listed,
+                                 void* hip_stream);
+/* Host only, no device: blocks [*first, *first + *count) of an index (a host copy of n entries) whose output meets the bytes
+ * [a, b) of the frame's output, among the LZF_FBLOCK_DELIVERED entries.  lzf_stream_index_locate's search and semantics: a >= b,
+ * n == 0 or a range wholly behind the delivered output give *count = 0; blocks of zero length are never at an edge of the
+ * result.  LZF_OK, or LZF_E_INVALID for a NULL argument. */
+int lzf_block_index_locate(const lzf_frame_block* index, size_t n, uint64_t a, uint64_t b, size_t* first, size_t* count);
+/* Decodes runs of consecutive blocks.  Run r is count[r] consecutive entries of the index of the frame at d_in[r] (in_len[r]
+ * bytes), given as HOST copies: runs[r] points at them.  Block k of the run is decoded to d_out[r] + (e[k].out_off -
+ * e[0].out_off); the run's total is the sum of its out_len.  d_in, in_len, runs, count, d_out, out_cap: HOST arrays of n_runs
+ * entries; d_in[r], d_out[r], d_dict: DEVICE addresses.  Runs may share a frame; outputs must not overlap each other or any
+ * input.  d_out_len, d_status: DEVICE arrays of n_runs entries, written in stream order.
+ * The host plans everything from the entries and reads nothing back: no wait except for its own upload of job lists.  A call
+ * that holds an entry without LZF_FBLOCK_DELIVERED or with LZF_FBLOCK_LINKED (block k of a linked frame needs every block before
+ * it: decode the frame), in_off + in_len (+ 4 with HAS_SUM) beyond in_len[r], in_len or out_len above block_maxsize, a stored
+ * block whose out_len is not its in_len, or out_off values that are not contiguous enqueues nothing and returns LZF_E_INVALID.
+ * out_cap[r] below the run's total gives that run LZF_OUT_CAPACITY, out_len 0 and no writes; count[r] == 0 is LZF_OK, 0.
+ * Enqueued: the block checksums (lzf_xxh32_batch over the payloads, compared with the word read from the input on the device,
+ * not with the entry's copy), the decode (lzf_decompress_batch_sized, every block at its final place with out_cap =
+ * output_limit = out_len and d_dict as its prefix), the stored copies (lzf_copy_ranges) and one kernel, one wavefront per run,
+ * that folds the results.  No output slots, no delivery copy, no passes of the memory budget; scratch (jobs, results, sums)
+ * comes from the stream-ordered pool.
+ *   d_status[r]   the first of, in block order: LZF_F_BLOCK_CHECKSUM_FAIL; a codec status 1..4; LZF_CONTRACT where a block's
+ *                 result differs from its entry (another decoded length, or no room in out_len bytes: the index does not
+ *                 describe these bytes).  LZF_OK otherwise.
+ *   d_out_len[r]  the bytes of the blocks before that one, or the total on LZF_OK.
+ * Nothing outside d_out[r][0, total) is ever written; behind a failing block [d_out_len, total) is unspecified.
+ * The content checksum is NEVER verified by this call: it needs the whole content.  lzf_frame_decompress_device_many remains
+ * the call that verifies it.  Not graph-capturable. */
+int lzf_frame_decompress_blocks_device(uint32_t n_runs, const uint8_t* const* d_in, const size_t* in_len,
+                                       const lzf_frame_block* const* runs, const size_t* count,
+                                       const uint8_t* d_dict, size_t dict_len,
+                                       uint8_t* const* d_out, const size_t* out_cap,
+                                       uint64_t* d_out_len, int32_t* d_status, void* hip_stream);
+
 /* lzf_frame_compress_stream_device: input s becomes max(1, ceil(in_len[s] / frame_bytes)) frames, written back to back into
  * d_out[s]: the bytes are the concatenation of lzf_frame_compress_many's output for each piece of frame_bytes bytes (the last
  * one shorter) with the same settings and dictionary.  With s->has_content_size every frame's header carries its own piece's

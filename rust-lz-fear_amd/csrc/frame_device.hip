@@ -27,12 +27,17 @@
 // lzf_frame_stream_decompressed_size_device: the stream scan, the size query over every frame it lists (size_frames, the body of
 // lzf_frame_decompressed_size_device), the decode's fold, and lzf_stream_index_kernel (lzf_stream_index.h's rules, one wavefront
 // per stream) for the frame index; lzf_stream_index_locate is that header's locate on the host.
+// lzf_frame_block_index_device: the size query over the caller's frames, then lzf_frame_block_index_kernel — the delivery body
+// in its index mode, over the size query's descriptors, job results and block checksums — for the block index of every frame
+// (lzf_block_index.h's rules).  lzf_frame_decompress_blocks_device: runs of consecutive blocks, planned from the caller's copies of
+// the entries alone (no scan, no read-back): checksums, the decode of every block at its final place with its exact length as
+// capacity, the stored copies, and lzf_block_run_fold_kernel, one wavefront per run, for status and out_len.
 //
 // One copy of each rule.  The walk is lzf_frame_scan.h's (the host driver runs the same header).  The passes of the memory budget
 // are frame_jobs.h's split_passes, for all four *_many drivers.  The decode plan is plan_frames (the scan's summaries and table
 // as frame_jobs.h's frames) and plan_pass (jobs, descriptors, checksum lists): decode_frames runs them per pass, the size query
 // once with sizes_only.  The small arrays of a call travel in one Meta: one image, one upload, one event, typed accessors.  The
-// four one-wavefront-per-frame / per-stream kernels share wave_incl_scan.
+// one-wavefront-per-frame / per-stream / per-run kernels share wave_incl_scan.
 #include <hip/hip_runtime.h>
 #include <cstring>
 #include <map>
@@ -41,6 +46,7 @@
 #include "lzf_frame_scan.h"
 #include "lzf_stream_walk.h"
 #include "lzf_stream_index.h"
+#include "lzf_block_index.h"
 #include "frame_jobs.h"
 #include "lzf_frame_layout.h"
 #include "lzf_chain_step.h"
@@ -161,7 +167,9 @@ __global__ __launch_bounds__(64) void lzf_frame_deliver_kernel(const DFrameDesc*
                                                                uint64_t* __restrict__ h_len, uint32_t* __restrict__ h_check,
                                                                int32_t* __restrict__ d_status, uint64_t* __restrict__ d_out_len, uint64_t* __restrict__ d_consumed) {
 #define LZF_DELIVER_COUNT_ONLY 0
+#define LZF_DELIVER_INDEX 0
 #include "frame_deliver_body.inc"
+#undef LZF_DELIVER_INDEX
 #undef LZF_DELIVER_COUNT_ONLY
 }
 // The size query's twins: delivery without the lists, and the chain step that carries the history as a length (lzf_chain_step.h).
@@ -170,7 +178,24 @@ __global__ __launch_bounds__(64) void lzf_frame_size_deliver_kernel(const DFrame
                                                                     const uint32_t* __restrict__ sums,
                                                                     int32_t* __restrict__ d_status, uint64_t* __restrict__ d_out_len, uint64_t* __restrict__ d_consumed) {
 #define LZF_DELIVER_COUNT_ONLY 1
+#define LZF_DELIVER_INDEX 0
 #include "frame_deliver_body.inc"
+#undef LZF_DELIVER_INDEX
+#undef LZF_DELIVER_COUNT_ONLY
+}
+// The block index of a frame (lzf_frame_block_index_device): the delivery body once more, counting only, in its index mode.  One
+// wavefront per frame, 64 blocks per round; the running output offset and the stop carry from round to round as in the delivery,
+// and the rounds go on behind the stop.  Lane i writes entry i of the round (lzf_block_index.h's fill_entry, 48 bytes in vector
+// stores) if the caller's room holds it; lane 0 writes the number of blocks found.
+__global__ __launch_bounds__(64) void lzf_frame_block_index_kernel(const DFrameDesc* __restrict__ frames, const DBlkDesc* __restrict__ blks,
+                                                                   const lzf_decompress_job* __restrict__ jobs, const lzf_job_result* __restrict__ res,
+                                                                   const uint32_t* __restrict__ sums,
+                                                                   lzf_frame_block* const* __restrict__ x_index, const uint64_t* __restrict__ x_cap,
+                                                                   uint64_t* __restrict__ d_n_listed) {
+#define LZF_DELIVER_COUNT_ONLY 1
+#define LZF_DELIVER_INDEX 1
+#include "frame_deliver_body.inc"
+#undef LZF_DELIVER_INDEX
 #undef LZF_DELIVER_COUNT_ONLY
 }
 __global__ __launch_bounds__(256) void lzf_chain_size_step_kernel(const lzf_chain_step* __restrict__ steps, lzf_chain_state* __restrict__ state,
@@ -408,6 +433,56 @@ __global__ __launch_bounds__(64) void lzf_stream_pack_kernel(const CSeg* __restr
 __global__ __launch_bounds__(256) void lzf_frame_patch_kernel(uint8_t* const* __restrict__ at, const uint32_t* __restrict__ val, uint32_t n) {
     const uint32_t k = blockIdx.x * 256u + threadIdx.x;
     if (k < n && at[k]) lzf_layout::wr32(at[k], val[k]);
+}
+
+// ---- runs of blocks (lzf_frame_decompress_blocks_device): per run and per block, for the fold kernel
+struct RRunDesc { uint32_t blk0, nb; int32_t status0; uint32_t run; };      // status0: LZF_OK, or LZF_OUT_CAPACITY (then nb = 0)
+struct RBlkDesc {
+    const uint8_t* sum_at;      // the block's checksum word in the input (any alignment), NULL: none
+    uint64_t out_len;           // the entry's
+    uint32_t job;               // decode job of the call, kNone: stored
+    uint32_t sum_idx;           // block checksum of the call, kNone: none
+};
+static_assert(sizeof(RBlkDesc) == 24, "run block descriptor");
+
+// The results of the runs, one wavefront per run, 64 blocks per round.  Per block, in block order: the checksum of its payload
+// against the word in the input, its job's status, its job's length against the entry's.  The first block that fails fixes the
+// run's status; out_len is the exclusive prefix of the entries' lengths at that block (wave_incl_scan within the round, the
+// running sum from round to round), or the total.  A stored block cannot fail but for its checksum.
+__global__ __launch_bounds__(64) void lzf_block_run_fold_kernel(const RRunDesc* __restrict__ runs, const RBlkDesc* __restrict__ blks,
+                                                                const lzf_job_result* __restrict__ res, const uint32_t* __restrict__ sums,
+                                                                int32_t* __restrict__ d_status, uint64_t* __restrict__ d_out_len) {
+    const RRunDesc R = runs[blockIdx.x];
+    const uint32_t lane = threadIdx.x;
+    uint64_t w = 0;
+    int st = R.status0;
+    for (uint32_t base = 0; base < R.nb; base += 64u) {
+        const uint32_t i = base + lane;
+        const bool act = i < R.nb;
+        uint64_t n = 0;
+        int code = LZF_OK;
+        if (act) {
+            const RBlkDesc b = blks[R.blk0 + i];
+            n = b.out_len;
+            if (b.sum_idx != kNone && sums[b.sum_idx] != lzf_scan::rd32(b.sum_at)) code = LZF_F_BLOCK_CHECKSUM_FAIL;
+            else if (b.job != kNone) {
+                const lzf_job_result r = res[b.job];
+                if (r.status >= LZF_UNEXPECTED_END && r.status <= LZF_INVALID_DEDUP_OFFSET) code = r.status;
+                else if (r.status != LZF_OK || r.out_len != n) code = LZF_CONTRACT;      // (LZF_OUT_CAPACITY: no room in out_len bytes)
+            }
+        }
+        const uint64_t incl = wave_incl_scan(n, lane);
+        const uint64_t fails = __ballot(act && code != LZF_OK);
+        if (fails) {
+            const int first = (int)__builtin_ctzll(fails);
+            st = __shfl(code, first, 64);
+            w += __shfl(incl - n, first, 64);
+            break;
+        }
+        w += __shfl(incl, 63, 64);
+    }
+    if (lane != 0) return;
+    d_status[R.run] = st; d_out_len[R.run] = w;
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
@@ -832,15 +907,16 @@ __global__ __launch_bounds__(64) void lzf_stream_index_kernel(const uint8_t* con
 // lzf_chain_size_step_kernel between the steps), lzf_frame_size_deliver_kernel for the delivery.  No output slots, hence one pass
 // whatever the memory budget is.  `more(sc)` puts what the caller's own kernels behind this need into the call's image before
 // its one upload; the caller ends with meta.wait().  Where every header failed and `more` added nothing, nothing is uploaded:
-// the scan kernel wrote the results.
+// the scan kernel wrote the results.  `P` is the call's one pass: a caller whose kernels read the descriptors, the job results
+// or the block checksums (the block index) finds them there once the call has returned; P.n_frames == 0: nothing was planned.
 template <class More>
 int size_frames(uint32_t n, const uint8_t* const* d_in, const size_t* in_len, size_t dict_len, uint64_t* d_out_len, uint64_t* d_consumed,
-                int32_t* d_status, hipStream_t st, Scan& sc, Meta& meta, More&& more) {
+                int32_t* d_status, hipStream_t st, Scan& sc, Meta& meta, Pass& P, More&& more) {
     // ---- scan: summaries (wait 1), block table (wait 2)
     RC_TRY(scan_summaries(n, d_in, in_len, st, sc, d_status, d_out_len, d_consumed));
     RC_TRY(scan_table(n, st, sc));
     // ---- the decode's plan with sizes_only; the content checksum needs the content: not verified
-    Pass P; P.f0 = 0; P.f1 = n;
+    P.f0 = 0; P.f1 = n;
     plan_frames(P, d_in, sc);
     if (!P.jf.empty()) RC_TRY(plan_pass(P, sc, DecodeCall{true, nullptr, nullptr, dict_len, nullptr, nullptr, nullptr}, meta));
     more(sc);
@@ -952,7 +1028,8 @@ int lzf_frame_decompressed_size_device(uint32_t n_frames, const uint8_t* const* 
     if (!d_consumed) { if (!own_consumed.get(8 * (size_t)n_frames)) return LZF_E_HIP; d_consumed = own_consumed.at<uint64_t>(0); }
     Scan sc(st);
     Meta meta(st);
-    RC_TRY(size_frames(n_frames, d_in, in_len, dict_len, d_out_len, d_consumed, d_status, st, sc, meta, [](const Scan&) {}));
+    Pass P;
+    RC_TRY(size_frames(n_frames, d_in, in_len, dict_len, d_out_len, d_consumed, d_status, st, sc, meta, P, [](const Scan&) {}));
     return meta.wait();                              // the image has left host memory; the kernels run on
 }
 
@@ -1014,7 +1091,8 @@ int lzf_frame_stream_decompressed_size_device(uint32_t n_streams, const uint8_t*
             i_index = meta.add(d_index, sizeof(void*) * (size_t)n_streams); i_cap = meta.add(cap);
         }
     };
-    RC_TRY(size_frames((uint32_t)n, f_in.data(), f_len.data(), dict_len, f_out_len, f_consumed, f_status, st, sc, meta, more));
+    Pass P;
+    RC_TRY(size_frames((uint32_t)n, f_in.data(), f_len.data(), dict_len, f_out_len, f_consumed, f_status, st, sc, meta, P, more));
     KERNEL(lzf_stream_fold_kernel, dim3(n_streams), dim3(64), 0, st, meta.img<const uint64_t>(i_first), (const int32_t*)f_status,
            (const uint64_t*)f_out_len, (const uint64_t*)f_consumed, meta.img<const uint64_t>(i_full), d_status, d_out_len, d_consumed, d_n_frames);
     KERNEL(lzf_stream_index_kernel, dim3(n_streams), dim3(64), 0, st, meta.img<const uint8_t* const>(i_in), meta.img<const uint64_t>(i_first),
@@ -1031,6 +1109,124 @@ int lzf_stream_index_locate(const lzf_stream_frame* index, size_t n, uint64_t a,
     lzf_sindex::locate(index, n, a, b, &lo, &cnt);
     *first = (size_t)lo; *count = (size_t)cnt;
     return LZF_OK;
+}
+
+// ---- the block index of a frame, and runs of its blocks
+int lzf_frame_block_count_device(uint32_t n_frames, const uint8_t* const* d_in, const size_t* in_len, size_t* n_found, void* hip_stream) {
+    if (n_frames && (!d_in || !in_len || !n_found)) return LZF_E_INVALID;
+    if (usable_device() != LZF_OK) return LZF_E_NO_DEVICE;
+    if (n_frames == 0) return LZF_OK;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    Scan sc(st);
+    RC_TRY(scan_summaries(n_frames, d_in, in_len, st, sc, nullptr, nullptr, nullptr));
+    for (uint32_t f = 0; f < n_frames; ++f) n_found[f] = sc.live(f) ? (size_t)sc.sum[f].n_blocks : 0;
+    return LZF_OK;
+}
+
+// size_frames over the caller's frames, then the delivery body in its index mode over the same descriptors, job results and block
+// checksums: the entries.  What that kernel reads of the caller's travels in size_frames' image: one upload.
+int lzf_frame_block_index_device(uint32_t n_frames, const uint8_t* const* d_in, const size_t* in_len, size_t dict_len,
+                                 lzf_frame_block* const* d_index, const size_t* index_cap,
+                                 uint64_t* d_out_len, uint64_t* d_consumed, int32_t* d_status, uint64_t* d_n_listed, void* hip_stream) {
+    if (n_frames && (!d_in || !in_len || !d_out_len || !d_status)) return LZF_E_INVALID;
+    if ((d_index == nullptr) != (index_cap == nullptr)) return LZF_E_INVALID;
+    if (d_index) for (uint32_t f = 0; f < n_frames; ++f) if (index_cap[f] && (!d_index[f] || (reinterpret_cast<uintptr_t>(d_index[f]) & 7u))) return LZF_E_INVALID;
+    if (n_frames == 0) return LZF_OK;
+    if (usable_device() != LZF_OK) return LZF_E_NO_DEVICE;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    PoolAlloc own_consumed(st);                      // (as the size query: the kernels write `consumed` of every frame)
+    if (!d_consumed) { if (!own_consumed.get(8 * (size_t)n_frames)) return LZF_E_HIP; d_consumed = own_consumed.at<uint64_t>(0); }
+    if (d_n_listed) DEV_TRY(hipMemsetAsync(d_n_listed, 0, 8 * (size_t)n_frames, st));       // a frame whose header fails lists nothing
+    Scan sc(st);
+    Meta meta(st);
+    Pass P;
+    size_t i_index = 0, i_cap = 0;
+    const auto more = [&](const Scan&) {
+        if (!d_index) return;
+        const std::vector<uint64_t> cap(index_cap, index_cap + n_frames);
+        i_index = meta.add(d_index, sizeof(void*) * (size_t)n_frames); i_cap = meta.add(cap);
+    };
+    RC_TRY(size_frames(n_frames, d_in, in_len, dict_len, d_out_len, d_consumed, d_status, st, sc, meta, P, more));
+    if (P.n_frames && (d_index || d_n_listed))
+        KERNEL(lzf_frame_block_index_kernel, dim3(P.n_frames), dim3(64), 0, st, meta.img<const DFrameDesc>(P.i_frames), meta.img<const DBlkDesc>(P.i_blks),
+               meta.img<const lzf_decompress_job>(P.i_jobs), meta.scr<const lzf_job_result>(P.s_res), meta.scr<const uint32_t>(P.s_sums),
+               d_index ? meta.img<lzf_frame_block* const>(i_index) : (lzf_frame_block* const*)nullptr,
+               d_index ? meta.img<const uint64_t>(i_cap) : (const uint64_t*)nullptr, d_n_listed);
+    return meta.wait();                              // the image has left host memory; the kernels run on
+}
+
+int lzf_block_index_locate(const lzf_frame_block* index, size_t n, uint64_t a, uint64_t b, size_t* first, size_t* count) {
+    if (!first || !count || (n && !index)) return LZF_E_INVALID;
+    uint64_t lo = 0, cnt = 0;
+    lzf_bindex::locate(index, n, a, b, &lo, &cnt);
+    *first = (size_t)lo; *count = (size_t)cnt;
+    return LZF_OK;
+}
+
+// Runs of blocks, planned from the caller's entries alone: every compressed block a job at its final place, every stored block
+// a copy, every checksum a hash; lzf_block_run_fold_kernel folds the results per run.  One image, one upload, no read-back.
+int lzf_frame_decompress_blocks_device(uint32_t n_runs, const uint8_t* const* d_in, const size_t* in_len,
+                                       const lzf_frame_block* const* runs, const size_t* count,
+                                       const uint8_t* d_dict, size_t dict_len, uint8_t* const* d_out, const size_t* out_cap,
+                                       uint64_t* d_out_len, int32_t* d_status, void* hip_stream) {
+    if (n_runs && (!d_in || !in_len || !runs || !count || !d_out || !out_cap || !d_out_len || !d_status)) return LZF_E_INVALID;
+    if (!d_dict) dict_len = 0;
+    uint64_t n_blocks = 0;
+    for (uint32_t r = 0; r < n_runs; ++r) {
+        if (count[r] && (!runs[r] || !d_in[r])) return LZF_E_INVALID;
+        if (lzf_bindex::check_run(runs[r], count[r], in_len[r]) != lzf_bindex::RUN_OK) return LZF_E_INVALID;
+        n_blocks += count[r];
+    }
+    if (n_blocks > 0x7FFFFFFFull) return LZF_E_INVALID;
+    if (n_runs == 0) return LZF_OK;
+    if (usable_device() != LZF_OK) return LZF_E_NO_DEVICE;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    std::vector<RRunDesc> rd(n_runs);
+    std::vector<RBlkDesc> bd;
+    std::vector<lzf_decompress_job> jobs;
+    std::vector<const uint8_t*> sptr, csrc; std::vector<uint8_t*> cdst; std::vector<uint64_t> slen, clen;
+    uint64_t max_in = 0, max_copy = 0;
+    for (uint32_t r = 0; r < n_runs; ++r) {
+        const uint64_t total = lzf_bindex::run_total(runs[r], count[r]);
+        rd[r] = RRunDesc{(uint32_t)bd.size(), 0u, LZF_OK, r};
+        if (out_cap[r] < total) { rd[r].status0 = LZF_OUT_CAPACITY; continue; }       // no block of the run is touched
+        if (count[r] && !d_out[r] && total) return LZF_E_INVALID;
+        rd[r].nb = (uint32_t)count[r];
+        uint64_t at = 0;                                // e[k].out_off - e[0].out_off: check_run found the places contiguous
+        for (size_t k = 0; k < count[r]; ++k) {
+            const lzf_frame_block& e = runs[r][k];
+            const uint8_t* const src = d_in[r] + e.in_off;
+            RBlkDesc b{nullptr, e.out_len, kNone, kNone};
+            if (e.flags & LZF_FBLOCK_HAS_SUM) { b.sum_at = src + e.in_len; b.sum_idx = (uint32_t)sptr.size(); sptr.push_back(src); slen.push_back(e.in_len); }
+            if (e.flags & LZF_FBLOCK_STORED) {
+                csrc.push_back(src); cdst.push_back(d_out[r] + at); clen.push_back(e.in_len);
+                if (e.in_len > max_copy) max_copy = e.in_len;
+            } else {
+                lzf_decompress_job j;
+                memset(&j, 0, sizeof j);
+                j.input = src; j.input_len = e.in_len; j.prefix = d_dict; j.prefix_len = dict_len;
+                j.out = d_out[r] + at; j.out_existing_len = 0; j.out_cap = e.out_len; j.output_limit = e.out_len;
+                b.job = (uint32_t)jobs.size(); jobs.push_back(j);
+                if (e.in_len > max_in) max_in = e.in_len;
+            }
+            bd.push_back(b);
+            at += e.out_len;
+        }
+    }
+    Meta meta(st);
+    const size_t i_runs = meta.add(rd), i_blks = meta.add(bd), i_jobs = meta.add(jobs), i_sptr = meta.add(sptr), i_slen = meta.add(slen),
+                 i_csrc = meta.add(csrc), i_cdst = meta.add(cdst), i_clen = meta.add(clen);
+    const size_t s_res = meta.room(sizeof(lzf_job_result) * jobs.size()), s_sums = meta.room(4 * sptr.size());
+    RC_TRY(meta.upload(true));
+    lzf_job_result* const d_res = meta.scr<lzf_job_result>(s_res);
+    uint32_t* const d_sums = meta.scr<uint32_t>(s_sums);
+    if (!sptr.empty()) RC_TRY(lzf_xxh32_batch(meta.img<const uint8_t* const>(i_sptr), meta.img<const uint64_t>(i_slen), d_sums, (uint32_t)sptr.size(), st));
+    if (!jobs.empty()) RC_TRY(lzf_decompress_batch_sized(meta.img<const lzf_decompress_job>(i_jobs), d_res, (uint32_t)jobs.size(), max_in, st));
+    if (!csrc.empty() && max_copy)
+        RC_TRY(lzf_copy_ranges(meta.img<const uint8_t* const>(i_csrc), meta.img<uint8_t* const>(i_cdst), meta.img<const uint64_t>(i_clen), (uint32_t)csrc.size(), max_copy, st));
+    KERNEL(lzf_block_run_fold_kernel, dim3(n_runs), dim3(64), 0, st, meta.img<const RRunDesc>(i_runs), meta.img<const RBlkDesc>(i_blks),
+           (const lzf_job_result*)d_res, (const uint32_t*)d_sums, d_status, d_out_len);
+    return meta.wait();                              // the image has left host memory; the kernels run on
 }
 
 }  // extern "C"

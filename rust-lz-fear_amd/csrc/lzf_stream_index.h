@@ -4,7 +4,8 @@
 //   ends_stream   the stream rule's stop: a frame that does not end at its EndMark with LZF_OK ends its stream (the predicate
 //                 of lzf_stream_fold_kernel: status != LZF_OK, or `consumed` short of where the structural walk ended)
 //   fill_entry    one lzf_stream_frame from a frame's size results: flags, and the content size from a parsed header
-//   locate        the frames of an index whose output meets [a, b): two binary searches over the frames' ends
+//   locate        the frames of an index whose output meets [a, b): two binary searches over the frames' ends (locate_units,
+//                 generic over the entry type: lzf_block_index.h runs it over the blocks of a frame)
 //
 // lzf_stream_index_kernel (frame_device.hip) runs ends_stream and fill_entry one lane per frame; lzf_stream_index_locate is
 // locate.  The CPU tests compile this header with g++ (tests/emu/emu_stream_index.cpp).
@@ -46,14 +47,16 @@ LZF_SCAN_HD inline uint64_t partition_point(uint64_t n, Pred&& pred) {
     return lo;
 }
 
-// Frames [*first, *first + *count) of index[0, n) whose output meets [a, b): frame k with out_off < b && out_off + out_len > a,
-// among the entries without LZF_SFRAME_BEHIND_STOP (a prefix of the index).  A frame's end, out_off + out_len, is the next
-// frame's out_off: the ends never decrease, so the first frame is the first whose end is beyond a, and the last one is the
-// first whose end reaches b, or the stream's total where b is beyond it.  Both have bytes of their own: frames of zero length
-// are never at either edge of the result (inside it they add nothing).  Nothing meets the range: *count = 0, *first = 0.
-LZF_SCAN_HD inline void locate(const lzf_stream_frame* index, uint64_t n, uint64_t a, uint64_t b, uint64_t* first, uint64_t* count) {
+// Units [*first, *first + *count) of index[0, n) whose output meets [a, b): unit k with out_off < b && out_off + out_len > a,
+// among the entries in front of the first one for which outside(entry) holds (a prefix of the index: the frames without
+// LZF_SFRAME_BEHIND_STOP of a stream's index, the delivered blocks of a frame's, lzf_block_index.h).  A unit's end, out_off +
+// out_len, is the next unit's out_off: the ends never decrease, so the first unit is the first whose end is beyond a, and the
+// last one is the first whose end reaches b, or the total where b is beyond it.  Both have bytes of their own: units of zero
+// length are never at either edge of the result (inside it they add nothing).  Nothing meets the range: *count = 0, *first = 0.
+template <class Entry, class Outside>
+LZF_SCAN_HD inline void locate_units(const Entry* index, uint64_t n, uint64_t a, uint64_t b, uint64_t* first, uint64_t* count, Outside&& outside) {
     *first = 0; *count = 0;
-    const uint64_t m = partition_point(n, [&](uint64_t k) { return (index[k].flags & LZF_SFRAME_BEHIND_STOP) != 0; });
+    const uint64_t m = partition_point(n, [&](uint64_t k) { return outside(index[k]); });
     if (m == 0 || a >= b) return;
     const uint64_t total = index[m - 1].out_off + index[m - 1].out_len;
     const uint64_t bb = b < total ? b : total;
@@ -61,6 +64,11 @@ LZF_SCAN_HD inline void locate(const lzf_stream_frame* index, uint64_t n, uint64
     const uint64_t lo = partition_point(m, [&](uint64_t k) { return index[k].out_off + index[k].out_len > a; });
     const uint64_t hi = partition_point(m, [&](uint64_t k) { return index[k].out_off + index[k].out_len >= bb; });
     *first = lo; *count = hi - lo + 1;      // (a < bb <= total: both exist, and lo <= hi)
+}
+
+// the frames of a stream's index: everything in front of the first entry with LZF_SFRAME_BEHIND_STOP
+LZF_SCAN_HD inline void locate(const lzf_stream_frame* index, uint64_t n, uint64_t a, uint64_t b, uint64_t* first, uint64_t* count) {
+    locate_units(index, n, a, b, first, count, [](const lzf_stream_frame& e) { return (e.flags & LZF_SFRAME_BEHIND_STOP) != 0; });
 }
 
 }  // namespace lzf_sindex

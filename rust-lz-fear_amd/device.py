@@ -15,7 +15,9 @@ DJOB = np.dtype([("input", "<u8"), ("input_len", "<u8"), ("prefix", "<u8"), ("pr
 RES = np.dtype([("out_len", "<u8"), ("status", "<i4"), ("reserved", "<u4")])
 SFRAME = np.dtype([("in_off", "<u8"), ("consumed", "<u8"), ("out_off", "<u8"), ("out_len", "<u8"), ("content_size", "<u8"),
                    ("status", "<i4"), ("flags", "<u4")])          # lzf_stream_frame
-assert CJOB.itemsize == 56 and DJOB.itemsize == 64 and RES.itemsize == 16 and SFRAME.itemsize == 48
+FBLOCK = np.dtype([("in_off", "<u8"), ("out_off", "<u8"), ("out_len", "<u8"), ("in_len", "<u4"), ("want_sum", "<u4"),
+                   ("block_maxsize", "<u4"), ("status", "<i4"), ("flags", "<u4"), ("reserved", "<u4")])          # lzf_frame_block
+assert CJOB.itemsize == 56 and DJOB.itemsize == 64 and RES.itemsize == 16 and SFRAME.itemsize == 48 and FBLOCK.itemsize == 48
 
 
 def to_device(arr, device):
@@ -191,6 +193,91 @@ def frame_compress_many(settings, frames, outs, dictionary=None, stream=None):
         t.record_stream(s)
     ffi.check(ffi.lib().lzf_frame_compress_device_many(C.byref(settings), n, ptrs, lens, dptr, dlen, optr, caps, out_len.data_ptr(),
                                                        status.data_ptr(), s.cuda_stream))
+    return status, out_len
+
+
+# ---- the block index of a frame, and runs of its blocks (include/lzfear_frame.h) ------------------------------------------
+
+def frame_block_count(frames, stream=None):
+    """lzf_frame_block_count_device: per frame the blocks the walk finds (0 for a frame whose header fails).  Synchronous."""
+    n, ptrs, lens = _frame_args(frames)
+    if n == 0:
+        return []
+    found = (C.c_size_t * n)()
+    ffi.check(ffi.lib().lzf_frame_block_count_device(n, ptrs, lens, found, _stream_ptr(stream)))
+    return list(found)
+
+
+def frame_block_index_raw(frames, dictionary_len=0, index=None, stream=None):
+    """lzf_frame_block_index_device: frame_decompressed_size's results and, with `index` (one uint8 CUDA tensor per frame, room
+    for numel() // 48 entries, 8-byte aligned), the blocks of every frame.  Returns (status int32, out_len int64, consumed int64,
+    n_listed int64) as CUDA tensors, written in order on `stream`.  The content checksum is not verified."""
+    n, ptrs, lens = _frame_args(frames)
+    dev = frames[0].device if n else torch.device("cuda", torch.cuda.current_device())
+    status = torch.empty(n, dtype=torch.int32, device=dev)         # (empty: the call writes every entry)
+    out_len, consumed, n_listed = (torch.empty(n, dtype=torch.int64, device=dev) for _ in range(3))
+    if n == 0:
+        return status, out_len, consumed, n_listed
+    iptr = icap = None
+    if index is not None:
+        assert len(index) == n
+        for t in index:
+            assert t.dtype == torch.uint8 and t.is_cuda and t.dim() == 1 and t.is_contiguous() and (t.numel() < FBLOCK.itemsize or t.data_ptr() % 8 == 0), \
+                "index: 1-D contiguous uint8 CUDA tensors at 8-byte aligned addresses"
+        iptr = (C.c_void_p * n)(*[t.data_ptr() if t.numel() >= FBLOCK.itemsize else None for t in index])
+        icap = (C.c_size_t * n)(*[t.numel() // FBLOCK.itemsize for t in index])
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    for t in (status, out_len, consumed, n_listed):
+        t.record_stream(s)
+    ffi.check(ffi.lib().lzf_frame_block_index_device(n, ptrs, lens, int(dictionary_len), iptr, icap, out_len.data_ptr(), consumed.data_ptr(),
+                                                     status.data_ptr(), n_listed.data_ptr(), s.cuda_stream))
+    return status, out_len, consumed, n_listed
+
+
+def frame_block_index(frames, dictionary_len=0, stream=None):
+    """The block index of every frame: counts the blocks (lzf_frame_block_count_device), allocates one entry tensor per frame and
+    runs frame_block_index_raw.  Returns (status, out_len, consumed, n_listed, entries): CUDA tensors as above and a list of uint8
+    CUDA tensors of 48 bytes per block found (view them as FBLOCK on the host)."""
+    frames = list(frames)
+    if not frames:
+        return frame_block_index_raw([], dictionary_len=dictionary_len, stream=stream) + ([],)
+    dev = frames[0].device
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    found = frame_block_count(frames, stream=s)
+    entries = [torch.empty(k * FBLOCK.itemsize, dtype=torch.uint8, device=dev) for k in found]
+    for e in entries:
+        e.record_stream(s)
+    return frame_block_index_raw(frames, dictionary_len=dictionary_len, index=entries, stream=s) + (entries,)
+
+
+def frame_decompress_blocks(frames, runs, outs, dictionary=None, stream=None):
+    """lzf_frame_decompress_blocks_device: run r is `runs[r]`, a numpy FBLOCK array of consecutive entries of the block index of
+    `frames[r]` (host copies), decoded into `outs[r]` (1-D uint8 CUDA tensors, their lengths are the capacities), every block
+    straight to its place.  Returns (status int32, out_len int64) as CUDA tensors, written in order on `stream`; nothing is
+    synchronised.  Raises ffi.LzfError(E_INVALID) for a run the call refuses; the content checksum is never verified."""
+    n, ptrs, lens = _frame_args(frames)
+    assert len(runs) == n and len(outs) == n
+    dev = frames[0].device if n else torch.device("cuda", torch.cuda.current_device())
+    status = torch.empty(n, dtype=torch.int32, device=dev)         # (empty: the call writes every entry)
+    out_len = torch.empty(n, dtype=torch.int64, device=dev)
+    if n == 0:
+        return status, out_len
+    for t in outs:
+        assert t.dtype == torch.uint8 and t.is_cuda and t.dim() == 1 and t.is_contiguous(), "outs: 1-D contiguous uint8 CUDA tensors"
+    keep = [np.ascontiguousarray(r, dtype=FBLOCK) for r in runs]
+    rptr = (C.c_void_p * n)(*[r.ctypes.data if len(r) else None for r in keep])
+    rcnt = (C.c_size_t * n)(*[len(r) for r in keep])
+    optr = (C.c_void_p * n)(*[t.data_ptr() for t in outs])
+    caps = (C.c_size_t * n)(*[t.numel() for t in outs])
+    dptr, dlen = None, 0
+    if dictionary is not None and dictionary.numel():
+        assert dictionary.dtype == torch.uint8 and dictionary.is_cuda and dictionary.is_contiguous()
+        dptr, dlen = dictionary.data_ptr(), dictionary.numel()
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    for t in (status, out_len):
+        t.record_stream(s)
+    ffi.check(ffi.lib().lzf_frame_decompress_blocks_device(n, ptrs, lens, rptr, rcnt, dptr, dlen, optr, caps, out_len.data_ptr(),
+                                                           status.data_ptr(), s.cuda_stream))
     return status, out_len
 
 

@@ -83,6 +83,7 @@ FRAME_EXPORTS = [
     "lzf_frame_compress_device_many", "lzf_frame_decompressed_size_device",
     "lzf_frame_stream_bound_device", "lzf_frame_decompress_stream_device", "lzf_frame_compress_stream_bound", "lzf_frame_compress_stream_device",
     "lzf_frame_stream_count_device", "lzf_frame_stream_decompressed_size_device", "lzf_stream_index_locate",
+    "lzf_frame_block_count_device", "lzf_frame_block_index_device", "lzf_block_index_locate", "lzf_frame_decompress_blocks_device",
 ]
 
 
@@ -95,6 +96,17 @@ class StreamFrame(C.Structure):
 assert C.sizeof(StreamFrame) == 48
 STREAM_NO_CONTENT_SIZE = (1 << 64) - 1
 SFRAME_COMPLETE, SFRAME_BEHIND_STOP = 1, 2
+
+
+class FrameBlock(C.Structure):
+    """lzf_frame_block: one entry of a frame's block index (lzf_frame_block_index_device)"""
+    _fields_ = [("in_off", C.c_uint64), ("out_off", C.c_uint64), ("out_len", C.c_uint64), ("in_len", C.c_uint32), ("want_sum", C.c_uint32),
+                ("block_maxsize", C.c_uint32), ("status", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(FrameBlock) == 48
+FBLOCK_STORED, FBLOCK_HAS_SUM, FBLOCK_LINKED, FBLOCK_DELIVERED, FBLOCK_BEHIND_STOP = 1, 2, 4, 8, 16
+F_BLOCK_CHECKSUM_FAIL, F_BLOCK_SIZE_OVERFLOW = 19, 22
 
 
 class FrameStats(C.Structure):
@@ -208,6 +220,14 @@ def lib():
                                                                 C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p,
                                                                 C.c_void_p, C.c_void_p, C.c_void_p]
         L.lzf_stream_index_locate.argtypes = [C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint64, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+        L.lzf_frame_block_count_device.argtypes = [C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_void_p]
+        L.lzf_frame_block_index_device.argtypes = [C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t,
+                                                   C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p]
+        L.lzf_block_index_locate.argtypes = [C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint64, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+        L.lzf_frame_decompress_blocks_device.argtypes = [C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p),
+                                                         C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p),
+                                                         C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 

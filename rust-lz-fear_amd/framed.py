@@ -436,6 +436,72 @@ def read_stream_range_device(stream_tensor, index, start, stop, dictionary=None,
     return out[start - base:stop - base]
 
 
+FrameBlockIndex = collections.namedtuple("FrameBlockIndex", "status out_len consumed blocks")
+FrameBlockIndex.__doc__ = """What lzf_frame_block_index_device says about one frame: `status`, `out_len` and `consumed` as
+decompressed_sizes_device reports them (the content checksum not verified), and `blocks`, a numpy structured array with the fields
+of lzf_frame_block (in_off, out_off, out_len, in_len, want_sum, block_maxsize, status, flags, reserved), one entry per block the
+walk finds."""
+
+
+def block_index_device(frames, dictionary_len=0, stream=None):
+    """Exact sizes and the block index of frames that live on the device (1-D uint8 CUDA tensors), found without decoding and
+    without output memory (lzf_frame_block_count_device, lzf_frame_block_index_device).  Returns [FrameBlockIndex] — per frame
+    (status, out_len, consumed, entries as a numpy structured array) — once `stream` has finished the call.  `dictionary_len`: the
+    length of the dictionary the frames will be decoded with."""
+    import numpy as np
+    import torch
+    from . import device
+    frames = list(frames)
+    if not frames:
+        return []
+    s = stream if stream is not None else torch.cuda.current_stream(frames[0].device)
+    with torch.cuda.stream(s):
+        status, out_len, consumed, _, entries = device.frame_block_index(frames, dictionary_len=dictionary_len, stream=s)
+    s.synchronize()
+    st, ol, co = status.cpu().tolist(), out_len.cpu().tolist(), consumed.cpu().tolist()
+    blocks = [np.ascontiguousarray(e.cpu().numpy()).view(device.FBLOCK) for e in entries]
+    return [FrameBlockIndex(st[k], ol[k], co[k], blocks[k]) for k in range(len(frames))]
+
+
+def locate_blocks(index, start, stop):
+    """lzf_block_index_locate: (first, count) of the delivered blocks of `index` (a FrameBlockIndex or its `blocks`) whose output
+    meets the bytes [start, stop) of the frame's output; count 0 where none does.  Host only."""
+    import numpy as np
+    blocks = np.ascontiguousarray(getattr(index, "blocks", index))
+    first, count = C.c_size_t(0), C.c_size_t(0)
+    ffi.check(ffi.lib().lzf_block_index_locate(blocks.ctypes.data if len(blocks) else None, len(blocks), max(int(start), 0),
+                                               max(int(stop), 0), C.byref(first), C.byref(count)))
+    return first.value, count.value
+
+
+def read_frame_range_device(frame_tensor, index, start, stop, dictionary=None, stream=None):
+    """Bytes [start, min(stop, index.out_len)) of the output of one frame of independent blocks (a 1-D uint8 CUDA tensor) with
+    `index`, its FrameBlockIndex: only the blocks that hold the range are decoded (lzf_block_index_locate finds them,
+    lzf_frame_decompress_blocks_device decodes the run into a tensor of exactly the run's length).  Returns a view of that output.
+    Raises FrameError with the run's status where it is not 0 (a block damaged since the index was taken: BlockChecksumFail, a
+    codec error, or 6, LZF_CONTRACT, where a block no longer decodes to the indexed length), ffi.LzfError for a linked-block frame (decode the
+    frame).  A range read verifies neither the content checksum nor the blocks it skips."""
+    import torch
+    from . import device
+    blocks = index.blocks
+    start, stop = max(int(start), 0), min(int(stop), int(index.out_len))
+    first, count = locate_blocks(blocks, start, stop) if start < stop else (0, 0)
+    if count == 0:
+        return torch.empty(0, dtype=torch.uint8, device=frame_tensor.device)
+    run = blocks[first:first + count]
+    base, total = int(run[0]["out_off"]), int(run["out_len"].sum())
+    s = stream if stream is not None else torch.cuda.current_stream(frame_tensor.device)
+    with torch.cuda.stream(s):
+        out = torch.empty(total, dtype=torch.uint8, device=frame_tensor.device)
+        status, out_len = device.frame_decompress_blocks([frame_tensor], [run], [out], dictionary=dictionary, stream=s)
+    s.synchronize()
+    st = int(status.item())
+    if st != 0:
+        raise FrameError(st)
+    assert int(out_len.item()) == total
+    return out[start - base:stop - base]
+
+
 class FrameBlockReader:
     """The C ABI's block-by-block reader (lzf_frame_reader_*, include/lzfear_frame.h) over a frame in memory:
     `LZ4FrameReader::new` + `decode_block` (src/framed/decompress.rs:102-161,198-282), one call = one block."""
