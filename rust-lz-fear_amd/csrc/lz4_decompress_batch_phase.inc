@@ -10,13 +10,38 @@
 //     LZF_FED_DECODE      the bitmap-fed kernel, instead of the two above: toks (window offsets, not yet verified) and the carried expect
 //                         (where the chain's next token starts), fed_carry and bail; the set-up then decodes each token once and checks the
 //                         chain's links before the batch writes anything (a broken link or UnexpectedEnd: bail, the loop ends with `expect` on
-//                         the failing batch's first token), and a short last batch of the list may be left for the next window
+//                         the failing batch's first token), and a short last batch of the list may be left for the next window.
+//                         Also carried: pend — out[pend, o) is still only in the ring (the DEFERRED FLUSH, below and at PHASE(3)); pend >= o:
+//                         nothing is pending.  The kernel drains it wherever its loop ends.
 //     LZF_FAR_LATE        optional: the far matches' loads behind the literal copy instead of in front of it
             LZF_STAGE_NEEDS(jv, DecodeJob); LZF_STAGE_NEEDS(rg.kRing, uint32_t); LZF_STAGE_NEEDS(sb.kCB, uint32_t); LZF_STAGE_NEEDS(lane, uint32_t);
             LZF_STAGE_NEEDS(o, uint32_t); LZF_STAGE_NEEDS(safe, uint32_t); LZF_STAGE_NEEDS(status, int); LZF_STAGE_NEEDS(cstart, uint32_t); LZF_STAGE_NEEDS(Tc, uint32_t);
             static_assert(kSpanMax + kNearHist == rg.kRing, "a batch's span and the intact history share the ring");
 #if defined(LZF_FED_DECODE)
-            LZF_STAGE_NEEDS(expect, uint32_t); LZF_STAGE_NEEDS(fed_carry, uint32_t); LZF_STAGE_NEEDS(bail, bool); LZF_STAGE_NEEDS(toks[0], uint16_t);
+            LZF_STAGE_NEEDS(expect, uint32_t); LZF_STAGE_NEEDS(fed_carry, uint32_t); LZF_STAGE_NEEDS(bail, bool); LZF_STAGE_NEEDS(toks[0], uint16_t); LZF_STAGE_NEEDS(pend, uint32_t);
+            // The deferred flush.  A batch does not write itself to `out` at its end: it leaves its bytes pending in the ring, and the NEXT batch
+            // flushes them behind its own far phase — once its far loads have been waited for and have landed in the ring, in front of its match
+            // rounds.  What it buys is the whole-line flush of the next point: with a range carried from batch to batch, the ragged ends need not
+            // be written as bytes.  That took 1.2 ms of 87 off the headline call; the deferral by itself — the next wait for a load no longer waiting
+            // for this flush's write acknowledgements, gfx950 counting both in one vmcnt — measured 0.2 - 0.4 %, inside the noise
+            // (profiles/fed_deferred_flush.txt).
+            //  - Whole 16-byte lines only (OutRing::flush_lines): the flush stops at the last 16-byte address at or below ob0 and leaves the ragged
+            //    end, up to 15 bytes, pending with this batch's bytes.  A line of `out` is written once and whole, and the common flush has no
+            //    head or tail bytes: only the first one behind a hand-over, a solo sequence or the job's start has a head.  So out[pend, o) is
+            //    pending, and at a batch's start pend is at most 15 below the start of the batch before.  The drains write bytes, as every flush did.
+            //  - The ring allows it: the batch before and the ragged end in front of it are at most kSpanMax + 15 < kNearHist bytes below ob0,
+            //    inside the history this batch keeps intact — it writes the ring only at [ob0, ob0 + kSpanMax).
+            //  - Nothing reads pending bytes from `out`: near_lo = ob0 - kNearHist < pend; a far source ends at or below near_lo, and the slow loop
+            //    and the cooperative far loop read jv.out[s] only for s < near_lo.
+            //  - `safe` (out[0, safe) is visible to this wave's loads) moves only where a full wait happened, and then to `pend`: what has
+            //    been issued.  Every `need` the fence test looks at is <= near_lo < pend, so one fence always satisfies it.  Not to ob0: the batch
+            //    before has not been issued yet, and a later far source may lie in it.  The price is known: a fence in front of 34 % of the batches
+            //    of the Silesia stand-in instead of 24 % (72 194 against 52 391 per copy), inside the gain measured.
+            //  - The solo path drains first (it writes `out` directly and re-fills the ring from it).  Every exit of the batch loop — an error status,
+            //    a bail (both raised before the batch wrote anything: o is still ob0), a carried batch, the window's end — leaves the range pending for
+            //    the kernel, which drains it when its window loop ends (parked, finished, failed, bailed) and carries it across windows and across
+            //    the walk-mode retry of a window otherwise: the retry runs no batch before the one that flushes it.
+            static_assert(kSpanMax + 16u <= kNearHist, "the batch before and the ragged end before it lie inside the history this batch keeps intact, above every far source");
 #elif !defined(LZF_TOKEN_AT)
 #error "lz4_decompress_batch_phase.inc: define LZF_TOKEN_AT(i) (or LZF_FED_DECODE) around the include"
 #endif
@@ -26,7 +51,7 @@
             uint32_t tidx = 0;
             if (LZF_DBG_SKIP & 1) { tidx = Tc; o += Tc; }      // (LZF_FED_DECODE: no decode either, the chain stops after one window)
 #if defined(LZF_FED_DECODE)
-            if (LZF_DBG_SKIP & 1) expect = jv.len;
+            if (LZF_DBG_SKIP & 1) { expect = jv.len; pend = o; }
 #endif
             while (tidx < Tc && status == LZF_OK) {
 #if defined(LZF_FED_DECODE)
@@ -170,6 +195,10 @@
                     // =============================================================
 #if defined(LZF_FED_DECODE)
                     expect = __builtin_amdgcn_readlane(next, 0);
+                    // (drain: from here on `out` is written directly, and the ring re-filled from it.  No range until the sequence is through:
+                    //  what an error exit below leaves in [pend, o) is in `out` already, not in the ring)
+                    if (!(LZF_DBG_SKIP & 16)) rg.flush(pend, o);
+                    pend = 0xFFFFFFFFu;
 #endif
                     const uint32_t s_L = __builtin_amdgcn_readlane(L, 0);
                     const uint32_t s_M = __builtin_amdgcn_readlane(M, 0);
@@ -224,6 +253,9 @@
                     // ring <- the tail of what was just written
                     wave_store_fence(); safe = o;
                     rg.fill((o - o_before > rg.kRing) ? o - rg.kRing : o_before, o);
+#if defined(LZF_FED_DECODE)
+                    pend = o;
+#endif
                     tidx += 1u;
                     continue;
                 }
@@ -310,7 +342,17 @@
                     if (is_slow && !from_prefix) need = near_lo;
                     if (is_slow && from_prefix && M > off - mo) need = near_lo;
                     if (need > ob0) need = ob0;
+#if defined(LZF_FED_DECODE)
+                    // (the batch before is not in `out` yet: the wait covers what has been issued, out[0, pend) — and need <= near_lo <= pend)
+                    if (__ballot(need > safe)) {
+#if defined(LZF_DBG_FED_COUNT)
+                        ++dbg_fed[5];
+#endif
+                        wave_store_fence(); safe = pend;
+                    }
+#else
                     if (__ballot(need > safe)) { wave_store_fence(); safe = ob0; }
+#endif
                 }
                 // far (never overlapping: offset > ring history > length): HBM -> ring.  The loads of the short
                 // ones are issued here and land while the literals are being copied; the stores follow below.
@@ -403,6 +445,16 @@
                     }
                 }
                 PHASE(3);
+#if defined(LZF_FED_DECODE)
+                // ---- the batch before: ring -> HBM (pend <= ob0; an empty range after a solo sequence or a hand-over)
+                // (The wait first: every load of this batch has been consumed by now, or was never issued — but hipcc's wait insertion carries the far
+                //  loads as pending past the EXEC branch around their LDS stores, and then puts a vmcnt(0) behind the flush where their registers are
+                //  used again: a wait for the stores' acknowledgement.  Here it waits for nothing, and nothing is pending behind it.)
+                __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0), the other counters left alone
+                if (LZF_DBG_SKIP & 128) { rg.flush_dry(pend, ob0); pend = ob0; }      // (analysis: the ring reads and addresses without the stores;
+                else if (LZF_DBG_SKIP & 16) pend = ob0;                               //  no flush at all)
+                else pend = rg.flush_lines(pend, ob0);
+#endif
                 unsigned long long unresolved = __ballot(is_near || is_slow);
                 const unsigned long long slow_mask = __ballot(is_slow);
                 // Rounds in stream order.  H = start of the first unresolved match: every output byte below H is
@@ -497,9 +549,13 @@
                     }
                 }
                 PHASE(4);
-                // ---- flush the batch ring -> HBM
                 o = ob0 + __builtin_amdgcn_readlane(incl, (nb - 1u) & 63u);
+#if defined(LZF_FED_DECODE)
+                // (out[ob0, o) stays in the ring behind what is pending already: the next batch flushes it, or the kernel when its loop ends)
+#else
+                // ---- flush the batch ring -> HBM
                 if (!(LZF_DBG_SKIP & 16)) rg.flush(ob0, o);
+#endif
                 tidx += nb;
                 PHASE(5);
             }

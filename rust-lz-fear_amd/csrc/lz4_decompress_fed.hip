@@ -107,8 +107,8 @@ __global__ LZF_FED_BOUNDS void lzf_decompress_fed_kernel(fed_args a) {      // (
     bool bailed = false, parked = false;
     uint32_t o = 0;
     PhaseTimers ph;
-#ifdef LZF_DBG_FED_COUNT   // analysis: [0] batches, [1] windows listed from the map, [2] windows walked, [3] trips of the match-round loop, [4] overlapping cooperative matches whose offset is a power of two (no division), of this wave's share of the job (LZF_FED_PIECES=1: the job) -> results[].reserved
-    uint32_t dbg_fed[5] = {0u, 0u, 0u, 0u, 0u};
+#ifdef LZF_DBG_FED_COUNT   // analysis: [0] batches, [1] windows listed from the map, [2] windows walked, [3] trips of the match-round loop, [4] overlapping cooperative matches whose offset is a power of two (no division), [5] store fences in front of a batch's far / slow sources (need > safe), of this wave's share of the job (LZF_FED_PIECES=1: the job) -> results[].reserved
+    uint32_t dbg_fed[6] = {0u, 0u, 0u, 0u, 0u, 0u};
 #endif
     if (LZF_DECODE_JOB_OUT_OF_CONTRACT(job)) continue;      // (LZF_CONTRACT: the pair kernel says so)
     {
@@ -135,6 +135,7 @@ __global__ LZF_FED_BOUNDS void lzf_decompress_fed_kernel(fed_args a) {      // (
             expect = fs->expect; o = fs->o;  // (a short batch the piece before left at its end is simply this piece's first)
         }
         uint32_t safe = o;   // out[0, safe) is visible to this wave's global loads
+        uint32_t pend = o;   // out[pend, o) is the last batch, still only in the ring: the next batch flushes it behind its far loads, or the drain below
         if (o > 0) rg.fill(o > (uint32_t)RING ? o - RING : 0u, o);   // Vec content on entry (or what the other slot wrote) = history
         ph.start();          // (section 1 here with the tokens' decode and the chain check: lzf_phase_timers.h)
 #if defined(LZF_FED_FIXED_ROUNDS)
@@ -176,6 +177,11 @@ __global__ LZF_FED_BOUNDS void lzf_decompress_fed_kernel(fed_args a) {      // (
             fed_walk = false;
             if (expect == expect_in && status == LZF_OK) { bailed = true; break; }      // (no progress: never, by the invariant — and never a spin)
         }
+        // The drain: whichever way the loop ended — parked, the chain's end, a status, a bail — the last batch goes to `out` here, in front of the
+        // hand-over's wait and of results[].  An error is raised before its batch writes anything, so `out` holds what it held when every batch
+        // flushed itself: all of the job up to the failing batch, a prefix of what the pair kernel writes again.  (A solo sequence that fails
+        // leaves nothing pending: pend >= o.)
+        if (pend < o && !(LZF_DBG_SKIP & 16)) rg.flush(pend, o);
         if (parked && status == LZF_OK && !bailed) {
             // hand the job on: what this wave wrote must be visible to another compute unit before the flag is
             if (lane == 0u) { fs->expect = expect; fs->o = o; }

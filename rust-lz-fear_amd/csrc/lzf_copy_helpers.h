@@ -14,7 +14,7 @@ constexpr uint32_t kShort = 64;          // bytes a lane moves by itself (litera
 constexpr uint32_t kFarShort = 32;       // same for far matches (their bytes wait in registers while the literals are copied)
 constexpr uint32_t kTotClamp = 1u << 25; // per-sequence output clamp inside the position scan
 #ifndef LZF_DBG_SKIP
-#define LZF_DBG_SKIP 0      // analysis builds only: bit0 batches, bit1 serial matches, bit2 far, bit3 literals, bit4 flush, bit5 round 1, bit6 (fed kernel) the moves of near overlapping matches of offset 1, 2, 4, 8
+#define LZF_DBG_SKIP 0      // analysis builds only: bit0 batches, bit1 serial matches, bit2 far, bit3 literals, bit4 flush, bit5 round 1, bit6 (fed kernel) the moves of near overlapping matches of offset 1, 2, 4, 8, bit7 (fed kernel) the flush without its stores
 #endif
 
 // The job as a decompress kernel sees it: global pointers, 32-bit positions, the output capacity clamped to them.

@@ -3,7 +3,8 @@
 //   lzf_ring_split   the (head, vector, tail) split of a range; plain constexpr code that the kernels and a CPU test compile
 //                    (tests/emu/emu_ring_split.cpp, against the model tests/alignment_cases.py::ring_flush_split)
 //   OutRing<RING>    the most recent RING bytes of output in LDS: ring index == output address mod RING (rb = out & 15 is the bias), so 16-byte
-//                    pieces of the ring line up with 16-byte pieces of HBM.  idx (RIDX), fill, flush.
+//                    pieces of the ring line up with 16-byte pieces of HBM.  idx (RIDX), fill, flush; flush_lines (the fed kernel's deferred
+//                    flush: the whole 16-byte pieces of a range, the rest left to the caller).
 // The stager of lzf_seg_resolve_pair_kernel (lz4_decompress_seg.hip) keeps a written-out copy of the split, which names this one.
 #ifndef LZF_OUT_RING_H
 #define LZF_OUT_RING_H
@@ -65,6 +66,34 @@ struct OutRing {
     }
     __device__ __forceinline__ void fill(uint32_t a, uint32_t b) const { move<false>(a, b); }
     __device__ __forceinline__ void flush(uint32_t a, uint32_t b) const { move<true>(a, b); }
+    // out[a, e) <- ring for the whole 16-byte pieces of [a, b) only; returns e, the last 16-byte address at or below b (biased), from where the
+    // caller keeps the rest pending (the fed kernel's deferred flush: a range that starts on such an address — every one but the first — has
+    // no head and no tail, and a 16-byte line of `out` is written once).  a, b uniform.  A range that does not reach its first 16-byte address
+    // stays pending as a whole (e == a).
+    __device__ __forceinline__ uint32_t flush_lines(uint32_t a, uint32_t b) const {
+        const uint32_t nh = (0u - (a + rb)) & 15u;
+        if (nh != 0u) {
+            if (b - a < nh) return a;
+            if (lane < nh) out[a + lane] = at(a + lane);
+            a += nh;
+        }
+        const uint32_t nv = (b - a) >> 4;
+        for (uint32_t c = lane; c < nv; c += kWave)
+            *reinterpret_cast<LZF_GLOBAL u32x4*>(out + a + 16u * c) = *reinterpret_cast<u32x4*>(&at(a + 16u * c));
+        return a + (nv << 4);
+    }
+    // (analysis, LZF_DBG_SKIP & 128: the flush's ring reads and address work with no store issued — what the stores themselves cost)
+    __device__ __forceinline__ void flush_dry(uint32_t a, uint32_t b) const {
+        const lzf_ring_parts s = lzf_ring_split(a, b, rb);
+        if (lane < s.head) { const uint32_t v = at(a + lane); asm volatile("" :: "v"(v), "v"(out + a + lane)); }
+        a += s.head;
+        for (uint32_t c = lane; c < s.vec; c += kWave) {
+            const u32x4 v = *reinterpret_cast<u32x4*>(&at(a + 16u * c));
+            asm volatile("" :: "v"(v), "v"(out + a + 16u * c));
+        }
+        a += s.vec << 4;
+        if (lane < s.tail) { const uint32_t v = at(a + lane); asm volatile("" :: "v"(v), "v"(out + a + lane)); }
+    }
 };
 
 }  // namespace
