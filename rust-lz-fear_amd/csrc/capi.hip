@@ -252,7 +252,7 @@ int lzf_decompress_batch_sized(const lzf_decompress_job* d_jobs, lzf_job_result*
 
 // decompress_raw's status and output.len() of every job, nothing decoded.  The call executes lzf_dispatch.h's size_plan:
 //   * few large blocks (the latency class): plan, parse and seam of the segmented pipeline, the tiles summed up, every job's tiles
-//     added up and checked (lz4_decoded_size_seg.inc) — scratch from the stream-ordered pool, about 1.2 bits per byte of
+//     added up and checked (lz4_decoded_size_seg.hip) — scratch from the stream-ordered pool, about 1.2 bits per byte of
 //     max_input_len x n_jobs, freed in stream order; a pool that refuses it only sends the call down the other way;
 //   * always last: lzf_decoded_size_kernel (lz4_decoded_size.hip), one wavefront per job, over the whole call; behind the class it skips
 //     the jobs that finished there.  As many workgroups as the device holds at once draw jobs from a 4-byte counter; with more jobs

@@ -1,4 +1,4 @@
-// capi_drivers.hip — the host drivers of the two multi-launch decompress paths: the segmented pipeline (lz4_decompress_seg.hip) and
+// capi_drivers.hip — the host drivers of the two multi-launch decompress paths: the segmented pipeline (lz4_seg_*.hip) and
 // the bitmap-fed kernel behind its plan + parse stages (lz4_decompress_fed.hip), and the front of the size call's latency class.  They execute a plan of lzf_dispatch.h; whether a
 // call comes here at all, with which ring and in which groups, is decided there.
 #include "capi_internal.h"
@@ -163,7 +163,7 @@ int seg_decompress(Device& dv, const lzf_decompress_job* d_jobs, lzf_job_result*
     return rc;
 }
 
-// ---- the size call's latency class (lz4_decoded_size_seg.inc) -------------------------------------------------------------------
+// ---- the size call's latency class (lz4_decoded_size_seg.hip) -------------------------------------------------------------------
 // plan, parse and seam of the pipeline over the whole call — `out` is not needed, prefix and existing output are lengths — then the
 // tiles summed up and every job's tiles added up and checked.  Enqueue only; the scratch stays with the caller until the one-wave
 // kernel behind this has looked at the state array.

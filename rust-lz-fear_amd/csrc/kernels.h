@@ -68,7 +68,8 @@ LZF_PAIRED_VARIANTS(LZF_EXTP)
 constexpr auto k_paired48 = lzf_decompress_paired_kernel<4096, 48, 640>;      // the two forms of the product dispatch (lzf_dispatch.h: kPaired48Lds, kPaired24Lds)
 constexpr auto k_paired24 = lzf_decompress_paired_kernel<4096, 24, 384>;
 // ---------------------------------------------------------------------------------------------------------------------
-// Segmented decompress (lz4_decompress_seg.hip): one block decoded by MANY wavefronts, as a pipeline of launches over the
+// Segmented decompress (lzf_seg_common.h; lz4_seg_front.hip: plan, parse, seam; lz4_seg_tiles.hip: tilesum, scan, records;
+// lz4_seg_order.hip: by_len, rank, order, pause; lz4_seg_resolve.hip): one block decoded by MANY wavefronts, as a pipeline of launches over the
 // whole batch.  Used for batches that leave the chip mostly empty with one workgroup per block (per-block latency regime).
 //   plan      per job: eligible?  (size window; a prefix and existing output in 31-bit positions)  chunk / tile counts
 //   parse     one wave per 16 KiB chunk of compressed bytes (chunks overlap by 2 KiB): speculative region-walk parse from
@@ -124,7 +125,7 @@ struct seg_ctx {
     // length, input_len >> 4, for a job the map does not cover) and counted up by the parse (every chunk adds the tokens it owns).  null: no order asked for
     uint32_t* est;
     uint32_t len_shift;
-    // the size call's latency class (lz4_decoded_size_seg.inc): plan, parse and seam serve lzf_size_tile_kernel / lzf_size_finish_kernel.
+    // the size call's latency class (lz4_decoded_size_seg.hip): plan, parse and seam serve lzf_size_tile_kernel / lzf_size_finish_kernel.
     // Nothing is decoded, so `out` may be NULL and prefix / existing output do not make a job ineligible (they enter the finish kernel's
     // checks); an empty input is a job of no chunk and no tile.  No arena: rec_top, recs, tile_tok and tile_out are NULL.
     uint32_t size_only;

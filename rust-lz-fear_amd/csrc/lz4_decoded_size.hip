@@ -10,7 +10,7 @@
 //   on by the round's sum.  Compressed bytes come from HBM once; nothing but the result is written: no ring, no copy stage,
 //   `prefix`, `out` and `out_cap` of the job are never looked at.  A token that reaches beyond its chunk (megabytes of 0xFF length
 //   bytes, literals over many chunks) is decoded ahead of the parse, its 0xFF run eight bytes at a time.
-// A call of few large blocks goes through the latency class first (lz4_decoded_size_seg.inc: a block summed up by many wavefronts);
+// A call of few large blocks goes through the latency class first (lz4_decoded_size_seg.hip: a block summed up by many wavefronts);
 // this kernel then runs last, over the whole call, and skips the jobs that class finished (SKIP, `done`).
 // UnexpectedEnd is the parse's finding (cerr: right behind the chunk's listed tokens); inside a sequence it precedes the
 // position checks (:63-71 before :72), and the failing sequence is never listed, so the order is the reference's.
@@ -63,7 +63,7 @@ __global__ __launch_bounds__(64) void lzf_decoded_size_kernel(const lzf_decompre
         t = rfl(t);
         if (t >= n_jobs) break;
         const uint32_t jid = perm ? perm[t] : t;       // (perm: the jobs longest input first, so that the launch does not end on a long one)
-        if (SKIP && done[jid].done) continue;          // finished by the latency class (lz4_decoded_size_seg.inc; uniform over the wave)
+        if (SKIP && done[jid].done) continue;          // finished by the latency class (lz4_decoded_size_seg.hip; uniform over the wave)
         const long long t_start = clock64();
         cgu8* __restrict__ in = as_global(jobs[jid].input);
         const uint64_t input_len = jobs[jid].input_len, plen = jobs[jid].prefix_len, existing = jobs[jid].out_existing_len;

@@ -1,6 +1,6 @@
-// lz4_decoded_size_seg.inc — the size call's latency class: ONE BLOCK SUMMED UP BY MANY WAVEFRONTS.  Included by
-// lz4_decompress_seg.hip inside namespace lzf, behind the tile helpers (tile_enumerate, tile_decode) it shares with the decode
-// pipeline's tile stages; the rule is lzf_size_rules.h (TileSum, summarise, clean), which the CPU tests compile with g++.
+// lz4_decoded_size_seg.hip — the size call's latency class: ONE BLOCK SUMMED UP BY MANY WAVEFRONTS.  The tile helpers
+// (tile_enumerate, tile_decode) are lzf_seg_common.h's, shared with the decode pipeline's tile stages (lz4_seg_tiles.hip);
+// the rule is lzf_size_rules.h (TileSum, summarise, clean), which the CPU tests compile with g++.
 //
 // lzf_decoded_size_kernel walks a block's token chain with one wavefront: about 20 ms for a 4 MiB block whatever the batch.  A
 // call that leaves the chip mostly empty takes the decode pipeline's front instead — plan, parse, seam: the bit map of the true
@@ -11,6 +11,10 @@
 //            position checks for its tile; a job of clean tiles gets {out_existing_len + total, LZF_OK} and done = 1
 // Nothing else is written, and nothing at all for a job that is not clean: lzf_decoded_size_kernel, launched last over the whole
 // call, skips the done jobs and gives every other one its status and length as it always did.
+#include "lzf_seg_common.h"
+#include "lzf_size_rules.h"
+
+namespace lzf {
 
 static_assert(kLenClamp == lzf_size::kTileLenClamp, "lzf_size_rules.h restates the clamp of tile_decode");
 static_assert(sizeof(lzf_size::TileSum) == sizeof(u32x4), "one 16-byte store per tile");
@@ -92,3 +96,5 @@ __global__ __launch_bounds__(64) void lzf_size_finish_kernel(seg_ctx c) {
         c.st[j].done = 1u;
     }
 }
+
+}  // namespace lzf

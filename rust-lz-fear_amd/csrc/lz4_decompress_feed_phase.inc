@@ -1,6 +1,6 @@
 // lz4_decompress_feed_phase.inc — the FEED stage of the bitmap-fed decompress kernels (lz4_decompress_fed.hip): what the PARSE
 // stage of lz4_decompress_parse_phase.inc produces for a chunk — the token list of the chunk — taken from the token bit map the
-// hop parse of the segmented pipeline wrote for the whole batch (lzf_seg_parse_kernel, lz4_decompress_seg.hip) instead of being
+// hop parse of the segmented pipeline wrote for the whole batch (lzf_seg_parse_kernel, lz4_seg_front.hip) instead of being
 // worked out in the kernel.  Textual include inside the kernel's window loop.
 //
 // A WINDOW is kRound = 32 * W bytes of compressed input from cstart, the 32-aligned position at or below `expect`, the chain's next

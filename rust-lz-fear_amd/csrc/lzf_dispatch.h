@@ -148,7 +148,7 @@ inline SegGroups seg_groups(const Geometry& g, const Knobs& kn, uint32_t n_jobs)
 }
 
 // ---- scratch layouts -----------------------------------------------------------------------------------------------------------------
-// chunks of the parse over `len` compressed bytes (the device's seg_nch, lz4_decompress_seg.hip, is asserted against this one)
+// chunks of the parse over `len` compressed bytes (the device's seg_nch, lz4_seg_front.hip, is asserted against this one)
 constexpr uint32_t seg_nch(uint32_t len) { return len <= kSegChunk ? 1u : 1u + (len - kSegChunk + kSegStride - 1u) / kSegStride; }
 // A caller that knows an upper bound of its jobs' input sizes gets scratch sized for it (the job array is in HBM, the host cannot look).
 struct SegDims { uint32_t max_in, maxch, maxtile; };

@@ -5,7 +5,7 @@
 //   OutRing<RING>    the most recent RING bytes of output in LDS: ring index == output address mod RING (rb = out & 15 is the bias), so 16-byte
 //                    pieces of the ring line up with 16-byte pieces of HBM.  idx (RIDX), fill, flush; flush_lines (the fed kernel's deferred
 //                    flush: the whole 16-byte pieces of a range, the rest left to the caller).
-// The stager of lzf_seg_resolve_pair_kernel (lz4_decompress_seg.hip) keeps a written-out copy of the split, which names this one.
+// The stager of lzf_seg_resolve_pair_kernel (lz4_seg_resolve.hip) keeps a written-out copy of the split, which names this one.
 #ifndef LZF_OUT_RING_H
 #define LZF_OUT_RING_H
 

@@ -10,7 +10,7 @@
 // Positions are 64-bit: a block below the decoder's input limit (2 GiB) decodes to up to 255 x that, and callers pass
 // 2^63 - 1 as "no limit".
 //
-// One block over many wavefronts (lzf_size_tile_kernel / lzf_size_finish_kernel, lz4_decoded_size_seg.inc): sums compose.  The true
+// One block over many wavefronts (lzf_size_tile_kernel / lzf_size_finish_kernel, lz4_decoded_size_seg.hip): sums compose.  The true
 // tokens that start in a tile of compressed bytes are summarised RELATIVE to the tile's first token (TileSum, summarise); a second
 // pass that knows every tile's base position finishes the three checks (clean).  That path only says "clean, and this long" or
 // nothing: which error a job has, and where, stays with the token-by-token walk above.

@@ -3,7 +3,7 @@ and tests/alignment_check.py run them through tests/redzone.py with explicit pla
 
 Every decompress kernel flushes its LDS ring to `out` as a byte-wise head up to the next 16-byte address, 16-byte vector stores and
 a byte-wise tail, all computed from rb = out & 15 (lz4_decompress_paired.hip ring_flush, lz4_decompress_fed.hip,
-lz4_decompress_seg.hip flush_range / fill_to, lz4_decompress_batched.hip); the compress kernels read and write with unaligned
+lz4_seg_resolve.hip flush_range / fill_to, lz4_decompress_batched.hip); the compress kernels read and write with unaligned
 8 / 16-byte accesses.  Each builder below returns a Shape: `items` (as ffi.decompress_blocks_host / compress_blocks_host), `expect`
 ((status, bytes) from the oracle), the low address bits `in_low` / `out_low` / `prefix_low` of every job, and `meta` (what the job is
 there for, for the structural checks).

@@ -1,5 +1,5 @@
 """The launch-order stage — what decides which job of a large call runs first — as host models, built cases and a census.  Plain Python and
-numpy: no GPU, no library.  The stage is seven kernels and one accumulation of the parse kernel (aux_kernels.hip, lz4_decompress_seg.hip,
+numpy: no GPU, no library.  The stage is seven kernels and one accumulation of the parse kernel (aux_kernels.hip, lz4_seg_front.hip,
 the dry run of lz4_compress_compact.hip); the models restate each from the source:
 
   cost_est        lzf_decompress_cost_kernel: tokens sampled in three windows, scaled to the input, plus the bytes' share (integer-exact);
@@ -107,7 +107,7 @@ def chunk_marks(P, h):
 
 
 def fed_eligible(job, min_in):
-    """lz4_decompress_seg.hip:155-163 with fed = 1: prefix and existing output do not matter; the map's window, an input and an output do."""
+    """lzf_seg_plan_kernel (lz4_seg_front.hip:34-43) with fed = 1: prefix and existing output do not matter; the map's window, an input and an output do."""
     n = job["input_len"]
     return min_in <= n <= SEG_MAX_IN and job["input"] is not None and not job.get("null_out", False)
 

@@ -1,4 +1,4 @@
-"""Handcrafted token streams for the plain-hop loop of lzf_seg_parse_kernel (lz4_decompress_seg.hip: two hops per trip, the halves with
+"""Handcrafted token streams for the plain-hop loop of lzf_seg_parse_kernel (lz4_seg_front.hip: two hops per trip, the halves with
 the two position registers in each other's role), and a model of what that kernel does with a chunk: pass 0, the fixed-point passes, the
 rows.  The model walks lane by lane exactly as the kernel's C++ twin does and keeps, for every hop, where in the loop it ended (plain,
 stop, step back on a 0xFF match-length extension, parked on a 0xFF literal-length extension, fe, merged on a mark of row A) and in which

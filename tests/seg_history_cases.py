@@ -1,4 +1,4 @@
-"""Built edges of the segmented decompress pipeline (lz4_decompress_seg.hip) for jobs WITH HISTORY — existing output out[0, E) and a prefix
+"""Built edges of the segmented decompress pipeline (lz4_seg_*.hip) for jobs WITH HISTORY — existing output out[0, E) and a prefix
 of P bytes — and the host model of its stages for them.  Plain Python and numpy: no GPU, no library.  The builders, the parse and the
 history-free model are seg_stage_cases.py's; here:
 

@@ -1,4 +1,4 @@
-"""Built edges of the segmented decompress pipeline (lz4_decompress_seg.hip) and a host model of its stages.  Plain Python and numpy: no
+"""Built edges of the segmented decompress pipeline (lz4_seg_*.hip) and a host model of its stages.  Plain Python and numpy: no
 GPU, no library.  Three parts:
 
   * the builder: raw blocks assembled sequence by sequence (Blk; _seq / _block / _walk, which test_gpu_fed_decode_once.py and

@@ -1,4 +1,4 @@
-"""Cases of the size call's latency class (lz4_decoded_size_seg.inc; the rule: lzf_size_rules.h TileSum / summarise / clean), shared by
+"""Cases of the size call's latency class (lz4_decoded_size_seg.hip; the rule: lzf_size_rules.h TileSum / summarise / clean), shared by
 tests/test_size_tiles_cpu.py and tests/test_gpu_size_latency.py.  Plain Python and numpy + the oracle for the expectations.
 
 A case is decoded_size_cases' dict (input, prefix_len, existing_len, limit, prefix, existing) with a name; its expectation is the

@@ -345,7 +345,7 @@ def test_segmented_pipeline_grouped_beside_application_streams():
 
 @pytest.mark.parametrize("seed,nseq", [(41, 30000), (42, 60000), (43, 120000)])
 def test_segmented_pipeline_every_copy_class(seed, nseq):
-    """Handcrafted streams that hit every copy path of the resolver (lz4_decompress_seg.hip): the four two-ended sizes with and
+    """Handcrafted streams that hit every copy path of the resolver (lz4_seg_resolve.hip): the four two-ended sizes with and
     without run-length offsets (1, 2, 4 — classes 1-4 and 9-12), long run-length matches stored by the whole wave, overlapping
     ones, 65..160-byte matches alone and four or more to a level, matches of thousands of bytes — at every ring position (the
     streams decode to several MiB).  The oracle agrees with the generator; the GPU with both."""

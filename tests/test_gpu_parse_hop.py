@@ -1,5 +1,5 @@
 """lzf_seg_parse_kernel's plain-hop loop makes two hops per trip, the second with the two position registers in each other's role, and
-lets a lane leave on the vector side alone (lz4_decompress_seg.hip).  The handcrafted jobs of tests/parse_hop_cases.py — one chunk or
+lets a lane leave on the vector side alone (lz4_seg_front.hip).  The handcrafted jobs of tests/parse_hop_cases.py — one chunk or
 two, 60 jobs in one launch — put every exit of that loop into the first and into the second half of a trip: the stop position and fe
 after 1..5 hops, the step back on a 0xFF match-length extension, literal-length extensions 0 / 254 / 255, successors one short of, on and
 one beyond end_r and fe, the last two staged bytes, re-walks that merge on their 1st..4th hop or never, 64 regions with 1..6 hops side

@@ -1,5 +1,5 @@
 """lzf_seg_parse_kernel stages a chunk's 16 KiB with ONE round trip of sixteen 16-byte loads per lane: no branch around a load, a lane
-whose 16 bytes end behind the chunk's `avail` loads the last whole 16 bytes in front of it and stores zeros (lz4_decompress_seg.hip).
+whose 16 bytes end behind the chunk's `avail` loads the last whole 16 bytes in front of it and stores zeros (lz4_seg_front.hip).
 The shapes here are the smallest at which that can go wrong: inputs of one chunk, of two, with a ragged tail of 1 / 15 bytes behind
 the last whole 16, and with a short last chunk — kSegChunk and kSegChunk + kSegStride each - 1, + 0, + 1, and three and seven whole
 chunks + 0, 1, 15, 16, 17 bytes.  Every length runs with one workgroup per job (LZF_SEG_GRID: it loops over all the job's chunks, the

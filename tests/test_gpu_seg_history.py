@@ -1,4 +1,4 @@
-"""The segmented decompress pipeline (lz4_decompress_seg.hip) on jobs WITH HISTORY — existing output and prefixes — stage by stage on the built
+"""The segmented decompress pipeline (lz4_seg_*.hip) on jobs WITH HISTORY — existing output and prefixes — stage by stage on the built
 edges of seg_history_cases.py, whose reach test_seg_history_cases_cpu.py proves without a GPU.  The conventions are test_gpu_seg_stages.py's:
 for each ring (LZF_SEG_RING = 32, 64, 128 KiB) a child process runs lzf_debug_seg (analysis library, min_in = 0) up to the scan (5), the records
 stage (6) and the resolve stage (8), the outputs at address residues 0 and 9 and the prefixes at odd ones, and compares what the stages left

@@ -1,4 +1,4 @@
-"""The segmented decompress pipeline (lz4_decompress_seg.hip) stage by stage on the built edges of seg_stage_cases.py, whose reach
+"""The segmented decompress pipeline (lz4_seg_*.hip) stage by stage on the built edges of seg_stage_cases.py, whose reach
 test_seg_stage_cases_cpu.py proves without a GPU.  For each ring (LZF_SEG_RING = 32, 64, 128 KiB) a child process runs lzf_debug_seg
 (analysis library, min_in = 0) up to the seam stage (3), the scan (5), the records stage (6) and the resolve stage (8), the outputs at address
 residues 0 and 9, and compares what the stages left with the host model: chunk and tile counts, every chunk's exit, vfrom and bit row, the stitched

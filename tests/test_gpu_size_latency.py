@@ -1,4 +1,4 @@
-"""GPU tests (-m gpu) of the size call's latency class (lz4_decoded_size_seg.inc: a block summed up by many wavefronts).
+"""GPU tests (-m gpu) of the size call's latency class (lz4_decoded_size_seg.hip: a block summed up by many wavefronts).
 
 The kernels' edges — the seam, tile and damaged cases of seg_stage_cases.py (one tile up to 67 chunks), the CPU file's boundary cases,
 inputs of a tile's and a chunk's length and one byte more, 65 tiles, one 4 MiB block, an empty and a one-token input, one stray byte

@@ -1,4 +1,4 @@
-"""Stage-by-stage check of the segmented decompress pipeline (lz4_decompress_seg.hip) against a host parse of the same
+"""Stage-by-stage check of the segmented decompress pipeline (lz4_seg_*.hip) against a host parse of the same
 blocks: token bit maps after the seam stage, token / output totals after the scan, every record after the record stage (sub-batch,
 class, flags and dependency level included: the model of tests/seg_stage_cases.py), and the decoded bytes.  Needs the ANALYSIS library (lzf_debug_seg is not in the product):
     LZF_LIB_PATH=rust-lz-fear_amd/liblzfear_hip_analysis.so python tools/seg_debug.py [--big N] [--small]

@@ -1,5 +1,5 @@
 // tools/seg_helper_model.c — round 6, review item 4: would HELPER wavefronts that place the off-chain matches of a block ahead of the
-// resolver shorten the resolve stage of the segmented pipeline (lz4_decompress_seg.hip) by the 1.5 x that would justify building them?
+// resolver shorten the resolve stage of the segmented pipeline (lz4_seg_resolve.hip) by the 1.5 x that would justify building them?
 //
 // The resolve stage today (one resolver wavefront + one stager per block): per batch of 64 sequences the resolver runs one LDS round
 // trip per DEPENDENCY LEVEL of the batch's matches (level 1 = every source byte is final when the batch starts — literals are placed by
