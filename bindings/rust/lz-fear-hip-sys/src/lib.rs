@@ -125,6 +125,11 @@ extern "C" {
     // decompress_raw's status and output.len() per job without decoding (prefix, out and out_cap of the jobs are never dereferenced)
     pub fn lzf_decompressed_size_batch(d_jobs: *const lzf_decompress_job, d_results: *mut lzf_job_result, n_jobs: u32, max_input_len: u64, hip_stream: *mut c_void) -> c_int;
     pub fn lzf_decompressed_size_batch_host(jobs: *const lzf_decompress_job, results: *mut lzf_job_result, n_jobs: u32) -> c_int;
+    // compressed sizes without output: compress2's status and the bytes it would write per job, nothing written (`out` is never
+    // dereferenced, out_cap is honoured, a writable table is written back: size a copy of a table that is to be compressed from later)
+    pub fn lzf_compressed_size_batch(d_jobs: *const lzf_compress_job, d_results: *mut lzf_job_result, n_jobs: u32,
+                                     table_kinds: u32, hip_stream: *mut c_void) -> c_int;
+    pub fn lzf_compressed_size_batch_host(jobs: *const lzf_compress_job, results: *mut lzf_job_result, n_jobs: u32) -> c_int;
     pub fn lzf_last_decompress_launch() -> *const c_char;
     pub fn lzf_last_size_launch() -> *const c_char;
     pub fn lzf_last_compress_launch() -> *const c_char;
@@ -161,6 +166,14 @@ extern "C" {
     pub fn lzf_frame_compress_stream_device(s: *const lzf_settings, frame_bytes: usize, n_streams: u32, d_in: *const *const u8,
                                             in_len: *const usize, d_dict: *const u8, dict_len: usize, d_out: *const *mut u8,
                                             out_cap: *const usize, d_out_len: *mut u64, d_status: *mut i32, hip_stream: *mut c_void) -> c_int;
+    // the (status, out_len) of lzf_frame_compress_device_many / lzf_frame_compress_stream_device with outputs that hold the bound, without
+    // writing a frame: no output memory, no checksum computed, never LZF_OUT_CAPACITY
+    pub fn lzf_frame_compressed_size_device(s: *const lzf_settings, n_frames: u32, d_in: *const *const u8, in_len: *const usize,
+                                            d_dict: *const u8, dict_len: usize, d_out_len: *mut u64, d_status: *mut i32,
+                                            hip_stream: *mut c_void) -> c_int;
+    pub fn lzf_frame_compress_stream_size_device(s: *const lzf_settings, frame_bytes: usize, n_streams: u32, d_in: *const *const u8,
+                                                 in_len: *const usize, d_dict: *const u8, dict_len: usize, d_out_len: *mut u64,
+                                                 d_status: *mut i32, hip_stream: *mut c_void) -> c_int;
     // exact sizes and a frame index of streams, without decoding: what lzf_frame_decompress_stream_device would report per stream (the content
     // checksum not verified) and, with room for lzf_frame_stream_count_device's number of entries per stream, every frame's lzf_stream_frame.
     // d_index / index_cap: host arrays of device addresses / capacities in entries, both null for sizes only; d_n_frames, d_n_listed may be null

@@ -260,6 +260,24 @@ int lzf_frame_compress_device_many(const lzf_settings* s, uint32_t n_frames,
                                    const uint8_t* d_dict, size_t dict_len,
                                    uint8_t* const* d_out, const size_t* out_cap,
                                    uint64_t* d_out_len, int32_t* d_status, void* hip_stream);
+/* lzf_frame_compressed_size_device is to lzf_frame_compress_device_many what lzf_frame_decompressed_size_device is to the decoder:
+ * per frame the status and out_len that call reports for the same settings, dictionary bytes and input whenever out_cap[f] >=
+ * lzf_frame_compress_bound — WITHOUT writing a frame.  It never reports LZF_OUT_CAPACITY; a bad block size gives
+ * LZF_F_INVALID_BLOCK_SIZE / LZF_F_PANIC on every frame, and the first block status other than LZF_OK / LZF_OUTPUT_FULL, in
+ * block order, fails the frame with out_len 0, as there.  Conventions of lzf_frame_compress_device_many: d_in / in_len are HOST
+ * arrays of device addresses, d_out_len / d_status DEVICE arrays, s->dictionary must be NULL.
+ * A frame's length does not depend on its checksums' VALUES, so no checksum is computed: neither lzf_xxh32_batch nor the serial
+ * content chain is launched — with a content checksum in the settings the answer simply counts its 4 bytes.  The blocks go
+ * through lzf_compressed_size_batch with out_cap = the block's length (the stored-block decision is the status), linked frames
+ * in lock-step with lzf_table_offset_batch as in the compress call, and one wavefront per frame folds the block results into
+ * the frame's length.  No output memory: the scratch is the compress call's WITHOUT its output slots — job lists, results, the
+ * dictionary copies and the linked streams' tables, which are the call's own scratch tables — in passes of the memory budget.
+ * Nothing of the caller's is written except d_out_len / d_status.  The host reads nothing back and waits only for its upload
+ * of the job lists to leave host memory. */
+int lzf_frame_compressed_size_device(const lzf_settings* s, uint32_t n_frames,
+                                     const uint8_t* const* d_in, const size_t* in_len,
+                                     const uint8_t* d_dict, size_t dict_len,
+                                     uint64_t* d_out_len, int32_t* d_status, void* hip_stream);
 
 /* ---- streams of back-to-back frames in device memory ------------------------------------------------------------------
  * "This also allows LZ4 frames to be concatenated back to back" (src/framed/mod.rs:6).  A content checksum is one serial XXH32
@@ -461,6 +479,14 @@ int lzf_frame_compress_stream_device(const lzf_settings* s, size_t frame_bytes, 
                                      const uint8_t* d_dict, size_t dict_len,
                                      uint8_t* const* d_out, const size_t* out_cap,
                                      uint64_t* d_out_len, int32_t* d_status, void* hip_stream);
+/* lzf_frame_compress_stream_size_device: the out_len / status lzf_frame_compress_stream_device reports for the same arguments
+ * whenever out_cap[s] holds the bound — the sum over the pieces of frame_bytes, each piece a frame — without writing anything
+ * (lzf_frame_compressed_size_device over the pieces, folded per stream by the compress call's own one-wavefront-per-stream
+ * kernel).  Never LZF_OUT_CAPACITY; no checksum is computed, no output memory is taken. */
+int lzf_frame_compress_stream_size_device(const lzf_settings* s, size_t frame_bytes, uint32_t n_streams,
+                                          const uint8_t* const* d_in, const size_t* in_len,
+                                          const uint8_t* d_dict, size_t dict_len,
+                                          uint64_t* d_out_len, int32_t* d_status, void* hip_stream);
 
 /* Frame assembly from already-compressed blocks (what rank 0 does after the RCCL all-gather of a
  * block-sharded compression): writes header, then for every block

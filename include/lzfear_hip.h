@@ -133,6 +133,24 @@ int lzf_device_count(void);
 #define LZF_KINDS_U32_FRESH_ONLY 4u
 int lzf_compress_batch(const lzf_compress_job* d_jobs, lzf_job_result* d_results,
                        uint32_t n_jobs, uint32_t table_kinds, void* hip_stream);
+/* raw::compress2's status and the number of bytes it would write, for every job, WITHOUT writing them: no output memory is
+ * needed.  The parse is the compressor's own with the stores to the output left out, so the answer is exact.  Same job struct
+ * as lzf_compress_batch (size, then compress, with one array).
+ *   out      ignored and never dereferenced: NULL or a dangling pointer is fine.
+ *   out_cap  IS honoured: status and out_len are what lzf_compress_batch writes for the job, LZF_OUTPUT_FULL at the same capacity
+ *            included (out_len is then the bytes written before the refused sequence, as there).  A frame layer passes
+ *            out_cap = the block's length and reads the stored-block decision from the status; pass UINT64_MAX for the pure size.
+ *   table    a caller-owned table is read and written back exactly as lzf_compress_batch does — tables carry from block to
+ *            block of a linked stream, so a size query over a chain needs the mutation.  LZF_CJOB_TABLE_READONLY is respected.
+ *            To size and LATER COMPRESS a job that has a writable table, give the size call a COPY of the table: the
+ *            compress call must start from the table as it was before the size call.
+ *   reserved a diagnostic: the job's probe batches + sequences for a job the compact-table kernel answered, kilo-cycles otherwise.
+ * table_kinds as above; LZF_KINDS_U32_FRESH_ONLY is the same promise, and a job that breaks it reports LZF_CONTRACT.  The call
+ * launches the compact-table kernel and the general kernels in their dry forms whatever the job count (no latency class);
+ * batches larger than the device holds at once may run in the compress call's launch order.  lzf_last_compress_launch is not
+ * touched.  Asynchronous on `hip_stream`, no host wait; scratch (the launch order's) comes from the stream-ordered pool alone. */
+int lzf_compressed_size_batch(const lzf_compress_job* d_jobs, lzf_job_result* d_results,
+                              uint32_t n_jobs, uint32_t table_kinds, void* hip_stream);
 
 /* Batched raw::decompress_raw — src/raw/decompress.rs:58-138 for every job. */
 int lzf_decompress_batch(const lzf_decompress_job* d_jobs, lzf_job_result* d_results,
@@ -237,6 +255,10 @@ int lzf_decompress_batch_host(const lzf_decompress_job* jobs, lzf_job_result* re
 /* lzf_decompressed_size_batch over host buffers: `input` of every job is a HOST pointer (staged to the device), `results` a
  * host array; prefix, out and out_cap are ignored as above.  Synchronous. */
 int lzf_decompressed_size_batch_host(const lzf_decompress_job* jobs, lzf_job_result* results, uint32_t n_jobs);
+/* lzf_compressed_size_batch over host buffers: `input` and `table` of every job are HOST pointers (staged to the device; a
+ * writable table is updated in place, as lzf_compress_batch_host does), `results` a host array; `out` is ignored, out_cap is
+ * honoured as above.  Synchronous. */
+int lzf_compressed_size_batch_host(const lzf_compress_job* jobs, lzf_job_result* results, uint32_t n_jobs);
 /* EncoderTable::replace on a HOST table — src/raw/compress/mod.rs:19-25 (trait), :64-71 (U32Table), :88-96 (U16Table):
  * swaps `pos + table.offset` into the slot of hash(input[pos..]) and returns the previous entry minus table.offset,
  * saturating at 0 (stale entries read as position 0).  hash = hash_for_u32 (:40-51: 5 bytes of an 8-byte little-endian

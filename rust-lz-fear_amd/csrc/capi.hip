@@ -111,11 +111,14 @@ constexpr auto k_compact = lzf::lzf_compress_compact_kernel<false>;
 constexpr auto k_compact_dry = lzf::lzf_compress_compact_kernel<true>;
 constexpr auto k_general_u32 = lzf::lzf_compress_wave_kernel<LZF_TABLE_U32>;
 constexpr auto k_general_u16 = lzf::lzf_compress_wave_kernel<LZF_TABLE_U16>;
+constexpr auto k_general_u32_dry = lzf::lzf_compress_wave_kernel<LZF_TABLE_U32, true>;      // the size call's (lzf_compressed_size_batch)
+constexpr auto k_general_u16_dry = lzf::lzf_compress_wave_kernel<LZF_TABLE_U16, true>;
 constexpr auto k_size = lzf::lzf_decoded_size_kernel<48, 768, false>;
 constexpr auto k_size_skip = lzf::lzf_decoded_size_kernel<48, 768, true>;      // behind the latency class: skips what that finished
 
-// the launches of lzf_compress_batch: the cost probe and the order when the plan wants them and the pool has room, then the kernels
-int compress_launches(const d::CompressPlan& p, const lzf_compress_job* d_jobs, lzf_job_result* d_results, uint32_t n_jobs, AsyncScratch& scratch, hipStream_t st) {
+// the launch order of a compress or compressed-size call: the cost probe and the order when the plan wants them and the pool has room.
+// *perm_out = the order in `scratch`, or null: the caller's order.
+int compress_order(const d::CompressPlan& p, const lzf_compress_job* d_jobs, uint32_t n_jobs, AsyncScratch& scratch, hipStream_t st, uint32_t** perm_out) {
     const d::Knobs& kn = knobs();
     // the cost of a compress job is not known from its size: probe (aux_kernels.hip), then longest first
     // (one call over N four-MiB blocks, caller's order against longest first, probe included: 1 020 blocks 287 / 286 ms, 2 040 338 / 293,
@@ -135,6 +138,16 @@ int compress_launches(const d::CompressPlan& p, const lzf_compress_job* d_jobs, 
         if (rc == LZF_OK) rc = launch_order_by_cost(d_jobs, pres, perm, n_jobs, piece, parts, st);
         if (rc != LZF_OK) return rc;
     }
+    *perm_out = perm;
+    return LZF_OK;
+}
+
+// the launches of lzf_compress_batch: the order, then the kernels
+int compress_launches(const d::CompressPlan& p, const lzf_compress_job* d_jobs, lzf_job_result* d_results, uint32_t n_jobs, AsyncScratch& scratch, hipStream_t st) {
+    const d::Knobs& kn = knobs();
+    uint32_t* perm = nullptr;
+    const int orc = compress_order(p, d_jobs, n_jobs, scratch, st, &perm);
+    if (orc != LZF_OK) return orc;
     const uint32_t alone = p.fresh_only ? 1u : 0u;
     if (p.kinds & LZF_KINDS_U32) {
 #ifdef LZF_DBG_DRY_MAIN      // analysis: results[].reserved = probe batches + sequences of the whole job (no output)
@@ -153,6 +166,21 @@ int compress_launches(const d::CompressPlan& p, const lzf_compress_job* d_jobs, 
     if (p.kinds & LZF_KINDS_U16)
         LAUNCH(k_general_u16, dim3(n_jobs), dim3(64), 0, st, d_jobs, d_results, n_jobs, 0u, (const uint32_t*)perm);
     g_last_compress = p.launch;
+    return LZF_OK;
+}
+
+// the launches of lzf_compressed_size_batch: the same order, then the dry forms — the compact kernel over the jobs it takes in a
+// compress call, the general kernels over the rest.  No latency class: whatever the job count, the team kernel is not launched.
+int compressed_size_launches(const d::CompressPlan& p, const lzf_compress_job* d_jobs, lzf_job_result* d_results, uint32_t n_jobs, AsyncScratch& scratch, hipStream_t st) {
+    uint32_t* perm = nullptr;
+    const int orc = compress_order(p, d_jobs, n_jobs, scratch, st, &perm);
+    if (orc != LZF_OK) return orc;
+    if (p.kinds & LZF_KINDS_U32) {
+        if (p.use_compact) LAUNCH(k_compact_dry, dim3(n_jobs), dim3(64), 0, st, d_jobs, d_results, n_jobs, (const uint32_t*)perm, p.fresh_only ? 1u : 0u);
+        if (!p.fresh_only) LAUNCH(k_general_u32_dry, dim3(n_jobs), dim3(64), 0, st, d_jobs, d_results, n_jobs, p.use_compact ? 1u : 0u, (const uint32_t*)perm);
+    }
+    if (p.kinds & LZF_KINDS_U16)
+        LAUNCH(k_general_u16_dry, dim3(n_jobs), dim3(64), 0, st, d_jobs, d_results, n_jobs, 0u, (const uint32_t*)perm);
     return LZF_OK;
 }
 
@@ -228,6 +256,24 @@ int lzf_compress_batch(const lzf_compress_job* d_jobs, lzf_job_result* d_results
     keep_pool_memory(dv);
     AsyncScratch scratch(st);
     rc = compress_launches(d::compress_plan(dv.geo, knobs(), n_jobs, table_kinds), d_jobs, d_results, n_jobs, scratch, st);
+    HIP_TRY(scratch.release());
+    return rc;
+}
+
+// compress2's status and the bytes it would write for every job, nothing written: the plan of lzf_compress_batch without its latency
+// class, executed with the dry kernels.  `out` is never dereferenced; out_cap, the tables and table_kinds mean what they mean there.
+// Enqueue only: no host wait.  (lzf_last_compress_launch is left alone: it speaks of the last lzf_compress_batch.)
+int lzf_compressed_size_batch(const lzf_compress_job* d_jobs, lzf_job_result* d_results, uint32_t n_jobs,
+                              uint32_t table_kinds, void* hip_stream) {
+    if (n_jobs == 0) return LZF_OK;
+    if (!d_jobs || !d_results) { g_last_error = "lzf_compressed_size_batch: NULL job/result array"; return LZF_E_INVALID; }
+    int rc = ensure_device();
+    if (rc < 0) return rc;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    Device& dv = device();
+    keep_pool_memory(dv);
+    AsyncScratch scratch(st);
+    rc = compressed_size_launches(d::compress_plan(dv.geo, knobs(), n_jobs, table_kinds), d_jobs, d_results, n_jobs, scratch, st);
     HIP_TRY(scratch.release());
     return rc;
 }

@@ -91,6 +91,43 @@ int lzf_compress_batch_host(const lzf_compress_job* jobs, lzf_job_result* result
     return LZF_OK;
 }
 
+int lzf_compressed_size_batch_host(const lzf_compress_job* jobs, lzf_job_result* results, uint32_t n_jobs) {
+    if (n_jobs == 0) return LZF_OK;
+    if (!jobs || !results) { g_last_error = "lzf_compressed_size_batch_host: NULL argument"; return LZF_E_INVALID; }
+    int rc = ensure_device();
+    if (rc < 0) return rc;
+    // one slab [inputs | tables] going up; `out` is not read by the size call and stays what it is (never dereferenced), out_cap is honoured
+    std::vector<size_t> in_off(n_jobs), tab_off(n_jobs);
+    size_t in_total = 0;
+    uint32_t kinds = 0;
+    std::vector<Seg> up;
+    for (uint32_t i = 0; i < n_jobs; ++i) {
+        if (jobs[i].table_kind > LZF_TABLE_U16) { g_last_error = "bad table_kind"; return LZF_E_INVALID; }
+        if (jobs[i].input_len && !jobs[i].input) { g_last_error = "lzf_compressed_size_batch_host: NULL input"; return LZF_E_INVALID; }
+        kinds |= jobs[i].table_kind == LZF_TABLE_U32 ? LZF_KINDS_U32 : LZF_KINDS_U16;
+        in_off[i] = in_total; in_total = align_up(in_total + jobs[i].input_len, 256);
+        if (jobs[i].input_len) up.push_back({in_off[i], const_cast<uint8_t*>(jobs[i].input), (size_t)jobs[i].input_len});
+    }
+    for (uint32_t i = 0; i < n_jobs; ++i) {
+        tab_off[i] = in_total;
+        if (jobs[i].table) { up.push_back({tab_off[i], static_cast<uint8_t*>(jobs[i].table), sizeof(lzf_u32_table)}); in_total = align_up(in_total + sizeof(lzf_u32_table), 256); }
+    }
+    HostCall<lzf_compress_job> h;
+    if ((rc = h.open(n_jobs, in_total ? in_total : 256, 0, false)) != LZF_OK) return rc;
+    std::vector<lzf_compress_job> dj(jobs, jobs + n_jobs);
+    for (uint32_t i = 0; i < n_jobs; ++i) {
+        dj[i].input = h.din + in_off[i];
+        if (jobs[i].table) dj[i].table = h.din + tab_off[i];
+    }
+    if ((rc = h.send(up, in_total, dj)) != LZF_OK) return rc;
+    if ((rc = h.fetch(lzf_compressed_size_batch(h.djobs, h.dres, n_jobs, kinds, h.cs), results)) != LZF_OK) return rc;
+    for (uint32_t i = 0; i < n_jobs; ++i)         // a writable table comes back as lzf_compress_batch_host leaves it
+        if (jobs[i].table && !(jobs[i].flags & LZF_CJOB_TABLE_READONLY) && results[i].status != LZF_CONTRACT)
+            HIP_TRY(hipMemcpyAsync(jobs[i].table, h.din + tab_off[i], sizeof(lzf_u32_table), hipMemcpyDeviceToHost, h.cs));
+    HIP_TRY(hipStreamSynchronize(h.cs));
+    return LZF_OK;
+}
+
 int lzf_decompress_batch_host(const lzf_decompress_job* jobs, lzf_job_result* results, uint32_t n_jobs) {
     if (n_jobs == 0) return LZF_OK;
     if (!jobs || !results) { g_last_error = "lzf_decompress_batch_host: NULL argument"; return LZF_E_INVALID; }

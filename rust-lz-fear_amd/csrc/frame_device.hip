@@ -18,6 +18,10 @@
 // out_len, and the lists of the steps behind it, by lzf_frame_layout.h's rule), the payload copy (lzf_copy_ranges), block and
 // content checksums (lzf_xxh32_batch) and the checksum words (lzf_frame_patch_kernel).
 //
+// lzf_frame_compressed_size_device / lzf_frame_compress_stream_size_device: the compress plan with `sizes_only` — no output slots,
+// jobs without `out` through lzf_compressed_size_batch, then lzf_frame_size_fold_kernel (per frame) or lzf_stream_pack_kernel (per
+// stream) over the job results alone: the (status, out_len) of the compress calls, nothing written, no checksum computed.
+//
 // lzf_frame_decompress_stream_device / lzf_frame_compress_stream_device: streams of back-to-back frames.  Decode: the stream scan
 // (lzf_stream_scan_kernel, lzf_stream_walk.h, one lane per stream, two launches and two waits) lists the frames, which then go
 // through the decode above (decode_frames); per pass, behind the decode launches, the count-only delivery finds every frame's
@@ -382,6 +386,32 @@ __global__ __launch_bounds__(64) void lzf_frame_assemble_kernel(const CFrameDesc
     d_status[F.frame] = st;
     d_out_len[F.frame] = ok ? w + lzf_layout::tail_len(csum) : 0ull;
     if (F.hash_idx != kNone) c_at[F.hash_idx] = ok ? F.dst + w + 4 : nullptr;     // (:279-281)
+}
+
+// lzf_frame_compressed_size_device: the assembly kernel's rule with nothing assembled.  One wavefront per frame, 64 blocks per
+// round: the first block, in block order, whose status is neither LZF_OK nor LZF_OUTPUT_FULL fails the frame with out_len 0;
+// otherwise the frame is its header, every block's block_span (a refused block counts its raw length: stored), the EndMark and
+// the content checksum's 4 bytes when the settings ask for one.  Nothing but d_status / d_out_len is written.
+__global__ __launch_bounds__(64) void lzf_frame_size_fold_kernel(const CFrameDesc* __restrict__ frames, const CBlkDesc* __restrict__ blks,
+                                                                 const lzf_job_result* __restrict__ res, uint32_t hdr_len, uint32_t flags,
+                                                                 int32_t* __restrict__ d_status, uint64_t* __restrict__ d_out_len) {
+    const CFrameDesc F = frames[blockIdx.x];
+    const uint32_t lane = threadIdx.x;
+    const bool bsum = (flags & kBlockSums) != 0, csum = (flags & kContentSum) != 0;
+    int st = F.status0;
+    uint64_t w = hdr_len;
+    for (uint32_t base = 0; st == LZF_OK && base < F.nb; base += 64u) {
+        const uint32_t i = base + lane;
+        const bool act = i < F.nb;
+        lzf_layout::Block b{0u, false, false, LZF_OK};
+        if (act) { const CBlkDesc c = blks[F.blk0 + i]; const lzf_job_result r = res[c.job]; b = lzf_layout::block_of(r.status, r.out_len, c.raw_len); }
+        const uint64_t bad = __ballot(b.bad);
+        if (bad) { st = __shfl(b.status, (int)__builtin_ctzll(bad), 64); break; }
+        w += wave_sum(act ? lzf_layout::block_span(b.len, bsum) : 0ull);
+    }
+    if (lane != 0) return;
+    d_status[F.frame] = st;
+    d_out_len[F.frame] = st == LZF_OK ? w + lzf_layout::tail_len(csum) : 0ull;
 }
 
 // Streams of frames (lzf_frame_compress_stream_device): the frames of one stream, CFrameDesc [fd0, fd0 + nf) of the pass, go
@@ -1255,9 +1285,14 @@ struct CStreamCtx {
 
 // lzf_frame_compress_device_many's work for n >= 1 frames on a usable device; with `cx` the frames of a stream are packed
 // behind each other on the device (lzf_stream_pack_kernel in front of the assembly).
+// sizes_only (lzf_frame_compressed_size_device, lzf_frame_compress_stream_size_device): the same plan without output — d_out and
+// out_cap are NULL, no frame is short of capacity, no output slots are taken, the jobs have no `out` and go through
+// lzf_compressed_size_batch, and behind them only the results are folded: lzf_frame_size_fold_kernel per frame, or, with `cx`,
+// lzf_stream_pack_kernel per stream (its places are offsets from NULL that nobody reads).  No copy, no checksum, no patch.
 int compress_frames(const lzf_settings* s, const uint32_t n, const uint8_t* const* d_in, const size_t* in_len,
                     const uint8_t* d_dict, size_t dict_len, uint8_t* const* d_out, const size_t* out_cap,
-                    uint64_t* d_out_len, int32_t* d_status, hipStream_t st, const CStreamCtx* cx) {
+                    uint64_t* d_out_len, int32_t* d_status, hipStream_t st, const CStreamCtx* cx, const bool sizes_only) {
+    const auto batch_call = sizes_only ? lzf_compressed_size_batch : lzf_compress_batch;
     uint8_t bd = 0;
     const int bd_rc = lzf_layout::bd_new(s->block_size, &bd);  // compress.rs:183
     const size_t bs = bd_rc == LZF_OK ? (size_t)s->block_size : 1;
@@ -1289,10 +1324,10 @@ int compress_frames(const lzf_settings* s, const uint32_t n, const uint8_t* cons
         return per_block_prefix ? nb[f] * dict_len + in_len[f] : (!indep && nb[f] && dict_len) ? dict_len + (in_len[f] < bs ? in_len[f] : bs) : 0;
     };
     for (uint32_t f = 0; f < n; ++f) {
-        status0[f] = bd_rc != LZF_OK ? bd_rc : out_cap[f] < lzf_frame_compress_bound(s, in_len[f]) ? LZF_OUT_CAPACITY : LZF_OK;
+        status0[f] = bd_rc != LZF_OK ? bd_rc : !sizes_only && out_cap[f] < lzf_frame_compress_bound(s, in_len[f]) ? LZF_OUT_CAPACITY : LZF_OK;
         if (status0[f] != LZF_OK) continue;
         nb[f] = (in_len[f] + bs - 1) / bs;
-        need[f] = in_len[f] + copies_of(f) + (indep ? 0 : sizeof(lzf_u32_table)) + 256 * nb[f] + 4096;   // output slots, copies, table, lists
+        need[f] = (sizes_only ? 0 : in_len[f]) + copies_of(f) + (indep ? 0 : sizeof(lzf_u32_table)) + 256 * nb[f] + 4096;   // output slots, copies, table, lists
     }
     // ---- passes of the memory budget (frame_jobs.h's split_passes); a frame whose scratch alone is over it is a pass of its own;
     //      streams: a pass holds whole streams
@@ -1311,7 +1346,7 @@ int compress_frames(const lzf_settings* s, const uint32_t n, const uint8_t* cons
     for (CPass& P : passes) {
         for (uint32_t f = P.f0; f < P.f1; ++f) {
             if (!nb[f]) continue;
-            P.n_jobs += (uint32_t)nb[f]; P.slots += in_len[f]; P.copies += copies_of(f);
+            P.n_jobs += (uint32_t)nb[f]; P.slots += sizes_only ? 0 : in_len[f]; P.copies += copies_of(f);
             if (!indep) ++P.n_linked;
         }
         P.tables = sizeof(lzf_u32_table) * (size_t)P.n_linked;
@@ -1364,11 +1399,11 @@ int compress_frames(const lzf_settings* s, const uint32_t n, const uint8_t* cons
                 j.input = c; copy += W.hist + W.n;
             } else j.input = d_in[f] + (W.lo - (indep ? 0 : dict_len));
             j.input_len = W.hist + W.n; j.cursor = W.hist;                             // :222,:243
-            j.out = dslots + slot; j.out_cap = W.n; j.table_kind = LZF_TABLE_U32;      // :242, :202
+            j.out = sizes_only ? nullptr : dslots + slot; j.out_cap = W.n; j.table_kind = LZF_TABLE_U32;      // :242, :202
             if (indep) { if (d_tmpl) { j.table = d_tmpl; j.flags = LZF_CJOB_TABLE_READONLY; } }   // :220,:270 template.clone()
             else { j.table = dtabs + lf[f - P.f0]; tabptr.push_back(j.table); adds.push_back(W.add); }
-            bdesc[jn] = CBlkDesc{d_in[f] + W.off, dslots + slot, jn, (uint32_t)W.n};
-            slot += W.n;
+            bdesc[jn] = CBlkDesc{d_in[f] + W.off, j.out, jn, (uint32_t)W.n};
+            if (!sizes_only) slot += W.n;
             frame_job[f - P.f0].push_back(jn);
             ++jn;
         };
@@ -1387,14 +1422,14 @@ int compress_frames(const lzf_settings* s, const uint32_t n, const uint8_t* cons
         for (uint32_t f = P.f0; f < P.f1; ++f) {
             CFrameDesc d;
             memset(&d, 0, sizeof d);
-            d.dst = d_out[f]; d.blk0 = (uint32_t)blks.size(); d.nb = (uint32_t)nb[f]; d.status0 = status0[f]; d.frame = f; d.hash_idx = kNone;
+            d.dst = sizes_only ? nullptr : d_out[f]; d.blk0 = (uint32_t)blks.size(); d.nb = (uint32_t)nb[f]; d.status0 = status0[f]; d.frame = f; d.hash_idx = kNone;
             for (uint32_t q : frame_job[f - P.f0]) blks.push_back(bdesc[q]);
-            if (csum && status0[f] == LZF_OK) {                 // (an empty input: no bytes to read, any valid address)
+            if (csum && !sizes_only && status0[f] == LZF_OK) {                 // (an empty input: no bytes to read, any valid address)
                 d.hash_idx = (uint32_t)hptr.size(); hptr.push_back(in_len[f] ? d_in[f] : d_out[f]); hlen.push_back(in_len[f]);
             }
             if (cx) {                                           // (dst: lzf_stream_pack_kernel puts the frame behind the one before it)
                 if (!hdr_idx.empty()) d.hdr_idx = hdr_idx[f];
-                if (segs.empty() || segs.back().stream != stream_of[f]) segs.push_back(CSeg{d_out[f], (uint32_t)fd.size(), 0u, stream_of[f], status0[f]});
+                if (segs.empty() || segs.back().stream != stream_of[f]) segs.push_back(CSeg{d.dst, (uint32_t)fd.size(), 0u, stream_of[f], status0[f]});
                 ++segs.back().nf;
             }
             fd.push_back(d);
@@ -1407,9 +1442,10 @@ int compress_frames(const lzf_settings* s, const uint32_t n, const uint8_t* cons
         P.i_tps = meta.add(tps); P.i_tpd = meta.add(tpd); P.i_tpl = meta.add(tpl);
         P.i_frames = meta.add(fd); P.i_blks = meta.add(blks);
         P.i_hptr = meta.add(hptr); P.i_hlen = meta.add(hlen);
-        const size_t n_at = (bsum ? (size_t)P.n_jobs : 0) + P.n_hash;
+        const size_t n_at = sizes_only ? 0 : (bsum ? (size_t)P.n_jobs : 0) + P.n_hash;
+        const size_t n_ranges = sizes_only ? 0 : (size_t)P.n_jobs;
         P.s_res = meta.room(sizeof(lzf_job_result) * (size_t)P.n_jobs);
-        P.s_rsrc = meta.room(8 * (size_t)P.n_jobs); P.s_rdst = meta.room(8 * (size_t)P.n_jobs); P.s_rlen = meta.room(8 * (size_t)P.n_jobs);
+        P.s_rsrc = meta.room(8 * n_ranges); P.s_rdst = meta.room(8 * n_ranges); P.s_rlen = meta.room(8 * n_ranges);
         P.s_at = meta.room(8 * n_at); P.s_val = meta.room(4 * n_at);
     }
     // ---- one upload, then the launches of every pass (the kernels write every scratch entry they read: no zeroing)
@@ -1429,14 +1465,23 @@ int compress_frames(const lzf_settings* s, const uint32_t n, const uint8_t* cons
                                                P.n_linked, sizeof(lzf_u32_table), st));
             else DEV_TRY(hipMemsetAsync(work.at<uint8_t>(up256(P.slots) + up256(P.copies)), 0, P.tables, st));
         }
-        if (P.n_jobs && indep) RC_TRY(lzf_compress_batch(jobs, res, P.n_jobs, LZF_KINDS_U32 | LZF_KINDS_U32_FRESH_ONLY, st));
+        if (P.n_jobs && indep) RC_TRY(batch_call(jobs, res, P.n_jobs, LZF_KINDS_U32 | LZF_KINDS_U32_FRESH_ONLY, st));
         else if (P.n_jobs) {
             for (size_t k = 0; k + 1 < P.step_off.size(); ++k) {    // no host round trip between the steps
                 const size_t a = P.step_off[k], c = P.step_off[k + 1] - a;
                 if (!c) continue;
                 if (k > 0) RC_TRY(lzf_table_offset_batch(meta.img<void* const>(P.i_tabptr) + a, meta.img<const uint64_t>(P.i_adds) + a, (uint32_t)c, LZF_TABLE_U32, st));
-                RC_TRY(lzf_compress_batch(jobs + a, res + a, (uint32_t)c, LZF_KINDS_U32, st));
+                RC_TRY(batch_call(jobs + a, res + a, (uint32_t)c, LZF_KINDS_U32, st));
             }
+        }
+        if (sizes_only) {                                       // the lengths from the results: nothing is assembled, copied or hashed
+            if (cx)
+                KERNEL(lzf_stream_pack_kernel, dim3(P.n_segs), dim3(64), 0, st, meta.img<const CSeg>(P.i_segs), meta.img<CFrameDesc>(P.i_frames),
+                       meta.img<const CBlkDesc>(P.i_blks), (const lzf_job_result*)res, hdr_len, flags, cx->s_status, cx->s_out_len);
+            else
+                KERNEL(lzf_frame_size_fold_kernel, dim3(P.n_frames), dim3(64), 0, st, meta.img<const CFrameDesc>(P.i_frames), meta.img<const CBlkDesc>(P.i_blks),
+                       (const lzf_job_result*)res, hdr_len, flags, d_status, d_out_len);
+            continue;
         }
         const size_t n_sums = bsum ? (size_t)P.n_jobs : 0;
         uint8_t** const at = meta.scr<uint8_t*>(P.s_at);
@@ -1456,6 +1501,38 @@ int compress_frames(const lzf_settings* s, const uint32_t n, const uint8_t* cons
     }
     return meta.wait();                                         // the image has left host memory; the launches run on
 }
+
+// lzf_frame_compress_stream_device's work behind its argument checks: the pieces of every input as frames of compress_frames.
+// sizes_only (lzf_frame_compress_stream_size_device): d_out / out_cap are NULL, and the frames need no status and length of their own.
+int compress_streams(const lzf_settings* s, size_t frame_bytes, uint32_t n_streams, const uint8_t* const* d_in, const size_t* in_len,
+                     const uint8_t* d_dict, size_t dict_len, uint8_t* const* d_out, const size_t* out_cap,
+                     uint64_t* d_out_len, int32_t* d_status, hipStream_t st, const bool sizes_only) {
+    if (s->dictionary) return LZF_E_INVALID;
+    if (!d_dict) dict_len = 0;
+    if (usable_device() != LZF_OK) return LZF_E_NO_DEVICE;
+    if (n_streams == 0) return LZF_OK;
+    // the pieces: stream q is max(1, ceil(in_len[q] / frame_bytes)) frames of the call
+    std::vector<uint64_t> first((size_t)n_streams + 1, 0);
+    for (uint32_t q = 0; q < n_streams; ++q) { const uint64_t k = (in_len[q] + frame_bytes - 1) / frame_bytes; first[q + 1] = first[q] + (k ? k : 1); }
+    const size_t n = (size_t)first[n_streams];
+    if (n > 0x7FFFFFFFull) return LZF_E_INVALID;
+    std::vector<const uint8_t*> f_in(n); std::vector<size_t> f_len(n), f_cap(n); std::vector<uint8_t*> f_out(n);
+    for (uint32_t q = 0; q < n_streams; ++q) {
+        const size_t cap = sizes_only || out_cap[q] >= lzf_frame_compress_stream_bound(s, frame_bytes, in_len[q]) ? SIZE_MAX : 0;
+        for (uint64_t f = first[q]; f < first[q + 1]; ++f) {
+            const size_t off = (size_t)(f - first[q]) * frame_bytes;
+            f_in[(size_t)f] = d_in[q] + off; f_len[(size_t)f] = in_len[q] - off < frame_bytes ? in_len[q] - off : frame_bytes;
+            f_out[(size_t)f] = sizes_only ? nullptr : d_out[q]; f_cap[(size_t)f] = cap;
+        }
+    }
+    const CStreamCtx cx{n_streams, first.data(), d_status, d_out_len};
+    if (sizes_only) return compress_frames(s, (uint32_t)n, f_in.data(), f_len.data(), d_dict, dict_len, nullptr, nullptr, nullptr, nullptr, st, &cx, true);
+    const size_t o_len = up256(4 * n);
+    PoolAlloc per(st);                                          // the frames' own status and length: scratch
+    if (!per.get(o_len + 8 * n)) return LZF_E_HIP;
+    return compress_frames(s, (uint32_t)n, f_in.data(), f_len.data(), d_dict, dict_len, f_out.data(), f_cap.data(),
+                           per.at<uint64_t>(o_len), per.at<int32_t>(0), st, &cx, false);
+}
 }  // namespace
 
 extern "C" {
@@ -1468,7 +1545,17 @@ int lzf_frame_compress_device_many(const lzf_settings* s, uint32_t n_frames, con
     if (!d_dict) dict_len = 0;
     if (usable_device() != LZF_OK) return LZF_E_NO_DEVICE;
     if (n_frames == 0) return LZF_OK;
-    return compress_frames(s, n_frames, d_in, in_len, d_dict, dict_len, d_out, out_cap, d_out_len, d_status, static_cast<hipStream_t>(hip_stream), nullptr);
+    return compress_frames(s, n_frames, d_in, in_len, d_dict, dict_len, d_out, out_cap, d_out_len, d_status, static_cast<hipStream_t>(hip_stream), nullptr, false);
+}
+
+int lzf_frame_compressed_size_device(const lzf_settings* s, uint32_t n_frames, const uint8_t* const* d_in, const size_t* in_len,
+                                     const uint8_t* d_dict, size_t dict_len, uint64_t* d_out_len, int32_t* d_status, void* hip_stream) {
+    if (!s || (n_frames && (!d_in || !in_len || !d_out_len || !d_status))) return LZF_E_INVALID;
+    if (s->dictionary) return LZF_E_INVALID;
+    if (!d_dict) dict_len = 0;
+    if (usable_device() != LZF_OK) return LZF_E_NO_DEVICE;
+    if (n_frames == 0) return LZF_OK;
+    return compress_frames(s, n_frames, d_in, in_len, d_dict, dict_len, nullptr, nullptr, d_out_len, d_status, static_cast<hipStream_t>(hip_stream), nullptr, true);
 }
 
 size_t lzf_frame_compress_stream_bound(const lzf_settings* s, size_t frame_bytes, size_t in_len) {
@@ -1482,31 +1569,15 @@ int lzf_frame_compress_stream_device(const lzf_settings* s, size_t frame_bytes, 
                                      const uint8_t* d_dict, size_t dict_len, uint8_t* const* d_out, const size_t* out_cap,
                                      uint64_t* d_out_len, int32_t* d_status, void* hip_stream) {
     if (!s || !frame_bytes || (n_streams && (!d_in || !in_len || !d_out || !out_cap || !d_out_len || !d_status))) return LZF_E_INVALID;
-    if (s->dictionary) return LZF_E_INVALID;
-    if (!d_dict) dict_len = 0;
-    if (usable_device() != LZF_OK) return LZF_E_NO_DEVICE;
-    if (n_streams == 0) return LZF_OK;
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    // the pieces: stream q is max(1, ceil(in_len[q] / frame_bytes)) frames of the call
-    std::vector<uint64_t> first((size_t)n_streams + 1, 0);
-    for (uint32_t q = 0; q < n_streams; ++q) { const uint64_t k = (in_len[q] + frame_bytes - 1) / frame_bytes; first[q + 1] = first[q] + (k ? k : 1); }
-    const size_t n = (size_t)first[n_streams];
-    if (n > 0x7FFFFFFFull) return LZF_E_INVALID;
-    std::vector<const uint8_t*> f_in(n); std::vector<size_t> f_len(n), f_cap(n); std::vector<uint8_t*> f_out(n);
-    for (uint32_t q = 0; q < n_streams; ++q) {
-        const size_t cap = out_cap[q] >= lzf_frame_compress_stream_bound(s, frame_bytes, in_len[q]) ? SIZE_MAX : 0;
-        for (uint64_t f = first[q]; f < first[q + 1]; ++f) {
-            const size_t off = (size_t)(f - first[q]) * frame_bytes;
-            f_in[(size_t)f] = d_in[q] + off; f_len[(size_t)f] = in_len[q] - off < frame_bytes ? in_len[q] - off : frame_bytes;
-            f_out[(size_t)f] = d_out[q]; f_cap[(size_t)f] = cap;
-        }
-    }
-    const size_t o_len = up256(4 * n);
-    PoolAlloc per(st);                                          // the frames' own status and length: scratch
-    if (!per.get(o_len + 8 * n)) return LZF_E_HIP;
-    const CStreamCtx cx{n_streams, first.data(), d_status, d_out_len};
-    return compress_frames(s, (uint32_t)n, f_in.data(), f_len.data(), d_dict, dict_len, f_out.data(), f_cap.data(),
-                           per.at<uint64_t>(o_len), per.at<int32_t>(0), st, &cx);
+    return compress_streams(s, frame_bytes, n_streams, d_in, in_len, d_dict, dict_len, d_out, out_cap, d_out_len, d_status, static_cast<hipStream_t>(hip_stream), false);
+}
+
+int lzf_frame_compress_stream_size_device(const lzf_settings* s, size_t frame_bytes, uint32_t n_streams,
+                                          const uint8_t* const* d_in, const size_t* in_len,
+                                          const uint8_t* d_dict, size_t dict_len,
+                                          uint64_t* d_out_len, int32_t* d_status, void* hip_stream) {
+    if (!s || !frame_bytes || (n_streams && (!d_in || !in_len || !d_out_len || !d_status))) return LZF_E_INVALID;
+    return compress_streams(s, frame_bytes, n_streams, d_in, in_len, d_dict, dict_len, nullptr, nullptr, d_out_len, d_status, static_cast<hipStream_t>(hip_stream), true);
 }
 
 }  // extern "C"

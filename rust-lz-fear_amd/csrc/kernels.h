@@ -212,12 +212,15 @@ __global__ __launch_bounds__(128) void lzf_seg_resolve_pair_kernel(seg_ctx c);
 extern template __global__ void lzf_seg_resolve_pair_kernel<32768>(seg_ctx);
 extern template __global__ void lzf_seg_resolve_pair_kernel<65536>(seg_ctx);
 extern template __global__ void lzf_seg_resolve_pair_kernel<131072>(seg_ctx);
-template <int KIND>
+// DRY: the size call's form (lzf_compressed_size_batch) — the same parse, no store to `out`
+template <int KIND, bool DRY = false>
 __global__ __launch_bounds__(64) void lzf_compress_wave_kernel(const lzf_compress_job* __restrict__ jobs,
                                          lzf_job_result* __restrict__ results, uint32_t n_jobs, uint32_t skip_compact,
                                          const uint32_t* __restrict__ perm);
-extern template __global__ void lzf_compress_wave_kernel<LZF_TABLE_U32>(const lzf_compress_job*, lzf_job_result*, uint32_t, uint32_t, const uint32_t*);
-extern template __global__ void lzf_compress_wave_kernel<LZF_TABLE_U16>(const lzf_compress_job*, lzf_job_result*, uint32_t, uint32_t, const uint32_t*);
+extern template __global__ void lzf_compress_wave_kernel<LZF_TABLE_U32, false>(const lzf_compress_job*, lzf_job_result*, uint32_t, uint32_t, const uint32_t*);
+extern template __global__ void lzf_compress_wave_kernel<LZF_TABLE_U16, false>(const lzf_compress_job*, lzf_job_result*, uint32_t, uint32_t, const uint32_t*);
+extern template __global__ void lzf_compress_wave_kernel<LZF_TABLE_U32, true>(const lzf_compress_job*, lzf_job_result*, uint32_t, uint32_t, const uint32_t*);
+extern template __global__ void lzf_compress_wave_kernel<LZF_TABLE_U16, true>(const lzf_compress_job*, lzf_job_result*, uint32_t, uint32_t, const uint32_t*);
 // LDS of one workgroup of lzf_compress_compact_kernel: 2048 words of slots + 128 of epoch parities + one scratch word per lane (the dispatch derives its residency from this)
 constexpr uint32_t kCompactLdsBytes = (4096u / 2u + 4096u / 32u + 64u) * 4u;
 template <bool DRY>

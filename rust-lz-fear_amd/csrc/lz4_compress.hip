@@ -43,7 +43,10 @@ template <> struct TableTraits<LZF_TABLE_U16> {
     }
 };
 
-template <int KIND>
+// DRY = the size call (capi.hip: lzf_compressed_size_batch): the same parse with every store to the output, and every load that only
+// feeds one, dropped at compile time; the table, the sink's pos / cap arithmetic, the statuses and the write-back of a caller-owned
+// table are the compressing form's, so out_len and status are what that form reports.  `out` is never dereferenced.
+template <int KIND, bool DRY>
 __global__ __launch_bounds__(64) void lzf_compress_wave_kernel(
     const lzf_compress_job* __restrict__ jobs, lzf_job_result* __restrict__ results, uint32_t n_jobs, uint32_t skip_compact,
     const uint32_t* __restrict__ perm) {
@@ -245,10 +248,12 @@ __global__ __launch_bounds__(64) void lzf_compress_wave_kernel(
                     status = LZF_OUTPUT_FULL;
                     break;
                 }
-                gu8* d = s.out + s.pos;
-                if (lane == 0) d[0] = (uint8_t)((L < 15u ? L : 15u) << 4);
-                if (nl) lsic_store(d + 1, L, nl, lane);
-                wave_copy(d + 1u + nl, in + ls, L, lane);
+                if constexpr (!DRY) {
+                    gu8* d = s.out + s.pos;
+                    if (lane == 0) d[0] = (uint8_t)((L < 15u ? L : 15u) << 4);
+                    if (nl) lsic_store(d + 1, L, nl, lane);
+                    wave_copy(d + 1u + nl, in + ls, L, lane);
+                }
                 s.pos += total;
                 cursor = len;
                 break;
@@ -305,7 +310,7 @@ __global__ __launch_bounds__(64) void lzf_compress_wave_kernel(
             const uint32_t lit_len = (m_pos - bt) - ls;                    // = L below
             const bool lit_fast = lit_len <= 1024u;
             uint32_t lit_b = 0, lit_t = 0; u32x4 lit_v = {0, 0, 0, 0};
-            if (lit_fast) {
+            if (!DRY && lit_fast) {      // (loads that only feed the stores below)
                 if (lit_len <= kWave) { if (lane < lit_len) lit_b = in[ls + lane]; }
                 else {
                     const uint32_t bulk = lit_len & ~15u;
@@ -347,25 +352,27 @@ __global__ __launch_bounds__(64) void lzf_compress_wave_kernel(
             const uint32_t nl = lsic_len(L), ne = lsic_len(extra);
             const uint32_t total = 1u + nl + L + 2u + ne;
             if (s.cap - s.pos < total) { status = LZF_OUTPUT_FULL; break; }
-            gu8* d = s.out + s.pos;
-            if (lane == 0) {
-                d[0] = (uint8_t)(((L < 15u ? L : 15u) << 4) | (extra < 15u ? extra : 15u));
-                d[1u + nl + L] = (uint8_t)dup_offset;
-                d[2u + nl + L] = (uint8_t)(dup_offset >> 8);
-            }
-            if (nl) lsic_store(d + 1, L, nl, lane);
-            if (lit_fast) {
-                gu8* ld = d + 1u + nl;
-                if (L <= kWave) { if (lane < L) ld[lane] = (uint8_t)lit_b; }
-                else {
-                    const uint32_t bulk = L & ~15u;
-                    if (lane * 16u < bulk) st16(ld + lane * 16u, lit_v);
-                    if (lane < L - bulk) ld[bulk + lane] = (uint8_t)lit_t;
+            if constexpr (!DRY) {
+                gu8* d = s.out + s.pos;
+                if (lane == 0) {
+                    d[0] = (uint8_t)(((L < 15u ? L : 15u) << 4) | (extra < 15u ? extra : 15u));
+                    d[1u + nl + L] = (uint8_t)dup_offset;
+                    d[2u + nl + L] = (uint8_t)(dup_offset >> 8);
                 }
-            } else {
-                wave_copy(d + 1u + nl, in + ls, L, lane);
+                if (nl) lsic_store(d + 1, L, nl, lane);
+                if (lit_fast) {
+                    gu8* ld = d + 1u + nl;
+                    if (L <= kWave) { if (lane < L) ld[lane] = (uint8_t)lit_b; }
+                    else {
+                        const uint32_t bulk = L & ~15u;
+                        if (lane * 16u < bulk) st16(ld + lane * 16u, lit_v);
+                        if (lane < L - bulk) ld[bulk + lane] = (uint8_t)lit_t;
+                    }
+                } else {
+                    wave_copy(d + 1u + nl, in + ls, L, lane);
+                }
+                if (ne) lsic_store(d + 3u + nl + L, extra, ne, lane);
             }
-            if (ne) lsic_store(d + 3u + nl + L, extra, ne, lane);
             s.pos += total;
             CPHASE(3);
         }
@@ -392,7 +399,9 @@ __global__ __launch_bounds__(64) void lzf_compress_wave_kernel(
     }
 }
 
-template __global__ void lzf_compress_wave_kernel<LZF_TABLE_U32>(const lzf_compress_job*, lzf_job_result*, uint32_t, uint32_t, const uint32_t*);
-template __global__ void lzf_compress_wave_kernel<LZF_TABLE_U16>(const lzf_compress_job*, lzf_job_result*, uint32_t, uint32_t, const uint32_t*);
+template __global__ void lzf_compress_wave_kernel<LZF_TABLE_U32, false>(const lzf_compress_job*, lzf_job_result*, uint32_t, uint32_t, const uint32_t*);
+template __global__ void lzf_compress_wave_kernel<LZF_TABLE_U16, false>(const lzf_compress_job*, lzf_job_result*, uint32_t, uint32_t, const uint32_t*);
+template __global__ void lzf_compress_wave_kernel<LZF_TABLE_U32, true>(const lzf_compress_job*, lzf_job_result*, uint32_t, uint32_t, const uint32_t*);
+template __global__ void lzf_compress_wave_kernel<LZF_TABLE_U16, true>(const lzf_compress_job*, lzf_job_result*, uint32_t, uint32_t, const uint32_t*);
 
 }  // namespace lzf

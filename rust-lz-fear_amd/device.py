@@ -40,6 +40,13 @@ def compress_batch(d_jobs, d_res, n, kinds=ffi.KINDS_U32, stream=None):
     ffi.check(ffi.lib().lzf_compress_batch(d_jobs.data_ptr(), d_res.data_ptr(), n, kinds, _stream_ptr(stream)))
 
 
+def compressed_size_batch(d_jobs, d_res, n, kinds=ffi.KINDS_U32, stream=None):
+    """lzf_compressed_size_batch: status and out_len of every compress job without writing its output.  The same job array as
+    compress_batch: `out` is not looked at, out_cap is honoured (UINT64_MAX: the pure size), a writable table is written back —
+    give the call a copy of a table that a later compress_batch is to start from."""
+    ffi.check(ffi.lib().lzf_compressed_size_batch(d_jobs.data_ptr(), d_res.data_ptr(), n, kinds, _stream_ptr(stream)))
+
+
 def decompress_batch(d_jobs, d_res, n, stream=None, max_input_len=None):
     """lzf_decompress_batch; with max_input_len (an upper bound of the jobs' input_len, which the caller of a device-resident
     job array usually knows) lzf_decompress_batch_sized: the segmented pipeline then sizes its scratch for that bound instead
@@ -168,11 +175,12 @@ def frame_decompressed_size(frames, dictionary_len=0, stream=None):
     return status, out_len, consumed
 
 
-def frame_compress_many(settings, frames, outs, dictionary=None, stream=None):
+def frame_compress_many(settings, frames, outs, dictionary=None, stream=None, caps=None):
     """lzf_frame_compress_device_many: every input of `frames` (1-D uint8 CUDA tensors) compressed into an LZ4 frame in `outs`
     (1-D uint8 CUDA tensors, their lengths are the capacities) with `settings` (an ffi.Settings whose `dictionary` is NULL; the
     dictionary is the uint8 CUDA tensor `dictionary`).  Returns (status int32, out_len int64) as CUDA tensors, written in order on
-    `stream`; nothing is synchronised."""
+    `stream`; nothing is synchronised.  `caps` (optional): the capacities the call is told, for outputs allocated with the exact
+    lengths of frame_compressed_size — the call writes nothing outside [0, out_len) — default: the tensors' lengths."""
     n, ptrs, lens = _frame_args(frames)
     assert len(outs) == n
     dev = frames[0].device if n else torch.device("cuda", torch.cuda.current_device())
@@ -183,7 +191,7 @@ def frame_compress_many(settings, frames, outs, dictionary=None, stream=None):
     for t in outs:
         assert t.dtype == torch.uint8 and t.is_cuda and t.dim() == 1 and t.is_contiguous(), "outs: 1-D contiguous uint8 CUDA tensors"
     optr = (C.c_void_p * n)(*[t.data_ptr() for t in outs])
-    caps = (C.c_size_t * n)(*[t.numel() for t in outs])
+    caps = (C.c_size_t * n)(*([t.numel() for t in outs] if caps is None else caps))
     dptr, dlen = None, 0
     if dictionary is not None and dictionary.numel():
         assert dictionary.dtype == torch.uint8 and dictionary.is_cuda and dictionary.is_contiguous()
@@ -376,10 +384,10 @@ def stream_index(streams, dictionary_len=0, stream=None):
     return stream_decompressed_size(streams, dictionary_len=dictionary_len, index=entries, stream=s) + (entries,)
 
 
-def stream_compress(settings, frame_bytes, tensors, outs, dictionary=None, stream=None):
+def stream_compress(settings, frame_bytes, tensors, outs, dictionary=None, stream=None, caps=None):
     """lzf_frame_compress_stream_device: every input of `tensors` written as frames of `frame_bytes` input bytes each, back to
     back, into its tensor of `outs`.  Returns (status int32, out_len int64) as CUDA tensors, written in order on `stream`;
-    nothing is synchronised."""
+    nothing is synchronised.  `caps`: as for frame_compress_many."""
     n, ptrs, lens = _frame_args(tensors)
     assert len(outs) == n
     dev = tensors[0].device if n else torch.device("cuda", torch.cuda.current_device())
@@ -390,7 +398,7 @@ def stream_compress(settings, frame_bytes, tensors, outs, dictionary=None, strea
     for t in outs:
         assert t.dtype == torch.uint8 and t.is_cuda and t.dim() == 1 and t.is_contiguous(), "outs: 1-D contiguous uint8 CUDA tensors"
     optr = (C.c_void_p * n)(*[t.data_ptr() for t in outs])
-    caps = (C.c_size_t * n)(*[t.numel() for t in outs])
+    caps = (C.c_size_t * n)(*([t.numel() for t in outs] if caps is None else caps))
     dptr, dlen = None, 0
     if dictionary is not None and dictionary.numel():
         assert dictionary.dtype == torch.uint8 and dictionary.is_cuda and dictionary.is_contiguous()
@@ -401,3 +409,36 @@ def stream_compress(settings, frame_bytes, tensors, outs, dictionary=None, strea
     ffi.check(ffi.lib().lzf_frame_compress_stream_device(C.byref(settings), int(frame_bytes), n, ptrs, lens, dptr, dlen, optr, caps,
                                                          out_len.data_ptr(), status.data_ptr(), s.cuda_stream))
     return status, out_len
+
+
+# ---- compressed sizes without output (include/lzfear_frame.h) --------------------------------------------------------------
+
+def _size_call(fn, head, tensors, dictionary, stream):
+    n, ptrs, lens = _frame_args(tensors)
+    dev = tensors[0].device if n else torch.device("cuda", torch.cuda.current_device())
+    status = torch.empty(n, dtype=torch.int32, device=dev)         # (empty: the call writes every entry)
+    out_len = torch.empty(n, dtype=torch.int64, device=dev)
+    if n == 0:
+        return status, out_len
+    dptr, dlen = None, 0
+    if dictionary is not None and dictionary.numel():
+        assert dictionary.dtype == torch.uint8 and dictionary.is_cuda and dictionary.is_contiguous()
+        dptr, dlen = dictionary.data_ptr(), dictionary.numel()
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    for t in (status, out_len):
+        t.record_stream(s)
+    ffi.check(fn(*head, n, ptrs, lens, dptr, dlen, out_len.data_ptr(), status.data_ptr(), s.cuda_stream))
+    return status, out_len
+
+
+def frame_compressed_size(settings, frames, dictionary=None, stream=None):
+    """lzf_frame_compressed_size_device: per input of `frames` the (status, out_len) frame_compress_many reports with outputs that
+    hold the bound, found without writing a frame: no output memory, no checksum computed.  Returns (status int32, out_len int64)
+    as CUDA tensors, written in order on `stream`; nothing is synchronised."""
+    return _size_call(ffi.lib().lzf_frame_compressed_size_device, (C.byref(settings),), frames, dictionary, stream)
+
+
+def stream_compressed_size(settings, frame_bytes, tensors, dictionary=None, stream=None):
+    """lzf_frame_compress_stream_size_device: per input the (status, out_len) stream_compress reports with outputs that hold the
+    bound — the sum over its pieces of `frame_bytes` — found without writing anything."""
+    return _size_call(ffi.lib().lzf_frame_compress_stream_size_device, (C.byref(settings), int(frame_bytes)), tensors, dictionary, stream)

@@ -66,7 +66,7 @@ class FrameInfo(C.Structure):
 
 
 EXPORTS = [
-    "lzf_abi_version", "lzf_last_error", "lzf_device_count", "lzf_compress_batch",
+    "lzf_abi_version", "lzf_last_error", "lzf_device_count", "lzf_compress_batch", "lzf_compressed_size_batch", "lzf_compressed_size_batch_host",
     "lzf_decompress_batch", "lzf_decompress_batch_sized", "lzf_decompressed_size_batch", "lzf_decompressed_size_batch_host", "lzf_last_decompress_launch", "lzf_last_compress_launch", "lzf_last_size_launch", "lzf_table_replace_host", "lzf_table_offset_host", "lzf_compress2_host_writer", "lzf_table_seed_from_dictionary", "lzf_table_offset", "lzf_table_offset_batch",
     "lzf_chain_decompress_step",
     "lzf_xxh32_batch", "lzf_copy_ranges", "lzf_compress_batch_host", "lzf_decompress_batch_host", "lzf_xxh32_batch_host",
@@ -80,7 +80,7 @@ FRAME_EXPORTS = [
     "lzf_frame_writer_new", "lzf_frame_writer_write", "lzf_frame_writer_finish", "lzf_frame_writer_sink_error", "lzf_frame_writer_free",
     "lzf_frame_get_stats", "lzf_frame_release_scratch", "lzf_frame_set_host_threads", "lzf_frame_set_memory_budget",
     "lzf_frame_set_pinned_limit", "lzf_frame_decompress_bound_device", "lzf_frame_decompress_device_many",
-    "lzf_frame_compress_device_many", "lzf_frame_decompressed_size_device",
+    "lzf_frame_compress_device_many", "lzf_frame_decompressed_size_device", "lzf_frame_compressed_size_device", "lzf_frame_compress_stream_size_device",
     "lzf_frame_stream_bound_device", "lzf_frame_decompress_stream_device", "lzf_frame_compress_stream_bound", "lzf_frame_compress_stream_device",
     "lzf_frame_stream_count_device", "lzf_frame_stream_decompressed_size_device", "lzf_stream_index_locate",
     "lzf_frame_block_count_device", "lzf_frame_block_index_device", "lzf_block_index_locate", "lzf_frame_decompress_blocks_device",
@@ -146,6 +146,8 @@ def lib():
         L.lzf_last_compress_launch.restype = C.c_char_p
         L.lzf_last_size_launch.restype = C.c_char_p
         L.lzf_compress_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.lzf_compressed_size_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.lzf_compressed_size_batch_host.argtypes = [C.POINTER(CompressJob), C.POINTER(JobResult), C.c_uint32]
         L.lzf_decompress_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.lzf_decompress_batch_sized.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p]
         L.lzf_decompressed_size_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p]
@@ -204,6 +206,10 @@ def lib():
                                                        C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.lzf_frame_compress_device_many.argtypes = [C.POINTER(Settings), C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p,
                                                      C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.lzf_frame_compressed_size_device.argtypes = [C.POINTER(Settings), C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p,
+                                                       C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.lzf_frame_compress_stream_size_device.argtypes = [C.POINTER(Settings), C.c_size_t, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                                            C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
         L.lzf_frame_decompressed_size_device.argtypes = [C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t,
                                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.lzf_frame_stream_bound_device.argtypes = [C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_void_p]
@@ -298,6 +304,33 @@ def compress_blocks_host(items):
         jobs[i].flags = CJOB_TABLE_READONLY if it.get("readonly") else 0
     check(lib().lzf_compress_batch_host(jobs, res, n))
     return [(res[i].status, C.string_at(keep[i][1], res[i].out_len) if res[i].status == OK else b"") for i in range(n)]
+
+
+def compressed_sizes_host(items):
+    """items: as for compress_blocks_host — dict(input=bytes, cursor=int, kind=TABLE_*, table=None|U32Table|U16Table, out_cap=int,
+    readonly=bool); out_cap None is the pure size (UINT64_MAX).  Returns [(status, out_len)]: what compress2 would return and the bytes
+    it would write, found on the device without writing them (lzf_compressed_size_batch_host).  A writable table is updated in place."""
+    n = len(items)
+    if n == 0:
+        return []
+    jobs = (CompressJob * n)()
+    res = (JobResult * n)()
+    keep = []
+    for i, it in enumerate(items):
+        data = bytes(it["input"])
+        keep.append(data)
+        cap = it.get("out_cap")
+        jobs[i].input = _bytes_address(data)
+        jobs[i].input_len = len(data)
+        jobs[i].cursor = it.get("cursor", 0)
+        jobs[i].out = None
+        jobs[i].out_cap = (1 << 64) - 1 if cap is None else cap
+        t = it.get("table")
+        jobs[i].table = C.addressof(t) if t is not None else None
+        jobs[i].table_kind = it.get("kind", TABLE_U32)
+        jobs[i].flags = CJOB_TABLE_READONLY if it.get("readonly") else 0
+    check(lib().lzf_compressed_size_batch_host(jobs, res, n))
+    return [(res[i].status, res[i].out_len) for i in range(n)]
 
 
 def decompress_blocks_host(items):

@@ -176,17 +176,9 @@ class CompressionSettings:
                 raise FrameError(st[f])
         return [C.string_at(outs[f], olen[f]) for f in range(n)]
 
-    def compress_many_device(self, tensors, content_size=None, stream=None):
-        """`compress_many` for inputs that live on the device (1-D uint8 CUDA tensors), compressed on the device into device
-        memory (lzf_frame_compress_device_many); `content_size` goes into every header (compress_with_size_unchecked).
-        Outputs are sized with lzf_frame_compress_bound; the dictionary is uploaded.  Returns one uint8 CUDA tensor per input,
-        the frame's bytes, once `stream` (default: the current stream) has finished the call; raises FrameError like
-        `compress_many`."""
+    def _device_call(self, tensors, content_size):
+        """What the device calls share: the settings without a host dictionary, the dictionary uploaded, the device."""
         import torch
-        from . import device
-        tensors = list(tensors)
-        if not tensors:
-            return []
         dev = tensors[0].device
         s = self._struct(content_size)
         s.dictionary = None                                 # (the device call takes the dictionary in device memory)
@@ -194,50 +186,101 @@ class CompressionSettings:
         d_dict = None
         if self._dictionary:
             d_dict = torch.frombuffer(bytearray(self._dictionary), dtype=torch.uint8).to(dev)
-        L = ffi.lib()
-        outs = [torch.empty(L.lzf_frame_compress_bound(C.byref(s), t.numel()), dtype=torch.uint8, device=dev) for t in tensors]
-        st = stream if stream is not None else torch.cuda.current_stream(dev)
-        if d_dict is not None:
-            st.wait_stream(torch.cuda.current_stream(dev))   # (the upload ran on the current stream)
-        with torch.cuda.stream(st):
-            status, out_len = device.frame_compress_many(s, tensors, outs, dictionary=d_dict, stream=st)
+        return dev, s, d_dict
+
+    @staticmethod
+    def _finish(st, status, out_len):
         st.synchronize()
         codes, lens = status.cpu().tolist(), out_len.cpu().tolist()
         for c in codes:
             if c != 0:
                 raise FrameError(c)
-        return [outs[f][:lens[f]] for f in range(len(tensors))]
+        return lens
 
-    def compress_streams_device(self, tensors, frame_bytes, with_size=False, stream=None):
-        """Every input of `tensors` (1-D uint8 CUDA tensors) written as a stream of back-to-back frames, one frame per
-        `frame_bytes` input bytes (lzf_frame_compress_stream_device): the bytes of `compress_many_device` over the pieces,
-        concatenated, packed on the device.  `with_size`: every frame's header carries its own piece's length.  Returns one
-        uint8 CUDA tensor per input once `stream` (default: the current stream) has finished the call; raises FrameError."""
+    def compressed_sizes_device(self, tensors, content_size=None, stream=None):
+        """The length of every frame `compress_many_device` would return for `tensors`, found on the device without writing a
+        frame (lzf_frame_compressed_size_device): no output memory is taken and no checksum is computed.  Returns a list of ints
+        once `stream` (default: the current stream) has finished the call; raises FrameError like `compress_many_device`."""
         import torch
         from . import device
         tensors = list(tensors)
         if not tensors:
             return []
-        dev = tensors[0].device
-        s = self._struct(0 if with_size else None)
-        s.dictionary = None                                 # (the device call takes the dictionary in device memory)
-        s.dictionary_len = 0
-        d_dict = None
-        if self._dictionary:
-            d_dict = torch.frombuffer(bytearray(self._dictionary), dtype=torch.uint8).to(dev)
-        L = ffi.lib()
-        outs = [torch.empty(L.lzf_frame_compress_stream_bound(C.byref(s), int(frame_bytes), t.numel()), dtype=torch.uint8, device=dev)
-                for t in tensors]
+        dev, s, d_dict = self._device_call(tensors, content_size)
         st = stream if stream is not None else torch.cuda.current_stream(dev)
         if d_dict is not None:
             st.wait_stream(torch.cuda.current_stream(dev))   # (the upload ran on the current stream)
         with torch.cuda.stream(st):
-            status, out_len = device.stream_compress(s, frame_bytes, tensors, outs, dictionary=d_dict, stream=st)
-        st.synchronize()
-        codes, lens = status.cpu().tolist(), out_len.cpu().tolist()
-        for c in codes:
-            if c != 0:
-                raise FrameError(c)
+            status, out_len = device.frame_compressed_size(s, tensors, dictionary=d_dict, stream=st)
+        return self._finish(st, status, out_len)
+
+    def compress_many_device(self, tensors, content_size=None, stream=None, exact=False):
+        """`compress_many` for inputs that live on the device (1-D uint8 CUDA tensors), compressed on the device into device
+        memory (lzf_frame_compress_device_many); `content_size` goes into every header (compress_with_size_unchecked).
+        Outputs are sized with lzf_frame_compress_bound; the dictionary is uploaded.  Returns one uint8 CUDA tensor per input,
+        the frame's bytes, once `stream` (default: the current stream) has finished the call; raises FrameError like
+        `compress_many`.
+        exact=True: the outputs are allocated from the size call (lzf_frame_compressed_size_device) instead of from the bound, and
+        every returned tensor owns exactly its frame's bytes.  (The compress call is still told the bound as the capacity: its
+        contract is that nothing outside [0, out_len) is written, and out_len is what the size call reported.)"""
+        import torch
+        from . import device
+        tensors = list(tensors)
+        if not tensors:
+            return []
+        dev, s, d_dict = self._device_call(tensors, content_size)
+        L = ffi.lib()
+        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        if d_dict is not None:
+            st.wait_stream(torch.cuda.current_stream(dev))   # (the upload ran on the current stream)
+        bounds = [L.lzf_frame_compress_bound(C.byref(s), t.numel()) for t in tensors]
+        caps = None
+        if exact:
+            with torch.cuda.stream(st):
+                status, out_len = device.frame_compressed_size(s, tensors, dictionary=d_dict, stream=st)
+            sizes, caps = self._finish(st, status, out_len), bounds
+            outs = [torch.empty(n, dtype=torch.uint8, device=dev) for n in sizes]
+        else:
+            outs = [torch.empty(b, dtype=torch.uint8, device=dev) for b in bounds]
+        with torch.cuda.stream(st):
+            status, out_len = device.frame_compress_many(s, tensors, outs, dictionary=d_dict, stream=st, caps=caps)
+        lens = self._finish(st, status, out_len)
+        if exact:
+            assert lens == sizes, "the size call and the compress call disagree"
+            return outs
+        return [outs[f][:lens[f]] for f in range(len(tensors))]
+
+    def compress_streams_device(self, tensors, frame_bytes, with_size=False, stream=None, exact=False):
+        """Every input of `tensors` (1-D uint8 CUDA tensors) written as a stream of back-to-back frames, one frame per
+        `frame_bytes` input bytes (lzf_frame_compress_stream_device): the bytes of `compress_many_device` over the pieces,
+        concatenated, packed on the device.  `with_size`: every frame's header carries its own piece's length.  Returns one
+        uint8 CUDA tensor per input once `stream` (default: the current stream) has finished the call; raises FrameError.
+        exact=True: as for `compress_many_device`, with lzf_frame_compress_stream_size_device as the size call."""
+        import torch
+        from . import device
+        tensors = list(tensors)
+        if not tensors:
+            return []
+        dev, s, d_dict = self._device_call(tensors, 0 if with_size else None)
+        L = ffi.lib()
+        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        if d_dict is not None:
+            st.wait_stream(torch.cuda.current_stream(dev))   # (the upload ran on the current stream)
+        bounds = [L.lzf_frame_compress_stream_bound(C.byref(s), int(frame_bytes), t.numel()) for t in tensors]
+        caps = None
+        if exact:
+            with torch.cuda.stream(st):
+                status, out_len = device.stream_compressed_size(s, frame_bytes, tensors, dictionary=d_dict, stream=st)
+            sizes, caps = self._finish(st, status, out_len), bounds
+            outs = [torch.empty(n, dtype=torch.uint8, device=dev) for n in sizes]
+        else:
+            outs = [torch.empty(b, dtype=torch.uint8, device=dev) for b in bounds]
+        with torch.cuda.stream(st):
+            status, out_len = device.stream_compress(s, frame_bytes, tensors, outs, dictionary=d_dict, stream=st, caps=caps)
+        lens = self._finish(st, status, out_len)
+        if exact:
+            assert lens == sizes, "the size call and the compress call disagree"
+            return outs
         return [outs[f][:lens[f]] for f in range(len(tensors))]
 
     def compress_with_size(self, data):          # :147-157
