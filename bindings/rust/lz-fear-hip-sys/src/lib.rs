@@ -117,6 +117,12 @@ extern "C" {
     pub fn lzf_table_offset_batch(d_tables: *const *mut c_void, d_adds: *const u64, n: u32, table_kind: u32, hip_stream: *mut c_void) -> c_int;
     pub fn lzf_chain_decompress_step(d_steps: *const lzf_chain_step, d_state: *mut lzf_chain_state, n_streams: u32,
                                      d_jobs: *mut lzf_decompress_job, d_results: *const lzf_job_result, hip_stream: *mut c_void) -> c_int;
+    // the chain step for streams of any length: jobs trimmed from 1 GiB of history on (one of the two steps per chain)
+    pub fn lzf_chain_decompress_step_trimmed(d_steps: *const lzf_chain_step, d_state: *mut lzf_chain_state, n_streams: u32,
+                                             d_jobs: *mut lzf_decompress_job, d_results: *const lzf_job_result, hip_stream: *mut c_void) -> c_int;
+    // jobs with long existing output restated over its last 64 KiB for the decode / size calls, and their results put back (d_trimmed != d_jobs)
+    pub fn lzf_history_trim_batch(d_jobs: *const lzf_decompress_job, d_trimmed: *mut lzf_decompress_job, d_shift: *mut u64, n_jobs: u32, hip_stream: *mut c_void) -> c_int;
+    pub fn lzf_history_restore_batch(d_results: *mut lzf_job_result, d_shift: *const u64, n_jobs: u32, hip_stream: *mut c_void) -> c_int;
     pub fn lzf_xxh32_batch(d_ptrs: *const *const u8, d_lens: *const u64, d_out: *mut u32, n: u32,
                            hip_stream: *mut c_void) -> c_int;
     pub fn lzf_copy_ranges(d_src: *const *const u8, d_dst: *const *mut u8, d_len: *const u64, n: u32, max_len: u64, hip_stream: *mut c_void) -> c_int;

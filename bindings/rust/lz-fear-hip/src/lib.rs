@@ -102,6 +102,9 @@ pub mod raw {
             output_limit: output_limit as u64,
         };
         let mut res = sys::lzf_job_result::default();
+        // A Vec of any length: from 1 GiB of existing output on (`existing >= 1 << 30`) the host entry point trims the job to the last
+        // 64 KiB of `output` — all an offset can reach —, stages only that, and restores out_len (lzfear_hip.h: lzf_history_trim_batch is
+        // the same rule for jobs in device memory).
         let rc = unsafe { sys::lzf_decompress_batch_host(&job, &mut res, 1) };
         assert_eq!(rc, 0, "lzfear_hip: no device / HIP error");
         output.truncate((res.out_len as usize).min(output.len()).max(existing));

@@ -152,7 +152,11 @@ int lzf_compress_batch(const lzf_compress_job* d_jobs, lzf_job_result* d_results
 int lzf_compressed_size_batch(const lzf_compress_job* d_jobs, lzf_job_result* d_results,
                               uint32_t n_jobs, uint32_t table_kinds, void* hip_stream);
 
-/* Batched raw::decompress_raw — src/raw/decompress.rs:58-138 for every job. */
+/* Batched raw::decompress_raw — src/raw/decompress.rs:58-138 for every job.
+ * Of out[0, out_existing_len) only the last 65 535 bytes are ever read (an offset is a u16, src/raw/decompress.rs:76), and with
+ * that much existing output the prefix is never read at all.  The kernels hold 31-bit positions: a job whose input_len,
+ * prefix_len or out_existing_len is 2 GiB - 256 or more reports LZF_CONTRACT.  For existing output there is a way around that
+ * costs nothing: lzf_history_trim_batch below restates such jobs over the tail of their history. */
 int lzf_decompress_batch(const lzf_decompress_job* d_jobs, lzf_job_result* d_results,
                          uint32_t n_jobs, void* hip_stream);
 /* The same with what the caller knows about the batch: an upper bound of the jobs' input_len (the job array lives in HBM, the
@@ -171,6 +175,7 @@ int lzf_decompress_batch_sized(const lzf_decompress_job* d_jobs, lzf_job_result*
  *            LZF_OK or 1..4, never LZF_OUT_CAPACITY.  The first failing sequence in stream order wins; inside a sequence the
  *            reference's order (UnexpectedEnd, then the limit :72-74, then the offset checks :83-89; literals are not
  *            limit-checked).  LZF_CONTRACT where the decoder refuses the job: input_len, out_existing_len or prefix_len of 2 GiB - 256 or more.
+ *            (That sentence describes jobs as they are handed in, untrimmed: after lzf_history_trim_batch no out_existing_len is that long.)
  *   out_len  on LZF_OK output.len(), out_existing_len included; unspecified on an error.  The decoder stops at 2 GiB of
  *            output; this call does not: a block that decodes to more (LZ4 expands up to 255 x) gets its true 64-bit length.
  *   reserved a diagnostic: kilo-cycles, as for the decoder, for a job the one-wave kernel answered; the number of 2 KiB tiles of the
@@ -190,6 +195,22 @@ int lzf_decompress_batch_sized(const lzf_decompress_job* d_jobs, lzf_job_result*
  * call enqueues its kernels and returns; no host wait. */
 int lzf_decompressed_size_batch(const lzf_decompress_job* d_jobs, lzf_job_result* d_results,
                                 uint32_t n_jobs, uint64_t max_input_len, void* hip_stream);
+/* Jobs with long existing output — a Vec that block after block is appended to, a linked stream — for the two calls above.
+ * decompress_raw compares output.len() with output_limit and with offsets only, and no offset reaches further back than 65 535
+ * bytes, so a job may be restated with its origin `shift` bytes further on without changing a byte or a status:
+ *   out_existing_len < 2^30, or > out_cap:  shift = 0, the job is copied as it is;
+ *   otherwise  shift = (out_existing_len - 65 536) & ~15   (a multiple of 16: out keeps its alignment), and the trimmed job has
+ *              out + shift, out_existing_len - shift, out_cap - shift and output_limit - shift (0 where the limit is below the
+ *              shift: MemoryLimitExceeded at the first match either way); input, prefix and their lengths are copied.
+ * lzf_history_trim_batch writes d_trimmed[i] and d_shift[i] for every job; d_trimmed must not be d_jobs (LZF_E_INVALID).  The
+ * caller then runs lzf_decompress_batch(_sized) or lzf_decompressed_size_batch on d_trimmed, and lzf_history_restore_batch adds
+ * d_shift[i] back to out_len of every result whose status is LZF_OK.  What stays out of contract: inputs and prefixes of
+ * 2 GiB - 256 and more, and one job that itself decodes past 2 GiB - 256 of (trimmed) output.  Asynchronous on `hip_stream`.
+ * The `_host` calls and lzf_chain_decompress_step_trimmed below apply the same rule themselves. */
+int lzf_history_trim_batch(const lzf_decompress_job* d_jobs, lzf_decompress_job* d_trimmed,
+                           uint64_t* d_shift, uint32_t n_jobs, void* hip_stream);
+int lzf_history_restore_batch(lzf_job_result* d_results, const uint64_t* d_shift,
+                              uint32_t n_jobs, void* hip_stream);
 /* Diagnostic: the kernels the calling thread's last lzf_decompress_batch launched (the batch size picks them: the
  * segmented pipeline — one block decoded by many wavefronts — up to four blocks per CU, one workgroup per block beyond). */
 const char* lzf_last_decompress_launch(void);
@@ -234,6 +255,15 @@ typedef struct lzf_chain_step {
 } lzf_chain_step;
 int lzf_chain_decompress_step(const lzf_chain_step* d_steps, lzf_chain_state* d_state, uint32_t n_streams,
                               lzf_decompress_job* d_jobs, const lzf_job_result* d_results, void* hip_stream);
+/* The same step for streams of ANY length, and the one the frame layer uses.  lzf_chain_decompress_step gives every job the whole
+ * stream as history, so a stream ends with LZF_CONTRACT (or LZF_OUT_CAPACITY) once it nears 2 GiB.  This call hands the job out
+ * trimmed from length >= 2^30 on, as lzf_history_trim_batch does it: with shift = (length - 65 536) & ~15 the job's `out` becomes
+ * the stream's out + shift and out_existing_len, out_cap and output_limit count from there; the job's out_len comes back short by
+ * that shift, which the next call of the chain adds again (the shift is a function of the length alone, so nothing is kept for
+ * it).  d_state stays absolute and 64-bit, and so does the place of a stored block.  Below 2^30 the two calls write the same
+ * bytes (`out` of a job untouched).  A chain uses ONE of the two calls from its first step to its last. */
+int lzf_chain_decompress_step_trimmed(const lzf_chain_step* d_steps, lzf_chain_state* d_state, uint32_t n_streams,
+                                      lzf_decompress_job* d_jobs, const lzf_job_result* d_results, void* hip_stream);
 
 /* Batched XXH32 (seed 0) of n device buffers: the per-block checksums of
  * src/framed/compress.rs:259-263 and src/framed/decompress.rs:228-235. */
@@ -249,7 +279,9 @@ int lzf_copy_ranges(const uint8_t* const* d_src, uint8_t* const* d_dst, const ui
 /* ---- host-buffer convenience (synchronous; stages through device scratch) ---------------
  * Same semantics as the batch calls but every pointer in the jobs is a HOST pointer and
  * `results` is a host array.  `table` pointers are host lzf_*_table structs, updated in
- * place.  Used by the frame layer and by callers that have not moved their data to HBM. */
+ * place.  Used by the frame layer and by callers that have not moved their data to HBM.
+ * The two decode-side calls trim long existing output themselves (see lzf_history_trim_batch): any out_existing_len <= out_cap
+ * is accepted, only the last 64 KiB of it are staged, and out_len comes back absolute. */
 int lzf_compress_batch_host(const lzf_compress_job* jobs, lzf_job_result* results, uint32_t n_jobs);
 int lzf_decompress_batch_host(const lzf_decompress_job* jobs, lzf_job_result* results, uint32_t n_jobs);
 /* lzf_decompressed_size_batch over host buffers: `input` of every job is a HOST pointer (staged to the device), `results` a

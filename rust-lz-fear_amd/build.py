@@ -27,7 +27,7 @@ CXX_SOURCES = ["frame.cpp", "host_staging.cpp", "capi_host.cpp"]
 HEADERS = ["kernels.h", "lzf_device.h", "lz4_decompress_batch_phase.inc", "lz4_decompress_parse_phase.inc", "lz4_decompress_feed_phase.inc", "lzf_seg_common.h",
            "analysis/capi_analysis.inc", "capi_internal.h", "capi_order.h", "lzf_dispatch.h",
            "lzf_copy_helpers.h", "lzf_out_ring.h", "lzf_phase_timers.h", "lzf_parse_helpers.h", "lzf_compress_common.h", "lzf_simt.h", "lz4_compress_team.inc",
-           "host_staging.h", "lzf_frame_scan.h", "lzf_stream_walk.h", "lzf_stream_index.h", "lzf_block_index.h", "frame_jobs.h", "lzf_frame_layout.h", "lzf_size_rules.h", "lzf_chain_step.h", "lzf_fed_window.h", "frame_deliver_body.inc",
+           "host_staging.h", "lzf_frame_scan.h", "lzf_stream_walk.h", "lzf_stream_index.h", "lzf_block_index.h", "frame_jobs.h", "lzf_frame_layout.h", "lzf_size_rules.h", "lzf_chain_step.h", "lzf_history_trim.h", "lzf_fed_window.h", "frame_deliver_body.inc",
            os.path.join(ROOT, "include", "lzfear_hip.h"), os.path.join(ROOT, "include", "lzfear_frame.h")]
 
 

@@ -135,7 +135,30 @@ __global__ void lzf_table_offset_batch_kernel(void* const* __restrict__ tables, 
 __global__ __launch_bounds__(256) void lzf_chain_decompress_step_kernel(const lzf_chain_step* __restrict__ steps, lzf_chain_state* __restrict__ state,
                                                                         uint32_t n, lzf_decompress_job* __restrict__ jobs,
                                                                         const lzf_job_result* __restrict__ results) {
-    chain_step<false>(steps, state, n, jobs, results);
+    chain_step<false, false>(steps, state, n, jobs, results);
+}
+// The same step with the history trim (lzfear_hip.h: lzf_chain_decompress_step_trimmed): the frame layer's, for streams of any length.
+__global__ __launch_bounds__(256) void lzf_chain_decompress_step_trimmed_kernel(const lzf_chain_step* __restrict__ steps, lzf_chain_state* __restrict__ state,
+                                                                                uint32_t n, lzf_decompress_job* __restrict__ jobs,
+                                                                                const lzf_job_result* __restrict__ results) {
+    chain_step<false, true>(steps, state, n, jobs, results);
+}
+
+// Jobs with long existing output for the decode and size calls (lzfear_hip.h: lzf_history_trim_batch / lzf_history_restore_batch;
+// the rule is lzf_history_trim.h's).  One thread per job.
+__global__ __launch_bounds__(256) void lzf_history_trim_kernel(const lzf_decompress_job* __restrict__ jobs, lzf_decompress_job* __restrict__ trimmed,
+                                                               uint64_t* __restrict__ shift, uint32_t n) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        uint64_t s;
+        trimmed[i] = lzf_trim::trim(jobs[i], &s);
+        shift[i] = s;
+    }
+}
+__global__ __launch_bounds__(256) void lzf_history_restore_kernel(lzf_job_result* __restrict__ results, const uint64_t* __restrict__ shift, uint32_t n) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t s = shift[i];
+        if (s && results[i].status == LZF_OK) results[i].out_len += s;
+    }
 }
 
 // Copies ranges [src[r], src[r] + len[r]) -> dst[r]: blockIdx.y = range, blockIdx.x = 64 KiB piece of it,

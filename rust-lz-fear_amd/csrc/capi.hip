@@ -386,6 +386,39 @@ int lzf_chain_decompress_step(const lzf_chain_step* d_steps, lzf_chain_state* d_
     return LZF_OK;
 }
 
+int lzf_chain_decompress_step_trimmed(const lzf_chain_step* d_steps, lzf_chain_state* d_state, uint32_t n_streams,
+                                      lzf_decompress_job* d_jobs, const lzf_job_result* d_results, void* hip_stream) {
+    if (n_streams == 0) return LZF_OK;
+    if (!d_steps || !d_state || !d_jobs || !d_results) { g_last_error = "lzf_chain_decompress_step_trimmed: NULL argument"; return LZF_E_INVALID; }
+    int rc = ensure_device();
+    if (rc < 0) return rc;
+    LAUNCH(lzf::lzf_chain_decompress_step_trimmed_kernel, dim3(n_streams), dim3(256), 0, static_cast<hipStream_t>(hip_stream), d_steps, d_state, n_streams, d_jobs, d_results);
+    return LZF_OK;
+}
+
+// Jobs with long existing output, restated over its last 64 KiB for the decode and size calls, and their results put back
+// (lzf_history_trim.h).  One launch each, one thread per job.
+int lzf_history_trim_batch(const lzf_decompress_job* d_jobs, lzf_decompress_job* d_trimmed, uint64_t* d_shift, uint32_t n_jobs, void* hip_stream) {
+    if (n_jobs == 0) return LZF_OK;
+    if (!d_jobs || !d_trimmed || !d_shift) { g_last_error = "lzf_history_trim_batch: NULL argument"; return LZF_E_INVALID; }
+    if (d_trimmed == d_jobs) { g_last_error = "lzf_history_trim_batch: d_trimmed must not be d_jobs"; return LZF_E_INVALID; }
+    int rc = ensure_device();
+    if (rc < 0) return rc;
+    const uint32_t blocks = (n_jobs - 1u) / 256u < 65535u ? (n_jobs - 1u) / 256u + 1u : 65536u;      // (the kernel strides over the rest)
+    LAUNCH(lzf::lzf_history_trim_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(hip_stream), d_jobs, d_trimmed, d_shift, n_jobs);
+    return LZF_OK;
+}
+
+int lzf_history_restore_batch(lzf_job_result* d_results, const uint64_t* d_shift, uint32_t n_jobs, void* hip_stream) {
+    if (n_jobs == 0) return LZF_OK;
+    if (!d_results || !d_shift) { g_last_error = "lzf_history_restore_batch: NULL argument"; return LZF_E_INVALID; }
+    int rc = ensure_device();
+    if (rc < 0) return rc;
+    const uint32_t blocks = (n_jobs - 1u) / 256u < 65535u ? (n_jobs - 1u) / 256u + 1u : 65536u;      // (the kernel strides over the rest)
+    LAUNCH(lzf::lzf_history_restore_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(hip_stream), d_results, d_shift, n_jobs);
+    return LZF_OK;
+}
+
 int lzf_copy_ranges(const uint8_t* const* d_src, uint8_t* const* d_dst, const uint64_t* d_len, uint32_t n, uint64_t max_len, void* hip_stream) {
     if (n == 0 || max_len == 0) return LZF_OK;
     if (!d_src || !d_dst || !d_len) { g_last_error = "lzf_copy_ranges: NULL argument"; return LZF_E_INVALID; }

@@ -5,6 +5,7 @@
 #include <vector>
 #include "capi_internal.h"
 #include "host_staging.h"
+#include "lzf_history_trim.h"
 
 using namespace lzf_capi;
 using lzf_host::Seg; using lzf_host::Staging;
@@ -133,13 +134,21 @@ int lzf_decompress_batch_host(const lzf_decompress_job* jobs, lzf_job_result* re
     if (!jobs || !results) { g_last_error = "lzf_decompress_batch_host: NULL argument"; return LZF_E_INVALID; }
     int rc = ensure_device();
     if (rc < 0) return rc;
+    // Long existing output is trimmed here, where the jobs are host structs (lzf_history_trim.h): of a history of 1 GiB and more only
+    // the last 64 KiB are staged and given room on the device; the results are restored on the way out.
+    std::vector<lzf_decompress_job> trimmed(n_jobs);
+    std::vector<uint64_t> shift(n_jobs);
+    for (uint32_t i = 0; i < n_jobs; ++i) {
+        if (jobs[i].out_existing_len > jobs[i].out_cap) { g_last_error = "out_existing_len > out_cap"; return LZF_E_INVALID; }
+        trimmed[i] = lzf_trim::trim(jobs[i], &shift[i]);
+    }
+    jobs = trimmed.data();
     // one slab going up: [inputs | prefixes | existing output]; the output slab is laid out the same way for the way back
     std::vector<size_t> in_off(n_jobs), pre_off(n_jobs), out_off(n_jobs);
     size_t in_total = 0, out_total = 0;
     uint64_t max_in = 0;
     std::vector<Seg> up, up_out;
     for (uint32_t i = 0; i < n_jobs; ++i) {
-        if (jobs[i].out_existing_len > jobs[i].out_cap) { g_last_error = "out_existing_len > out_cap"; return LZF_E_INVALID; }
         in_off[i] = in_total; in_total = align_up(in_total + jobs[i].input_len, 256);
         if (jobs[i].input_len) up.push_back({in_off[i], const_cast<uint8_t*>(jobs[i].input), (size_t)jobs[i].input_len});
         if (jobs[i].input_len > max_in) max_in = jobs[i].input_len;
@@ -175,6 +184,7 @@ int lzf_decompress_batch_host(const lzf_decompress_job* jobs, lzf_job_result* re
             down.push_back({out_off[i] + (size_t)jobs[i].out_existing_len, jobs[i].out + jobs[i].out_existing_len, (size_t)(n - jobs[i].out_existing_len)});
     }
     HIP_TRY(h.sg.download(down, out_total, h.dout, h.cs));
+    for (uint32_t i = 0; i < n_jobs; ++i) lzf_trim::restore(results[i], shift[i]);
     return LZF_OK;
 }
 
@@ -198,10 +208,18 @@ int lzf_decompressed_size_batch_host(const lzf_decompress_job* jobs, lzf_job_res
     }
     HostCall<lzf_decompress_job> h;
     if ((rc = h.open(n_jobs, in_total ? in_total : 256, 0, false)) != LZF_OK) return rc;
-    std::vector<lzf_decompress_job> dj(jobs, jobs + n_jobs);
-    for (uint32_t i = 0; i < n_jobs; ++i) dj[i].input = h.din + in_off[i];
+    std::vector<lzf_decompress_job> dj(n_jobs);
+    std::vector<uint64_t> shift(n_jobs);
+    for (uint32_t i = 0; i < n_jobs; ++i) {         // (long existing output trimmed as in lzf_decompress_batch_host: any length is answered)
+        lzf_decompress_job j = jobs[i];
+        if (j.out_cap < j.out_existing_len) j.out_cap = j.out_existing_len;      // out_cap is ignored by this call: it must not hold the trim back
+        dj[i] = lzf_trim::trim(j, &shift[i]);
+        dj[i].input = h.din + in_off[i];
+    }
     if ((rc = h.send(up, in_total, dj)) != LZF_OK) return rc;
-    return h.fetch(lzf_decompressed_size_batch(h.djobs, h.dres, n_jobs, max_in, h.cs), results);
+    if ((rc = h.fetch(lzf_decompressed_size_batch(h.djobs, h.dres, n_jobs, max_in, h.cs), results)) != LZF_OK) return rc;
+    for (uint32_t i = 0; i < n_jobs; ++i) lzf_trim::restore(results[i], shift[i]);
+    return LZF_OK;
 }
 
 // ---- EncoderTable on host tables (src/raw/compress/mod.rs:40-61, :64-74, :88-99) --------------------------------------

@@ -20,6 +20,7 @@
 #include "lzf_frame_scan.h"
 #include "frame_jobs.h"
 #include "lzf_frame_layout.h"
+#include "lzf_history_trim.h"
 
 namespace {
 // a HIP failure inside a driver: nothing asynchronous may still read the caller's (or this call's) host arrays when it returns
@@ -816,7 +817,7 @@ int decompress_group(Staging& sg, std::vector<DFrame>& fr, uint32_t f0, uint32_t
         }
         HIPOK(sg.join_copies(cs));
         for (size_t k = 0; k < n_steps; ++k) {
-            if (n_chain) RCOK(lzf_chain_decompress_step(d_steps + k * n_chain, d_state, n_chain, d_jobs, d_res, cs));
+            if (n_chain) RCOK(lzf_chain_decompress_step_trimmed(d_steps + k * n_chain, d_state, n_chain, d_jobs, d_res, cs));
             const size_t a = plan.step_off[k], cnt = plan.step_off[k + 1] - a;
             if (cnt) RCOK(lzf_decompress_batch_sized(d_jobs + a, d_res + a, (uint32_t)cnt, lzf_frame_jobs::step_max_input(plan, k), cs));
         }
@@ -858,7 +859,8 @@ int decompress_group(Staging& sg, std::vector<DFrame>& fr, uint32_t f0, uint32_t
             if (b.compressed) {
                 const lzf_job_result& r = res[J.job[i]];
                 if (r.status != LZF_OK) { st = r.status; break; }                             // CodecError
-                if (F.linked) { n = (size_t)r.out_len - hist; dsrc = dout + J.out_off + hist; }
+                // (linked: the chain step hands a job with 1 GiB and more of history out trimmed, lzf_history_trim.h — its out_len counts from the shift of `hist`)
+                if (F.linked) { n = (size_t)(r.out_len + lzf_trim::shift_of(hist, ~0ull)) - hist; dsrc = dout + J.out_off + hist; }
                 else { n = (size_t)r.out_len; dsrc = dout + J.slot[i]; }
             } else { n = b.len; dsrc = F.linked ? dout + J.out_off + hist : din + F.in_off + (b.data - in[f]); }   // :250 stored
             hist += n;

@@ -205,7 +205,7 @@ __global__ __launch_bounds__(64) void lzf_frame_block_index_kernel(const DFrameD
 __global__ __launch_bounds__(256) void lzf_chain_size_step_kernel(const lzf_chain_step* __restrict__ steps, lzf_chain_state* __restrict__ state,
                                                                   uint32_t n, lzf_decompress_job* __restrict__ jobs,
                                                                   const lzf_job_result* __restrict__ results) {
-    lzf::chain_step<true>(steps, state, n, jobs, results);
+    lzf::chain_step<true, true>(steps, state, n, jobs, results);
 }
 
 // decompress.rs:207-211: FrameChecksumFail where the EndMark was read, nothing stopped the frame and the hash differs
@@ -800,7 +800,7 @@ int decode_frames(const uint32_t n, const uint8_t* const* d_in, const size_t* in
         if (P.n_sums) RC_TRY(lzf_xxh32_batch(meta.img<const uint8_t* const>(P.i_sptr), meta.img<const uint64_t>(P.i_slen), d_sums, P.n_sums, st));
         const lzf_frame_jobs::Plan& pl = P.plan;
         for (size_t k = 0; k < pl.n_steps; ++k) {
-            if (pl.n_chain) RC_TRY(lzf_chain_decompress_step(meta.img<const lzf_chain_step>(P.i_steps) + k * pl.n_chain, meta.scr<lzf_chain_state>(P.s_state),
+            if (pl.n_chain) RC_TRY(lzf_chain_decompress_step_trimmed(meta.img<const lzf_chain_step>(P.i_steps) + k * pl.n_chain, meta.scr<lzf_chain_state>(P.s_state),
                                                              pl.n_chain, d_jobs, d_res, st));
             const size_t a = pl.step_off[k], c = pl.step_off[k + 1] - a;
             if (c) RC_TRY(lzf_decompress_batch_sized(d_jobs + a, d_res + a, (uint32_t)c, lzf_frame_jobs::step_max_input(pl, k), st));

@@ -252,4 +252,9 @@ __global__ void lzf_table_offset_kernel(void* table, uint32_t kind, uint64_t add
 __global__ void lzf_table_offset_batch_kernel(void* const* __restrict__ tables, const uint64_t* __restrict__ adds, uint32_t n, uint32_t kind);
 __global__ void lzf_chain_decompress_step_kernel(const lzf_chain_step* __restrict__ steps, lzf_chain_state* __restrict__ state, uint32_t n,
                                                  lzf_decompress_job* __restrict__ jobs, const lzf_job_result* __restrict__ results);
+__global__ void lzf_chain_decompress_step_trimmed_kernel(const lzf_chain_step* __restrict__ steps, lzf_chain_state* __restrict__ state, uint32_t n,
+                                                         lzf_decompress_job* __restrict__ jobs, const lzf_job_result* __restrict__ results);
+__global__ void lzf_history_trim_kernel(const lzf_decompress_job* __restrict__ jobs, lzf_decompress_job* __restrict__ trimmed,
+                                        uint64_t* __restrict__ shift, uint32_t n);
+__global__ void lzf_history_restore_kernel(lzf_job_result* __restrict__ results, const uint64_t* __restrict__ shift, uint32_t n);
 }  // namespace lzf

@@ -66,6 +66,37 @@ def decompressed_size_batch(d_jobs, d_res, n, stream=None, max_input_len=None):
     ffi.check(ffi.lib().lzf_decompressed_size_batch(d_jobs.data_ptr(), d_res.data_ptr(), n, bound, _stream_ptr(stream)))
 
 
+def history_trim_batch(d_jobs, d_trimmed, d_shift, n, stream=None):
+    """lzf_history_trim_batch: d_trimmed[i] = job i restated over the last 64 KiB of its existing output (jobs with less than 1 GiB of it are
+    copied), d_shift[i] = what lzf_history_restore_batch adds back.  d_trimmed must not be d_jobs; d_shift: n uint64 in device memory."""
+    ffi.check(ffi.lib().lzf_history_trim_batch(d_jobs.data_ptr(), d_trimmed.data_ptr(), d_shift.data_ptr(), n, _stream_ptr(stream)))
+
+
+def history_restore_batch(d_res, d_shift, n, stream=None):
+    ffi.check(ffi.lib().lzf_history_restore_batch(d_res.data_ptr(), d_shift.data_ptr(), n, _stream_ptr(stream)))
+
+
+def _with_long_history(call, d_jobs, d_res, n, stream, max_input_len):
+    d_trimmed = torch.empty(n * DJOB.itemsize, dtype=torch.uint8, device=d_jobs.device)
+    d_shift = torch.empty(n, dtype=torch.int64, device=d_jobs.device)
+    history_trim_batch(d_jobs, d_trimmed, d_shift, n, stream)
+    call(d_trimmed, d_res, n, stream=stream, max_input_len=max_input_len)
+    history_restore_batch(d_res, d_shift, n, stream)
+    return d_trimmed, d_shift
+
+
+def decompress_batch_long_history(d_jobs, d_res, n, stream=None, max_input_len=None):
+    """decompress_batch for jobs whose existing output may be long — tensors that are appended to past 2 GiB: trim, decode, restore, all on
+    `stream`.  out_len comes back absolute.  Returns the two scratch tensors (the trimmed jobs, the shifts): keep them until the stream has
+    run when it is not the current one."""
+    return _with_long_history(decompress_batch, d_jobs, d_res, n, stream, max_input_len)
+
+
+def decompressed_size_batch_long_history(d_jobs, d_res, n, stream=None, max_input_len=None):
+    """decompressed_size_batch the same way: any out_existing_len <= out_cap is answered."""
+    return _with_long_history(decompressed_size_batch, d_jobs, d_res, n, stream, max_input_len)
+
+
 def last_size_launch():
     """lzf_last_size_launch: what this thread's last decompressed_size_batch launched ("latency: ..." = the class of few large blocks)."""
     return ffi.lib().lzf_last_size_launch().decode()

@@ -68,7 +68,7 @@ class FrameInfo(C.Structure):
 EXPORTS = [
     "lzf_abi_version", "lzf_last_error", "lzf_device_count", "lzf_compress_batch", "lzf_compressed_size_batch", "lzf_compressed_size_batch_host",
     "lzf_decompress_batch", "lzf_decompress_batch_sized", "lzf_decompressed_size_batch", "lzf_decompressed_size_batch_host", "lzf_last_decompress_launch", "lzf_last_compress_launch", "lzf_last_size_launch", "lzf_table_replace_host", "lzf_table_offset_host", "lzf_compress2_host_writer", "lzf_table_seed_from_dictionary", "lzf_table_offset", "lzf_table_offset_batch",
-    "lzf_chain_decompress_step",
+    "lzf_chain_decompress_step", "lzf_chain_decompress_step_trimmed", "lzf_history_trim_batch", "lzf_history_restore_batch",
     "lzf_xxh32_batch", "lzf_copy_ranges", "lzf_compress_batch_host", "lzf_decompress_batch_host", "lzf_xxh32_batch_host",
 ]
 FRAME_EXPORTS = [
@@ -173,6 +173,9 @@ def lib():
                                                 C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
         L.lzf_table_offset_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         L.lzf_chain_decompress_step.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.lzf_chain_decompress_step_trimmed.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.lzf_history_trim_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.lzf_history_restore_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.lzf_xxh32.restype = C.c_uint32
         L.lzf_xxh32.argtypes = [C.c_char_p, C.c_size_t, C.c_uint32]
         L.lzf_xxh32_reset.argtypes = [C.POINTER(Xxh32State), C.c_uint32]
@@ -267,6 +270,11 @@ def xxh32_blocks_host(blocks):
     out = (C.c_uint32 * n)()
     check(lib().lzf_xxh32_batch_host(ptrs, lens, out, n))
     return list(out)
+
+
+def buffer_bytes(buf, n):
+    """The first n bytes of a ctypes buffer as bytes, for any n (ctypes.string_at takes its size as a C int: no more than 2 GiB - 1)."""
+    return memoryview(buf).cast("B")[:n].tobytes()
 
 
 def _bytes_address(b):
@@ -367,7 +375,7 @@ def decompress_blocks_host(items):
     out = []
     for i in range(n):
         ln = min(res[i].out_len, jobs[i].out_cap)
-        out.append((res[i].status, C.string_at(keep[i][2], ln)))
+        out.append((res[i].status, buffer_bytes(keep[i][2], ln)))
         keep[i] = None                           # a block's staging buffer goes as soon as its bytes are out (streaming readers: memory = blocks in flight)
     return out
 

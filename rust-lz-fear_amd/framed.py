@@ -312,8 +312,8 @@ def decompress_frame(frame, dictionary=b"", cap=None):
     rc = ffi.lib().lzf_frame_decompress(frame, len(frame), dictionary, len(dictionary), out, cap, C.byref(n), C.byref(used))
     ffi.check(rc)
     if rc != 0:
-        raise FrameError(rc, C.string_at(out, n.value))
-    return C.string_at(out, n.value)
+        raise FrameError(rc, ffi.buffer_bytes(out, n.value))
+    return ffi.buffer_bytes(out, n.value)                 # (any length: a linked-block frame may decode to more than 2 GiB)
 
 
 def decompress_frames(frames, dictionary=b"", caps=None, with_consumed=False):
@@ -337,8 +337,8 @@ def decompress_frames(frames, dictionary=b"", caps=None, with_consumed=False):
     st = (C.c_int * n)()
     ffi.check(ffi.lib().lzf_frame_decompress_many(n, ins, lens, dictionary, len(dictionary), outp, capa, olen, used, st))
     if with_consumed:
-        return [(st[f], C.string_at(outs[f], olen[f]), used[f]) for f in range(n)]
-    return [(st[f], C.string_at(outs[f], olen[f])) for f in range(n)]
+        return [(st[f], ffi.buffer_bytes(outs[f], olen[f]), used[f]) for f in range(n)]
+    return [(st[f], ffi.buffer_bytes(outs[f], olen[f])) for f in range(n)]
 
 
 def decompressed_sizes_device(frames, dictionary_len=0, stream=None):
