@@ -445,17 +445,17 @@ static int compress_many_pass(const lzf_settings* s, uint32_t n_frames, const ui
     const bool per_block_prefix = indep && dict_len > 0;                       // :218,:268 in_buffer = dict ++ block, for every block
     const bool bsum = s->block_checksums != 0, csum = s->content_checksum != 0;
 
-    // ---- layout: input slab, output slab (cap n per block, :242), job list ordered by step
-    struct Fr { size_t nb, in_off, job0, data_off, out0; uint32_t grp; };      // data_off: the frame's own bytes in the slab (not per_block_prefix); out0: its first output slot
+    // ---- the plan (frame_jobs.h): jobs in launch order, every block's output slot as long as the block (:242); the input slab
+    lzf_frame_jobs::CPlan plan;
+    if (!lzf_frame_jobs::compress_plan(n_frames, in_len, status, bs, dict_len, indep, plan)) return LZF_E_INVALID;
+    const size_t n_jobs = plan.jobs.size(), out_total = plan.slots;
+    struct Fr { size_t in_off, data_off, out0; uint32_t grp; };                 // data_off: the frame's own bytes in the slab (not per_block_prefix); out0: its first output slot
     std::vector<Fr> fr(n_frames);
-    size_t in_total = 0, out_total = 0, n_jobs = 0, max_nb = 0, pack_bound = 0;
+    size_t in_total = 0, out0 = 0;
     for (uint32_t f = 0; f < n_frames; ++f) {
-        fr[f].nb = status[f] == LZF_OK ? (in_len[f] + bs - 1) / bs : 0;
-        fr[f].in_off = in_total; fr[f].data_off = in_total + (per_block_prefix ? 0 : dict_len);
-        fr[f].job0 = n_jobs; fr[f].out0 = pack_bound; fr[f].grp = 0;           // (job0: independent mode, where jobs are in frame order)
-        if (fr[f].nb) in_total = up256(in_total + (per_block_prefix ? fr[f].nb * dict_len : dict_len) + in_len[f]);
-        if (fr[f].nb) pack_bound += in_len[f];                                  // every block's output slot is as long as the block (:242)
-        n_jobs += fr[f].nb; if (fr[f].nb > max_nb) max_nb = fr[f].nb;
+        const size_t nb = plan.nb[f];
+        fr[f] = Fr{in_total, in_total + (per_block_prefix ? 0 : dict_len), out0, 0};
+        if (nb) { in_total = up256(in_total + (per_block_prefix ? nb * dict_len : dict_len) + in_len[f]); out0 += in_len[f]; }
     }
     if (n_jobs == 0) {                                                          // only empty inputs: header + EndMark each
         for (uint32_t f = 0; f < n_frames; ++f) if (status[f] == LZF_OK) {
@@ -464,18 +464,14 @@ static int compress_many_pass(const lzf_settings* s, uint32_t n_frames, const ui
         }
         return LZF_OK;
     }
-    if (n_jobs > 0x7FFFFFFFull) return LZF_E_INVALID;
     Staging& sg = Staging::get();
     std::lock_guard<std::mutex> guard(sg.lock());
     TRACE_BEGIN();
     hipStream_t cs = sg.stream(0), hs = sg.stream(3);
     if (!cs || !hs) return fail_hip();
-    if (!sg.pinned(in_total > pack_bound ? in_total : pack_bound)) return fail_hip();
+    if (!sg.pinned(in_total > out_total ? in_total : out_total)) return fail_hip();
     TRACE("c: pinned slab");
     std::vector<lzf_compress_job> jobs(n_jobs);
-    std::vector<uint32_t> job_frame(n_jobs), job_block(n_jobs);
-    std::vector<size_t> job_out_off(n_jobs);
-    std::vector<size_t> step_off;                                               // linked: jobs of step k are [step_off[k], step_off[k+1])
     // ---- sub-groups of whole frames.  A call with enough independent blocks to fill the chip several times over travels in up to
     //      kPipe groups, one behind the other on the same stream: group g compresses while g + 1 is still on its way in and
     //      g - 1 is on its way out.  (Linked streams, and calls too small to keep the chip busy per group, are one group.)
@@ -487,16 +483,16 @@ static int compress_many_pass(const lzf_settings* s, uint32_t n_frames, const ui
     const uint32_t n_groups = indep && n_jobs >= 2u * kFill ? ((n_jobs + kFill - 1) / kFill < kPipe ? (uint32_t)((n_jobs + kFill - 1) / kFill) : kPipe) : 1u;
     std::vector<uint32_t> gend(n_groups, n_frames);                             // group g = frames [gend[g-1], gend[g])
     for (uint32_t g = 0, f = 0; g + 1 < n_groups; ++g) {
-        while (f < n_frames && (fr[f].nb == 0 || fr[f].job0 + fr[f].nb < n_jobs * (size_t)(g + 1) / n_groups)) ++f;
+        while (f < n_frames && (plan.nb[f] == 0 || plan.first[f + 1] < n_jobs * (size_t)(g + 1) / n_groups)) ++f;
         gend[g] = f < n_frames ? ++f : n_frames;
     }
-    // the layout is one address space for inputs [0, in_total) and one for output slots [0, pack_bound); group g's part of each is
+    // the layout is one address space for inputs [0, in_total) and one for output slots [0, out_total); group g's part of each is
     // backed by its own allocation, addressed through a base biased by where the part starts
     std::vector<uintptr_t> din_b(n_groups), dout_b(n_groups);
     for (uint32_t g = 0; g < n_groups; ++g) {
         const uint32_t fa = g ? gend[g - 1] : 0, fb = gend[g];
         const size_t ia = fa < n_frames ? fr[fa].in_off : in_total, ib = fb < n_frames ? fr[fb].in_off : in_total;
-        const size_t oa = fa < n_frames ? fr[fa].out0 : pack_bound, ob = fb < n_frames ? fr[fb].out0 : pack_bound;
+        const size_t oa = fa < n_frames ? fr[fa].out0 : out_total, ob = fb < n_frames ? fr[fb].out0 : out_total;
         void* const di = sg.device(S_IN_G + (int)g, ib - ia);
         void* const dob = sg.device(S_OUT_G + (int)g, ob - oa);
         if (!di || !dob) return fail_hip();
@@ -510,14 +506,9 @@ static int compress_many_pass(const lzf_settings* s, uint32_t n_frames, const ui
 
     lzf_u32_table tmpl;
     if (dict_len >= 8) { RCOK(seeded_template(dict, dict_len, &tmpl)); } else memset(&tmpl, 0, sizeof tmpl);
-    std::vector<void*> h_tabptr(n_jobs, nullptr);
-    std::vector<uint64_t> h_adds(n_jobs, 0);
-    uint32_t n_linked = 0;
-    std::vector<uint32_t> lf_index(n_frames, 0);
     lzf_u32_table* d_tabs = nullptr; void* d_tmpl = nullptr;
     if (!indep) {
-        for (uint32_t f = 0; f < n_frames; ++f) if (fr[f].nb) lf_index[f] = n_linked++;
-        d_tabs = static_cast<lzf_u32_table*>(sg.device(S_TABS, sizeof(lzf_u32_table) * (size_t)(n_linked ? n_linked : 1)));
+        d_tabs = static_cast<lzf_u32_table*>(sg.device(S_TABS, sizeof(lzf_u32_table) * (size_t)(plan.n_linked ? plan.n_linked : 1)));
         if (!d_tabs) return fail_hip();
     } else if (dict_len >= 8) {
         d_tmpl = sg.device(S_TMPL, sizeof tmpl);
@@ -525,54 +516,29 @@ static int compress_many_pass(const lzf_settings* s, uint32_t n_frames, const ui
         HIPOK(hipMemcpyAsync(d_tmpl, &tmpl, sizeof tmpl, hipMemcpyHostToDevice, cs));
     }
 
-    size_t jn = 0;
-    std::vector<std::vector<lzf_frame_jobs::CWindow>> win(n_frames);             // every block's input window (frame_jobs.h)
-    for (uint32_t f = 0; f < n_frames; ++f) if (fr[f].nb) lzf_frame_jobs::compress_windows(in_len[f], bs, dict_len, indep, win[f]);
-    if (indep) {
-        for (uint32_t f = 0; f < n_frames; ++f) {
-            fr[f].job0 = jn; up_first[f] = up.size();
-            size_t w = fr[f].in_off;
-            if (fr[f].nb && !per_block_prefix) seg(w, in[f], in_len[f]);
-            for (size_t i = 0; i < fr[f].nb; ++i, ++jn) {
-                const lzf_frame_jobs::CWindow& W = win[f][i];
-                lzf_compress_job& j = jobs[jn];
-                memset(&j, 0, sizeof j);
-                if (per_block_prefix) {                                         // dict ++ block, a copy of its own
-                    seg(w, dict, dict_len); seg(w + dict_len, in[f] + W.off, W.n);
-                    j.input = din_at(f, w); w += W.hist + W.n;
-                } else j.input = din_at(f, fr[f].in_off + W.lo);
-                j.input_len = W.hist + W.n; j.cursor = W.hist;
-                j.out_cap = W.n; j.table_kind = LZF_TABLE_U32;                 // :242, :202
-                if (dict_len >= 8) { j.table = d_tmpl; j.flags = LZF_CJOB_TABLE_READONLY; }       // :220,:270 template.clone()
-                job_frame[jn] = f; job_block[jn] = (uint32_t)i; job_out_off[jn] = out_total; out_total += W.n;
-            }
-        }
-        step_off = {0, n_jobs};
-    } else {
-        // linked blocks (:271-275): in_buffer = the last <= 64 KiB of (dict ++ data so far) ++ block, a pointer into the
-        // stream's slab (dict ++ data); the table's offset grows by what the window forgets
-        for (uint32_t f = 0; f < n_frames; ++f) if (fr[f].nb) { seg(fr[f].in_off, dict, dict_len); seg(fr[f].in_off + dict_len, in[f], in_len[f]); }
-        for (size_t k = 0; k < max_nb; ++k) {
-            step_off.push_back(jn);
-            for (uint32_t f = 0; f < n_frames; ++f) {
-                if (k >= fr[f].nb) continue;
-                const lzf_frame_jobs::CWindow& W = win[f][k];
-                lzf_compress_job& j = jobs[jn];
-                memset(&j, 0, sizeof j);
-                j.input = din_at(f, fr[f].in_off + W.lo); j.input_len = W.hist + W.n; j.cursor = W.hist;   // :222,:243
-                j.out_cap = W.n; j.table_kind = LZF_TABLE_U32;
-                j.table = d_tabs + lf_index[f];
-                h_tabptr[jn] = j.table; h_adds[jn] = W.add;                     // applied before this step
-                job_frame[jn] = f; job_block[jn] = (uint32_t)k; job_out_off[jn] = out_total; out_total += W.n;
-                ++jn;
-            }
-        }
-        step_off.push_back(jn);
+    // the slab: dict ++ block for every block (independent blocks with a dictionary), or dict ++ data; then every job at S[W.lo]
+    for (uint32_t f = 0; f < n_frames; ++f) {
+        up_first[f] = up.size();
+        if (!plan.nb[f]) continue;
+        size_t w = fr[f].in_off;
+        if (per_block_prefix) for (size_t k = 0; k < plan.nb[f]; ++k) {
+            const lzf_frame_jobs::CWindow& W = plan.of(f, k).W;
+            seg(w, dict, dict_len); seg(w + dict_len, in[f] + W.off, W.n); w += dict_len + W.n;
+        } else { seg(w, dict, dict_len); seg(w + dict_len, in[f], in_len[f]); }
+    }
+    std::vector<void*> h_tabptr(indep ? 0 : n_jobs);
+    std::vector<uint64_t> h_adds(indep ? 0 : n_jobs);
+    for (size_t q = 0; q < n_jobs; ++q) {
+        const lzf_frame_jobs::CJob& r = plan.jobs[q];
+        const uint32_t f = r.frame;
+        void* const table = indep ? d_tmpl : d_tabs + r.table;                  // :220,:270 template.clone(), or the stream's own
+        lzf_frame_jobs::fill_compress_job(jobs[q], r, din_at(f, fr[f].in_off + (per_block_prefix ? r.block * dict_len + r.W.off : r.W.lo)),
+                                          reinterpret_cast<uint8_t*>(dout_b[fr[f].grp] + r.slot), table, indep && d_tmpl);
+        if (!indep) { h_tabptr[q] = table; h_adds[q] = r.W.add; }               // applied before the job's step
     }
     lzf_compress_job* const d_jobs = static_cast<lzf_compress_job*>(sg.device(S_JOBS, sizeof(lzf_compress_job) * n_jobs));
     lzf_job_result* const d_res = static_cast<lzf_job_result*>(sg.device(S_RES, sizeof(lzf_job_result) * n_jobs));
     if (!d_jobs || !d_res) return fail_hip();
-    for (size_t q = 0; q < n_jobs; ++q) jobs[q].out = reinterpret_cast<uint8_t*>(dout_b[fr[job_frame[q]].grp] + job_out_off[q]);
     // results come back through the pinned mailbox: [block results | content hashes | block checksums]
     const size_t mb_res = 0, mb_chash = up256(sizeof(lzf_job_result) * n_jobs), mb_sums = mb_chash + up256(sizeof(uint32_t) * n_frames);
     uint8_t* const mbox = sg.mailbox(mb_sums + sizeof(uint32_t) * n_jobs);
@@ -584,8 +550,8 @@ static int compress_many_pass(const lzf_settings* s, uint32_t n_frames, const ui
     void** d_tabptr = nullptr; uint64_t* d_adds = nullptr;
     std::vector<lzf_u32_table> h_tabs;
     if (!indep) {
-        h_tabs.assign(n_linked, tmpl);                                          // :213-214 table = template.clone()
-        HIPOK(hipMemcpyAsync(d_tabs, h_tabs.data(), sizeof(lzf_u32_table) * n_linked, hipMemcpyHostToDevice, cs));
+        h_tabs.assign(plan.n_linked, tmpl);                                          // :213-214 table = template.clone()
+        HIPOK(hipMemcpyAsync(d_tabs, h_tabs.data(), sizeof(lzf_u32_table) * plan.n_linked, hipMemcpyHostToDevice, cs));
         d_tabptr = static_cast<void**>(sg.device(S_TABPTR, sizeof(void*) * n_jobs));
         d_adds = static_cast<uint64_t*>(sg.device(S_ADDS, sizeof(uint64_t) * n_jobs));
         if (!d_tabptr || !d_adds) return fail_hip();
@@ -605,8 +571,7 @@ static int compress_many_pass(const lzf_settings* s, uint32_t n_frames, const ui
         HIPOK(sg.join_copies(cs));
         TRACE("c:     join");
         if (indep) {
-            size_t a = n_jobs, e = 0;
-            for (uint32_t f = fa; f < fb; ++f) if (fr[f].nb) { if (fr[f].job0 < a) a = fr[f].job0; if (fr[f].job0 + fr[f].nb > e) e = fr[f].job0 + fr[f].nb; }
+            const size_t a = plan.first[fa], e = plan.first[fb];                // (frame order is job order)
             if (e > a) {
                 RCOK(lzf_compress_batch(d_jobs + a, d_res + a, (uint32_t)(e - a), LZF_KINDS_U32 | LZF_KINDS_U32_FRESH_ONLY, cs));
                 TRACE("c:     batch call");
@@ -614,8 +579,8 @@ static int compress_many_pass(const lzf_settings* s, uint32_t n_frames, const ui
                 TRACE("c:     result copy");
             }
         } else {
-            for (size_t k = 0; k + 1 < step_off.size(); ++k) {                 // no host round trip between the steps
-                const size_t a = step_off[k], cnt = step_off[k + 1] - a;
+            for (size_t k = 0; k + 1 < plan.step_off.size(); ++k) {                 // no host round trip between the steps
+                const size_t a = plan.step_off[k], cnt = plan.step_off[k + 1] - a;
                 if (!cnt) continue;
                 if (k > 0) RCOK(lzf_table_offset_batch(d_tabptr + a, d_adds + a, (uint32_t)cnt, LZF_TABLE_U32, cs));
                 RCOK(lzf_compress_batch(d_jobs + a, d_res + a, (uint32_t)cnt, LZF_KINDS_U32, cs));
@@ -632,7 +597,7 @@ static int compress_many_pass(const lzf_settings* s, uint32_t n_frames, const ui
     std::vector<uint32_t> content(n_frames, 0);
     std::vector<uint32_t> dev_hash_frames, host_hash_frames;
     if (csum) for (uint32_t f = 0; f < n_frames; ++f) if (status[f] == LZF_OK) {
-        if (fr[f].nb == 0) content[f] = lzf_xxh32(in[f], 0, 0);
+        if (plan.nb[f] == 0) content[f] = lzf_xxh32(in[f], 0, 0);
         else if (!per_block_prefix && in_len[f] <= kDeviceHashMax) dev_hash_frames.push_back(f);
         else host_hash_frames.push_back(f);
     }
@@ -659,8 +624,10 @@ static int compress_many_pass(const lzf_settings* s, uint32_t n_frames, const ui
     // ---- out, group after group (:244-263, :277-281): header and length words straight into the caller's buffer, every
     //      compressed payload from its output slot through the slab to its place in the frame, stored blocks (:250-255)
     //      from the caller's own input, block checksums over the device copies of both
-    std::vector<std::vector<size_t>> frame_jobs(n_frames);
-    for (size_t q = 0; q < n_jobs; ++q) { auto& v = frame_jobs[job_frame[q]]; if (v.size() <= job_block[q]) v.resize(job_block[q] + 1); v[job_block[q]] = q; }
+    uint8_t hdr[lzf_layout::kMaxHeader];
+    const uint32_t hdr_len = (uint32_t)write_header(s, bd, hdr);
+    std::vector<lzf_layout::Block> blk(plan.max_nb);                            // one frame's blocks and their places (lzf_frame_layout.h)
+    std::vector<uint64_t> pos(plan.max_nb), sum_pos(plan.max_nb);
     struct Patch { uint8_t* at; size_t hash_index; };
     std::vector<Patch> sum_at;                                                  // where block checksum i goes
     struct HostCopy { uint8_t* dst; const uint8_t* src; size_t n; };
@@ -676,28 +643,29 @@ static int compress_many_pass(const lzf_settings* s, uint32_t n_frames, const ui
         const size_t hash0 = n_hashed;
         for (uint32_t f = g ? gend[g - 1] : 0; f < gend[g]; ++f) {
             if (status[f] != LZF_OK) continue;
-            if (fr[f].nb == 0) { status[f] = lzf_frame_assemble(s, 0, nullptr, nullptr, nullptr, content[f], out[f], out_cap[f], &out_len[f]); continue; }   // an empty input: header + EndMark
-            const size_t nb = fr[f].nb;
-            int st = LZF_OK;
-            for (size_t i = 0; i < nb && st == LZF_OK; ++i) { const int bst = res[frame_jobs[f][i]].status; if (bst != LZF_OK && bst != LZF_OUTPUT_FULL) st = bst; }
-            if (st != LZF_OK) { status[f] = st; continue; }
-            size_t w = write_header(s, bd, out[f]);
-            for (size_t i = 0; i < nb; ++i) {
-                const size_t q = frame_jobs[f][i], off = i * bs, n = in_len[f] - off < bs ? in_len[f] - off : bs;
-                const bool stored = res[q].status == LZF_OUTPUT_FULL;                                     // :250-255
-                const uint32_t len = stored ? (uint32_t)n : (uint32_t)res[q].out_len;
-                wr32(out[f] + w, stored ? (len | INCOMPRESSIBLE) : len); w += 4;                           // :247,253
-                if (stored) stored_copies.push_back({out[f] + w, in[f] + off, n});
-                else if (len) down.push_back({job_out_off[q], out[f] + w, len});                          // :258
-                w += len;
+            const uint32_t nb = (uint32_t)plan.nb[f];
+            if (nb == 0) { status[f] = lzf_frame_assemble(s, 0, nullptr, nullptr, nullptr, content[f], out[f], out_cap[f], &out_len[f]); continue; }   // an empty input: header + EndMark
+            const size_t* const job = &plan.job_of[plan.first[f]];
+            for (uint32_t i = 0; i < nb; ++i) blk[i] = lzf_layout::block_of(res[job[i]].status, res[job[i]].out_len, (uint32_t)plan.jobs[job[i]].W.n);   // :244-255
+            uint64_t end_at = 0, content_pos = 0;
+            const uint64_t len = lzf_layout::lay_out(hdr_len, nb, blk.data(), bsum, csum, pos.data(), sum_pos.data(), &end_at, &content_pos, &status[f]);
+            if (status[f] != LZF_OK) continue;
+            memcpy(out[f], hdr, hdr_len);
+            for (uint32_t i = 0; i < nb; ++i) {
+                const size_t q = job[i];
+                const lzf_layout::Block& b = blk[i];
+                uint8_t* const at = out[f] + pos[i];
+                wr32(at, lzf_layout::size_word(b));                                                        // :247,253
+                if (b.stored) stored_copies.push_back({at + 4, in[f] + plan.jobs[q].W.off, b.len});
+                else if (b.len) down.push_back({plan.jobs[q].slot, at + 4, b.len});                        // :258
                 if (bsum) {                                                                                // :259-263
-                    h_ptr.push_back(stored ? jobs[q].input + jobs[q].cursor : jobs[q].out); h_len.push_back(len);
-                    sum_at.push_back({out[f] + w, n_hashed++}); w += 4;
+                    h_ptr.push_back(b.stored ? jobs[q].input + jobs[q].cursor : jobs[q].out); h_len.push_back(b.len);
+                    sum_at.push_back({out[f] + sum_pos[i], n_hashed++});
                 }
             }
-            wr32(out[f] + w, 0); w += 4;                                                                   // :277 EndMark
-            if (csum) { content_at[f] = out[f] + w; w += 4; }                                              // :279-281
-            out_len[f] = w;
+            wr32(out[f] + end_at, 0);                                                                      // :277 EndMark
+            if (csum) content_at[f] = out[f] + content_pos;                                                // :279-281
+            out_len[f] = (size_t)len;
         }
         if (!h_ptr.empty()) {
             Lists& rl = sum_lists[g];

@@ -1,6 +1,7 @@
 // frame_jobs.h — the decode jobs of one pass of frames, shared by lzf_frame_decompress_many (frame.cpp: frames in host
-// memory, uploaded) and lzf_frame_decompress_device_many (frame_device.hip: frames in device memory); at the end the input
-// windows of the compress jobs, shared the same way by lzf_frame_compress_many and lzf_frame_compress_device_many.
+// memory, uploaded) and lzf_frame_decompress_device_many (frame_device_decode.hip: frames in device memory); at the end the
+// compress jobs of one pass (input windows, launch order, output slots, tables), shared the same way by lzf_frame_compress_many
+// and lzf_frame_compress_device_many.
 //
 // Layout of decompress.rs:238-269 on the device: an independent frame's compressed blocks each get an output slot of
 // block_out_bound + input length (the limit plus what the literals may overshoot); a linked frame is one stream
@@ -127,7 +128,7 @@ inline uint64_t step_max_input(const Plan& p, size_t k) {
 }
 
 // ---- the compress side: every block's input window (src/framed/compress.rs:217-275), shared by lzf_frame_compress_many
-//      (frame.cpp) and lzf_frame_compress_device_many (frame_device.hip)
+//      (frame.cpp) and lzf_frame_compress_device_many (frame_device_compress.hip)
 // Block k's payload is data[off, off + n).  Its job compresses S[lo, lo + hist + n) from cursor `hist`, where
 //   linked blocks (:271-275): S = dict ++ data and the history is the last <= 64 KiB of what came before it (block 0: the whole
 //     dictionary); `add` is what the window forgot since the block before: the stream's table.offset(add) is due before it.
@@ -135,8 +136,8 @@ inline uint64_t step_max_input(const Plan& p, size_t k) {
 //   independent blocks with a dictionary (:218,:268): S = dict ++ this block alone, lo = 0, hist = dict_len;
 //   independent blocks without one: S = data, lo = off, hist = 0.
 struct CWindow { size_t off, n, lo, hist; uint64_t add; };
+// appends the windows of one input's blocks to w
 inline void compress_windows(size_t in_len, size_t bs, size_t dict_len, bool indep, std::vector<CWindow>& w) {
-    w.clear();
     const size_t nb = (in_len + bs - 1) / bs;
     size_t lo = 0, len = dict_len;                        // linked: the history is S[lo, lo + len)
     uint64_t pending = 0;
@@ -148,6 +149,68 @@ inline void compress_windows(size_t in_len, size_t bs, size_t dict_len, bool ind
         pending = 0;
         if (len > LZF_WINDOW_SIZE) { const size_t forget = len - LZF_WINDOW_SIZE; pending = forget; lo += forget; len = LZF_WINDOW_SIZE; }
     }
+}
+
+// The compress jobs of one pass of frames, free of addresses: the twin of Plan / build above, for both compress drivers.
+// A frame takes part when the driver's status for it is LZF_OK up front; the others get no job.  Independent blocks go in frame
+// order, one step; linked streams go step-major (block k of every stream that has one in step k: streams run in lock-step, with
+// lzf_table_offset_batch of `W.add` on table `table` before the step).  Every job's output slot is as long as its block (:242),
+// the slots stand one behind the other in job order.
+struct CJob { uint32_t frame, block; CWindow W; size_t slot; uint32_t table; };      // table: linked: the stream's index among the linked streams
+struct CPlan {
+    std::vector<size_t> nb;               // per frame: its blocks, 0 where it takes no part
+    std::vector<CJob> jobs;               // launch order
+    std::vector<size_t> step_off;         // jobs of step k are [step_off[k], step_off[k + 1])
+    std::vector<size_t> first, job_of;    // frame f's block k is job job_of[first[f] + k] (first: n + 1 entries)
+    size_t max_nb = 0, slots = 0;         // slots: the bytes of all output slots
+    uint32_t n_linked = 0;
+    const CJob& of(uint32_t f, size_t k) const { return jobs[job_of[first[f] + k]]; }
+};
+// false: more jobs than a launch takes (nothing is planned)
+inline bool compress_plan(uint32_t n, const size_t* in_len, const int* status0, size_t bs, size_t dict_len, bool indep, CPlan& p) {
+    p = CPlan{};
+    p.nb.assign(n, 0); p.first.assign((size_t)n + 1, 0);
+    std::vector<uint32_t> table(n, 0);
+    size_t total = 0;
+    for (uint32_t f = 0; f < n; ++f) {
+        p.first[f] = total;
+        if (status0[f] != LZF_OK) continue;
+        p.nb[f] = (in_len[f] + bs - 1) / bs; total += p.nb[f];
+        if (p.nb[f] > p.max_nb) p.max_nb = p.nb[f];
+        if (!indep && p.nb[f]) table[f] = p.n_linked++;
+    }
+    p.first[n] = total;
+    if (total > 0x7FFFFFFFull) return false;
+    std::vector<CWindow> win;             // in frame order: frame f's at first[f]
+    win.reserve(total);
+    for (uint32_t f = 0; f < n; ++f) if (p.nb[f]) compress_windows(in_len[f], bs, dict_len, indep, win);
+    p.jobs.reserve(total); p.job_of.resize(total);
+    auto add_job = [&](uint32_t f, size_t k) {
+        const CWindow& W = win[p.first[f] + k];
+        p.job_of[p.first[f] + k] = p.jobs.size();
+        p.jobs.push_back(CJob{f, (uint32_t)k, W, p.slots, table[f]});
+        p.slots += W.n;
+    };
+    if (indep) {
+        for (uint32_t f = 0; f < n; ++f) for (size_t k = 0; k < p.nb[f]; ++k) add_job(f, k);
+        p.step_off = {0, total};
+    } else {
+        for (size_t k = 0; k < p.max_nb; ++k) {
+            p.step_off.push_back(p.jobs.size());
+            for (uint32_t f = 0; f < n; ++f) if (k < p.nb[f]) add_job(f, k);
+        }
+        p.step_off.push_back(total);
+    }
+    return true;
+}
+// The job of record r: `input` = where S[W.lo] stands, `out` = the job's slot, `table` = its stream's table or the call's template
+// (NULL: a fresh one); readonly_template: an independent block's template.clone() (:220,:270).
+inline void fill_compress_job(lzf_compress_job& j, const CJob& r, const uint8_t* input, uint8_t* out, void* table, bool readonly_template) {
+    memset(&j, 0, sizeof j);
+    j.input = input; j.input_len = r.W.hist + r.W.n; j.cursor = r.W.hist;      // :222,:243
+    j.out = out; j.out_cap = r.W.n;                                            // :242
+    j.table = table; j.table_kind = LZF_TABLE_U32;                             // :202
+    if (readonly_template) j.flags = LZF_CJOB_TABLE_READONLY;
 }
 
 // lzf_frame_set_memory_budget's value (0: half of the free device memory), read under the frame layer's lock (frame.cpp)

@@ -8,7 +8,7 @@
 //   check_run     what lzf_frame_decompress_blocks_device asks of a run of entries before it enqueues anything
 //   run_total     the bytes a run decodes to
 //
-// lzf_frame_block_index_kernel (frame_device.hip) is the delivery body in its index mode and runs fill_entry one lane per block;
+// lzf_frame_block_index_kernel (frame_device_index.hip) is the delivery body in its index mode and runs fill_entry one lane per block;
 // the host runs check_run and locate.  The CPU tests compile this header with g++ (tests/emu/emu_block_index.cpp).
 #ifndef LZF_BLOCK_INDEX_H
 #define LZF_BLOCK_INDEX_H

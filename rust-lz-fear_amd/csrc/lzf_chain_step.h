@@ -1,5 +1,5 @@
 // lzf_chain_step.h — the step between two blocks of a linked-block stream (lzfear_hip.h: lzf_chain_decompress_step and
-// lzf_chain_decompress_step_trimmed), shared by the decode (aux_kernels.hip: the two lzf_chain_decompress_step*_kernel) and by the frame layer's size query (frame_device.hip:
+// lzf_chain_decompress_step_trimmed), shared by the decode (aux_kernels.hip: the two lzf_chain_decompress_step*_kernel) and by the frame layer's size query (frame_device_decode.hip:
 // lzf_chain_size_step_kernel).  kCountOnly: the stream's history is carried as a length alone — a stored block adds its
 // length and copies nothing; every length put into the next job is the decode's.
 //

@@ -7,9 +7,10 @@
 //                  refused (LZF_OUTPUT_FULL) is stored raw (:250-255), any other status but LZF_OK fails the frame; block i
 //                  takes 4 + payload + [4] bytes, the EndMark and the optional content checksum follow the last one.
 //
-// lzf_frame_compress_many (frame.cpp) writes frames on the host with these; lzf_frame_compress_device_many (frame_device.hip)
-// runs the same rule in its assembly kernel, one wavefront per frame (a wave-wide exclusive scan of block_span).  The CPU tests
-// compile this header with g++ (tests/emu/emu_frame_layout.cpp) and hold lay_out below to lzf_frame_assemble's bytes.
+// lzf_frame_compress_many (frame.cpp) places frames on the host with block_of and lay_out; lzf_frame_compress_device_many
+// (frame_device_compress.hip) runs the same rule in its assembly kernel, one wavefront per frame (a wave-wide exclusive scan of
+// block_span).  The CPU tests compile this header with g++ (tests/emu/emu_frame_layout.cpp) and hold lay_out below to
+// lzf_frame_assemble's bytes.
 #ifndef LZF_FRAME_LAYOUT_H
 #define LZF_FRAME_LAYOUT_H
 

@@ -3,7 +3,7 @@
 //   read_header   LZ4FrameReader::new, src/framed/decompress.rs:102-161 (header.rs:29-81 for FLG / BD)
 //   walk_blocks   the u32 length hops of decode_block, src/framed/decompress.rs:198-235
 //
-// This is the frame layer's only walk.  The device frame layer (frame_device.hip) runs it in its scan kernels, one lane per
+// This is the frame layer's only walk.  The device frame layer (frame_device_scan.hip) runs it in its scan kernels, one lane per
 // frame; the host driver (frame.cpp) runs it over the caller's bytes: lzf_frame_read_header and lzf_frame_decompress_many through
 // both, the block-by-block reader through a walk_blocks that stops behind its one block.  The CPU tests compile this header with g++
 // (tests/emu/emu_frame_scan.cpp) and hold it to the reference's statuses and `consumed` on the decode corpus.  No

@@ -7,7 +7,7 @@
 //   locate        the frames of an index whose output meets [a, b): two binary searches over the frames' ends (locate_units,
 //                 generic over the entry type: lzf_block_index.h runs it over the blocks of a frame)
 //
-// lzf_stream_index_kernel (frame_device.hip) runs ends_stream and fill_entry one lane per frame; lzf_stream_index_locate is
+// lzf_stream_index_kernel (frame_device_index.hip) runs ends_stream and fill_entry one lane per frame; lzf_stream_index_locate is
 // locate.  The CPU tests compile this header with g++ (tests/emu/emu_stream_index.cpp).
 #ifndef LZF_STREAM_INDEX_H
 #define LZF_STREAM_INDEX_H

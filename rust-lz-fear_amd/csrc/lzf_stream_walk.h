@@ -9,7 +9,7 @@
 // (INPUT_ERROR, consumed = everything); 4 or more trailing bytes that are not the magic — skippable and legacy frames
 // included, the reference knows neither — are a frame that fails with WRONG_MAGIC after 4 bytes.
 // What only the decode finds (a block checksum, a codec error, a block beyond block_maxsize, an empty block, the output
-// capacity, the content checksum) ends the stream earlier: the stream kernels of frame_device.hip apply those stops to the
+// capacity, the content checksum) ends the stream earlier: the stream kernels of frame_device_decode.hip apply those stops to the
 // frames this walk lists.  The stream scan kernel runs walk_frames one lane per stream; the CPU tests compile this header
 // with g++ (tests/emu/emu_stream_walk.cpp).
 #ifndef LZF_STREAM_WALK_H
