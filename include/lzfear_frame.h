@@ -234,6 +234,29 @@ int lzf_frame_decompressed_size_device(uint32_t n_frames, const uint8_t* const* 
                                        size_t dict_len,
                                        uint64_t* d_out_len, uint64_t* d_consumed, int32_t* d_status,
                                        void* hip_stream);
+/* "Does this frame deliver exactly these bytes?" per frame, WITHOUT decoding it: no output memory, no delivery copy.  For callers
+ * who compress on the device and then free the only copy of the input — verify the frame first.  Conventions of
+ * lzf_frame_decompressed_size_device: d_in / in_len / d_expected / expected_len are HOST arrays, d_in[f] and d_expected[f] DEVICE
+ * addresses (d_expected[f] may be NULL where expected_len[f] is 0); d_at, d_consumed (may be NULL), d_status are DEVICE arrays
+ * written in stream order; d_dict / dict_len: the dictionary in device memory, NULL = none.  Per frame, in this order:
+ *   1. st = what lzf_frame_decompressed_size_device reports (block checksums verified, the content checksum not).  If it is not
+ *      LZF_OK: d_status = st, d_at = that call's out_len.
+ *   2. otherwise the delivered content, out_len bytes, is compared with d_expected[f][0, expected_len[f]): a first differing
+ *      position, or lengths that differ, give LZF_MISMATCH with d_at = that position, or the shorter length.
+ *   3. otherwise, where the reader reached the EndMark and the frame carries a content checksum, XXH32 of the EXPECTED bytes (the
+ *      chain the compress call runs over its input, lzf_xxh32_batch: ~1.3 GB/s per frame, many frames at once) is compared with
+ *      the stored word: LZF_F_FRAME_CHECKSUM_FAIL, d_at = out_len.
+ *   4. otherwise LZF_OK, d_at = out_len.
+ * d_consumed[f] is the size query's.  Behind the size query's own work every delivered block becomes one job of
+ * lzf_decompress_verify_batch (include/lzfear_hip.h) — against known plaintext block k's history is the expected bytes in front of
+ * it, so the blocks of a linked frame are verified side by side, in one call with every other frame's, with no lock-step — or,
+ * stored, one compared range; one wavefront per frame takes the first failing block.  The host waits as the size query does and
+ * no more.  Scratch: the size query's, plus 48 + 120 bytes per block and 4 per frame, from the stream-ordered pool; none of it
+ * depends on the decoded sizes.  Only the expected bytes, the frames and the dictionary are read. */
+int lzf_frame_verify_device(uint32_t n_frames, const uint8_t* const* d_in, const size_t* in_len,
+                            const uint8_t* d_dict, size_t dict_len,
+                            const uint8_t* const* d_expected, const size_t* expected_len,
+                            uint64_t* d_at, uint64_t* d_consumed, int32_t* d_status, void* hip_stream);
 /* lzf_frame_compress_many for inputs that live in device memory, compressed into device memory: compress_internal
  * (src/framed/compress.rs:160-282) of every frame with the settings `s` (a host struct, shared by all frames as in
  * lzf_frame_compress_many: flags, dictionary id and content size of the header come from it).  s->dictionary must be NULL

@@ -51,6 +51,7 @@ enum {
      * out_cap >= output_limit + input_len and this never happens */
     LZF_OUT_CAPACITY = 7
 };
+#define LZF_MISMATCH 8   /* verify calls only: the block decodes cleanly, but not to the expected bytes */
 
 /* ---- library-level return codes (negative) ---------------------------------------------- */
 enum {
@@ -195,6 +196,34 @@ int lzf_decompress_batch_sized(const lzf_decompress_job* d_jobs, lzf_job_result*
  * call enqueues its kernels and returns; no host wait. */
 int lzf_decompressed_size_batch(const lzf_decompress_job* d_jobs, lzf_job_result* d_results,
                                 uint32_t n_jobs, uint64_t max_input_len, void* hip_stream);
+/* "Does this block decode to exactly these bytes?" for every job, WITHOUT decoding it: no output memory beyond the expected bytes
+ * the caller already holds, and nothing but d_results is written.  Against a known plaintext no sequence depends on another — a
+ * literal byte must equal the expected byte, a match byte must equal the expected byte `offset` earlier — so the call is the size
+ * call's walk plus compares, parallel inside a block.  Same job struct as the decoder and the size call (size, verify and decode
+ * with one array):
+ *   out[0, out_existing_len)        history, trusted as in the decode;
+ *   out[out_existing_len, out_cap)  the EXPECTED bytes.  `out` is read, never written;
+ *   prefix, output_limit            as in the decode.
+ * The result, in this order of precedence:
+ *   1. the size call's status for the job, if that is not LZF_OK (1..4, or LZF_CONTRACT under the size call's own conditions),
+ *      whatever the bytes: a malformed block is malformed first.  out_len is unspecified.
+ *   2. with n the decoded output.len() and p the first position in [out_existing_len, min(n, out_cap)) whose decoded byte differs
+ *      from out[p]: LZF_MISMATCH if p exists or n != out_cap, with out_len = p if it exists, else min(n, out_cap).
+ *   3. LZF_OK with out_len = n = out_cap.
+ * LZF_OUT_CAPACITY is never reported.  No byte outside input[0, input_len), prefix[0, prefix_len) and out[0, out_cap) is read: a
+ * buffer may end where its allocation ends.  The size call's two classes, picked by the call's size alone (lzf_last_verify_launch says
+ * which ran; results are the same either way): a call of up to 16 jobs per compute unit whose max_input_len is 64 KiB or more takes
+ * the LATENCY CLASS first — the size call's front and tile sums, then one wavefront per 2 KiB tile of input compares the tile's
+ * sequences at their positions, for every job of 64 KiB .. 4 MiB + 32 KiB of input that decodes cleanly — and always last, one
+ * wavefront per job over the whole call, skipping what the class answered.  Those thresholds are the size call's, inherited, not
+ * measured for this call.  max_input_len as for the size call; the class's scratch is the size call's plus 8 bytes per tile and
+ * per job, at most 3 GiB, from the stream-ordered pool, and a pool that refuses it is no error.  `reserved`: the number of tiles
+ * for a job the class answered, kilo-cycles otherwise.
+ * lzf_history_trim_batch / lzf_history_restore_batch work on these jobs unchanged — `out`, with its expected bytes, moves with the
+ * origin, and the restore adds the shift to the position of an LZF_MISMATCH as it does to the length of an LZF_OK.
+ * Asynchronous on `hip_stream`, no host wait. */
+int lzf_decompress_verify_batch(const lzf_decompress_job* d_jobs, lzf_job_result* d_results,
+                                uint32_t n_jobs, uint64_t max_input_len, void* hip_stream);
 /* Jobs with long existing output — a Vec that block after block is appended to, a linked stream — for the two calls above.
  * decompress_raw compares output.len() with output_limit and with offsets only, and no offset reaches further back than 65 535
  * bytes, so a job may be restated with its origin `shift` bytes further on without changing a byte or a status:
@@ -217,6 +246,9 @@ const char* lzf_last_decompress_launch(void);
 /* The same for the calling thread's last lzf_decompressed_size_batch: "latency: ..." when the latency class ran in front of the
  * one-wave kernel, the one-wave kernel's name alone otherwise (larger calls, small inputs, no scratch from the pool). */
 const char* lzf_last_size_launch(void);
+/* The same for the calling thread's last lzf_decompress_verify_batch: "latency: ..." when the latency class ran in front of the
+ * one-wave kernel, the one-wave kernel's name alone otherwise. */
+const char* lzf_last_verify_launch(void);
 /* The same for the calling thread's last lzf_compress_batch: "lzf_compress_team_kernel" (the latency class: no more jobs than
  * compute units, a team of three wavefronts and a CU's LDS per block) or "lzf_compress_compact_kernel" (one wavefront per
  * block, 18 per CU), plus the general kernels that ran beside it for U16 / writable-table jobs. */
@@ -287,6 +319,10 @@ int lzf_decompress_batch_host(const lzf_decompress_job* jobs, lzf_job_result* re
 /* lzf_decompressed_size_batch over host buffers: `input` of every job is a HOST pointer (staged to the device), `results` a
  * host array; prefix, out and out_cap are ignored as above.  Synchronous. */
 int lzf_decompressed_size_batch_host(const lzf_decompress_job* jobs, lzf_job_result* results, uint32_t n_jobs);
+/* lzf_decompress_verify_batch over host buffers: `input`, `prefix` and `out` of every job are HOST pointers; the input, the prefix
+ * and out[0, out_cap) — history and expected bytes; of a history of 1 GiB and more its last 64 KiB — are staged to the device,
+ * `results` is a host array.  out_len comes back absolute, for LZF_MISMATCH as well.  Synchronous. */
+int lzf_decompress_verify_batch_host(const lzf_decompress_job* jobs, lzf_job_result* results, uint32_t n_jobs);
 /* lzf_compressed_size_batch over host buffers: `input` and `table` of every job are HOST pointers (staged to the device; a
  * writable table is updated in place, as lzf_compress_batch_host does), `results` a host array; `out` is ignored, out_cap is
  * honoured as above.  Synchronous. */

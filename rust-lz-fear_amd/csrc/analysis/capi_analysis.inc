@@ -68,6 +68,7 @@ static const KnobRow kKnobRows[] = {
     // the size call's latency class: force = every call that fits its scratch / off = none; its smallest input; LZF_SIZE_FORCE=1 its scratch
     // refused, 2 no one-wave kernel behind it (tests/test_gpu_size_latency.py: what the class finished itself)
     {"LZF_SIZE_SEG", nullptr, nullptr, [](const char* e, d::Knobs& k) { k.size_seg = !strcmp(e, "force") ? d::kForced : !strcmp(e, "off") ? d::kOff : d::kByRule; }},
+    {"LZF_VERIFY_SEG", nullptr, nullptr, [](const char* e, d::Knobs& k) { k.verify_seg = !strcmp(e, "force") ? d::kForced : !strcmp(e, "off") ? d::kOff : d::kByRule; }},
     {"LZF_SIZE_SEG_MIN_IN", &d::Knobs::size_seg_min_in, knob_any, nullptr},
     {"LZF_SIZE_FORCE", &d::Knobs::size_force, knob_in<0, 2>, nullptr},
     {"LZF_FED_VERBOSE", nullptr, nullptr, [](const char*, d::Knobs& k) { k.fed_verbose = true; }},

@@ -157,7 +157,7 @@ __global__ __launch_bounds__(256) void lzf_history_trim_kernel(const lzf_decompr
 __global__ __launch_bounds__(256) void lzf_history_restore_kernel(lzf_job_result* __restrict__ results, const uint64_t* __restrict__ shift, uint32_t n) {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
         const uint64_t s = shift[i];
-        if (s && results[i].status == LZF_OK) results[i].out_len += s;
+        if (s && (results[i].status == LZF_OK || results[i].status == LZF_MISMATCH)) results[i].out_len += s;      // (lzf_trim::restore: a length, or the verify call's position)
     }
 }
 

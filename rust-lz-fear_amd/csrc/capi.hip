@@ -16,6 +16,7 @@ namespace {
 thread_local const char* g_last_decompress = "";      // what the last lzf_decompress_batch of this thread launched (lzf_last_decompress_launch)
 thread_local const char* g_last_compress = "";        // ... and the last lzf_compress_batch
 thread_local const char* g_last_size = "";            // ... and the last lzf_decompressed_size_batch
+thread_local const char* g_last_verify = "";          // ... and the last lzf_decompress_verify_batch
 }
 
 int ensure_device() {
@@ -114,6 +115,8 @@ constexpr auto k_general_u16 = lzf::lzf_compress_wave_kernel<LZF_TABLE_U16>;
 constexpr auto k_general_u32_dry = lzf::lzf_compress_wave_kernel<LZF_TABLE_U32, true>;      // the size call's (lzf_compressed_size_batch)
 constexpr auto k_general_u16_dry = lzf::lzf_compress_wave_kernel<LZF_TABLE_U16, true>;
 constexpr auto k_size = lzf::lzf_decoded_size_kernel<48, 768, false>;
+constexpr auto k_verify = lzf::lzf_verify_kernel<48, 768, false>;
+constexpr auto k_verify_skip = lzf::lzf_verify_kernel<48, 768, true>;    // behind the latency class: skips what that finished
 constexpr auto k_size_skip = lzf::lzf_decoded_size_kernel<48, 768, true>;      // behind the latency class: skips what that finished
 
 // the launch order of a compress or compressed-size call: the cost probe and the order when the plan wants them and the pool has room.
@@ -241,6 +244,7 @@ const char* lzf_last_error(void) { return g_last_error.c_str(); }
 const char* lzf_last_decompress_launch(void) { return g_last_decompress; }
 const char* lzf_last_compress_launch(void) { return g_last_compress; }
 const char* lzf_last_size_launch(void) { return g_last_size; }
+const char* lzf_last_verify_launch(void) { return g_last_verify; }
 int lzf_device_count(void) { return ensure_device(); }
 
 // Launch order (both batch calls): a batch of more jobs than the chip holds at once runs longest job first, or the launch
@@ -338,6 +342,50 @@ int lzf_decompressed_size_batch(const lzf_decompress_job* d_jobs, lzf_job_result
     const uint32_t grid = n_jobs < room ? n_jobs : (uint32_t)room;
     if (done) LAUNCH(k_size_skip, dim3(grid), dim3(64), 0, st, d_jobs, d_results, n_jobs, static_cast<uint32_t*>(ticket.p), (const uint32_t*)perm, done);
     else LAUNCH(k_size, dim3(grid), dim3(64), 0, st, d_jobs, d_results, n_jobs, static_cast<uint32_t*>(ticket.p), (const uint32_t*)perm, (const lzf::seg_job*)nullptr);
+    HIP_TRY(ticket.release());
+    HIP_TRY(seg_mem.release());
+    return LZF_OK;
+}
+
+// Does every job decode to the bytes its `out` holds?  The call executes lzf_dispatch.h's verify_plan, the size call's arrangement:
+//   * few large blocks (the latency class): the size call's front and tile sums, then every tile's base, the compares tile by tile
+//     and the verdicts of the jobs of clean tiles (lz4_verify.hip); a pool that refuses the scratch sends the call down the other way;
+//   * always last: lzf_verify_kernel, one wavefront per job over the whole call, skipping what the class finished; launched as the
+//     size call launches its one-wave kernel (a 4-byte job counter; longest input first beyond one residency, 4 bytes per job).
+// Enqueue only: no host wait.
+int lzf_decompress_verify_batch(const lzf_decompress_job* d_jobs, lzf_job_result* d_results, uint32_t n_jobs, uint64_t max_input_len, void* hip_stream) {
+    if (n_jobs == 0) return LZF_OK;
+    if (!d_jobs || !d_results) { g_last_error = "lzf_decompress_verify_batch: NULL job/result array"; return LZF_E_INVALID; }
+    int rc = ensure_device();
+    if (rc < 0) return rc;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    Device& dv = device();
+    keep_pool_memory(dv);
+    const d::VerifyPlan plan = d::verify_plan(dv.geo, knobs(), n_jobs, max_input_len);
+    AsyncScratch seg_mem(st);
+    const lzf::seg_job* done = nullptr;
+    if (plan.try_seg && (rc = verify_seg_front(dv, d_jobs, d_results, n_jobs, plan, seg_mem, st, &done, max_input_len)) != LZF_OK) return rc;
+    g_last_verify = done ? plan.seg_launch : plan.last_launch;
+    uint32_t resident = 0;             // workgroups of the kernel per CU
+    {
+        std::lock_guard<std::mutex> lk(device_mutex());
+        if (!dv.verify_resident || dv.spare) {
+            int per = 0;
+            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_verify, 64, 0));
+            dv.verify_resident = per > 0 ? (uint32_t)per : 1u;
+        }
+        resident = dv.verify_resident;
+    }
+    const uint64_t room = (uint64_t)resident * dv.geo.cu;
+    const bool ordered = n_jobs > room;
+    AsyncScratch ticket(st);
+    HIP_TRY(hipMallocAsync(&ticket.p, 256 + (ordered ? sizeof(uint32_t) * (size_t)n_jobs : 0u), st));
+    HIP_TRY(hipMemsetAsync(ticket.p, 0, 4, st));
+    uint32_t* const perm = ordered ? static_cast<uint32_t*>(ticket.p) + 64 : nullptr;
+    if (ordered && (rc = launch_order_by_input_len(d_jobs, perm, n_jobs, st)) != LZF_OK) return rc;
+    const uint32_t grid = n_jobs < room ? n_jobs : (uint32_t)room;
+    if (done) LAUNCH(k_verify_skip, dim3(grid), dim3(64), 0, st, d_jobs, d_results, n_jobs, static_cast<uint32_t*>(ticket.p), (const uint32_t*)perm, done);
+    else LAUNCH(k_verify, dim3(grid), dim3(64), 0, st, d_jobs, d_results, n_jobs, static_cast<uint32_t*>(ticket.p), (const uint32_t*)perm, (const lzf::seg_job*)nullptr);
     HIP_TRY(ticket.release());
     HIP_TRY(seg_mem.release());
     return LZF_OK;

@@ -191,6 +191,40 @@ int size_seg_front(Device& dv, const lzf_decompress_job* d_jobs, lzf_job_result*
     return rc;
 }
 
+// ---- the verify call's latency class (lz4_verify.hip) -----------------------------------------------------------------------------
+// The size call's front and tile sums as they are, then the finish kernel that keeps every tile's base, the compares tile by tile
+// and the verdicts of the jobs of clean tiles.  Enqueue only; the scratch stays with the caller until the one-wave kernel behind
+// this has looked at the state array.
+int verify_seg_front(Device& dv, const lzf_decompress_job* d_jobs, lzf_job_result* d_results, uint32_t n, const d::VerifyPlan& plan, AsyncScratch& mem, hipStream_t st,
+                     const lzf::seg_job** done, uint64_t max_in_hint) {
+    *done = nullptr;
+    const d::VerifyLayout l = d::verify_layout(n, max_in_hint);
+    if (!mem.alloc(l.total)) return LZF_OK;                      // (no scratch: the one-wave kernel takes the whole call)
+    lzf::seg_ctx c{};
+    c.jobs = d_jobs; c.results = d_results; c.n_jobs = n;
+    c.max_in = l.s.d.max_in; c.min_in = plan.min_in; c.maxch = l.s.d.maxch; c.maxtile = l.s.d.maxtile;
+    c.st = area<lzf::seg_job>(mem, l.s.o_st);
+    c.xexit = area<uint32_t>(mem, l.s.o_xexit);
+    c.vfrom = area<uint32_t>(mem, l.s.o_vfrom);
+    c.tile_sum = area<lzf::u32x4>(mem, l.s.o_tile_sum);
+    c.bits = area<uint32_t>(mem, l.s.o_bits);
+    c.by_len = plan.by_len ? area<uint32_t>(mem, l.s.o_by_len) : nullptr;
+    c.n_cu = dv.geo.cu; c.g_off = 0u; c.g_n = n; c.size_only = 1u;
+    uint64_t* const tile_base = area<uint64_t>(mem, l.o_tile_base);
+    unsigned long long* const job_min = area<unsigned long long>(mem, l.o_job_min);
+    if (hipMemsetAsync(job_min, 0xFF, 8u * (size_t)n, st) != hipSuccess) { g_last_error = "verify, latency class: memset failed"; return LZF_E_HIP; }
+    int rc = seg_launch_prep(c, st);
+    if (rc == LZF_OK) rc = seg_launch_front(c, 3u, st);           // parse, seam
+    const dim3 tiles(seg_grid(seg_tile_target(c), n, c.maxtile), n);
+    if (rc == LZF_OK) LAUNCH_RC(rc, lzf::lzf_size_tile_kernel, tiles, dim3(64), 0, st, c);
+    if (rc == LZF_OK) LAUNCH_RC(rc, lzf::lzf_verify_finish_kernel, dim3(n), dim3(64), 0, st, c, tile_base);
+    if (rc == LZF_OK) LAUNCH_RC(rc, lzf::lzf_verify_tile_kernel, tiles, dim3(64), 0, st, c, (const uint64_t*)tile_base, job_min);
+    if (rc == LZF_OK) LAUNCH_RC(rc, lzf::lzf_verify_end_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, c, (const unsigned long long*)job_min);
+    if (rc != LZF_OK) g_last_error = "verify, latency class: launch failed";
+    *done = c.st;
+    return rc;
+}
+
 // ---- the bitmap-fed kernel (lz4_decompress_fed.hip): batches beyond the segmented pipeline's ----------------------------------
 // plan + parse of the segmented pipeline over the whole batch (the token bit map of every block: one bit per compressed byte;
 // no seam stage — the fed wavefront carries the true chain and masks or walks what a chunk's parse marked before it fell in step),

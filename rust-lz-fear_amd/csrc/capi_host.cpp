@@ -222,6 +222,48 @@ int lzf_decompressed_size_batch_host(const lzf_decompress_job* jobs, lzf_job_res
     return LZF_OK;
 }
 
+int lzf_decompress_verify_batch_host(const lzf_decompress_job* jobs, lzf_job_result* results, uint32_t n_jobs) {
+    if (n_jobs == 0) return LZF_OK;
+    if (!jobs || !results) { g_last_error = "lzf_decompress_verify_batch_host: NULL argument"; return LZF_E_INVALID; }
+    int rc = ensure_device();
+    if (rc < 0) return rc;
+    // long existing output trimmed as in lzf_decompress_batch_host; one slab going up: [inputs | prefixes | out[0, out_cap): history and expected bytes]
+    std::vector<lzf_decompress_job> dj(n_jobs);
+    std::vector<uint64_t> shift(n_jobs);
+    std::vector<size_t> in_off(n_jobs), pre_off(n_jobs), out_off(n_jobs);
+    size_t in_total = 0;
+    uint64_t max_in = 0;
+    std::vector<Seg> up;
+    for (uint32_t i = 0; i < n_jobs; ++i) {
+        dj[i] = lzf_trim::trim(jobs[i], &shift[i]);
+        if ((dj[i].input_len && !dj[i].input) || (dj[i].prefix_len && !dj[i].prefix) || (dj[i].out_cap && !dj[i].out)) {
+            g_last_error = "lzf_decompress_verify_batch_host: NULL buffer with a length"; return LZF_E_INVALID;
+        }
+        in_off[i] = in_total; in_total = align_up(in_total + dj[i].input_len, 256);
+        if (dj[i].input_len) up.push_back({in_off[i], const_cast<uint8_t*>(dj[i].input), (size_t)dj[i].input_len});
+        if (dj[i].input_len > max_in) max_in = dj[i].input_len;
+    }
+    for (uint32_t i = 0; i < n_jobs; ++i) {
+        pre_off[i] = in_total; in_total = align_up(in_total + dj[i].prefix_len, 256);
+        if (dj[i].prefix_len) up.push_back({pre_off[i], const_cast<uint8_t*>(dj[i].prefix), (size_t)dj[i].prefix_len});
+    }
+    for (uint32_t i = 0; i < n_jobs; ++i) {
+        out_off[i] = in_total; in_total = align_up(in_total + dj[i].out_cap, 256);
+        if (dj[i].out_cap) up.push_back({out_off[i], dj[i].out, (size_t)dj[i].out_cap});
+    }
+    HostCall<lzf_decompress_job> h;
+    if ((rc = h.open(n_jobs, in_total ? in_total : 256, 0, false)) != LZF_OK) return rc;
+    for (uint32_t i = 0; i < n_jobs; ++i) {
+        dj[i].input = h.din + in_off[i];
+        dj[i].prefix = h.din + pre_off[i];
+        dj[i].out = h.din + out_off[i];
+    }
+    if ((rc = h.send(up, in_total, dj)) != LZF_OK) return rc;
+    if ((rc = h.fetch(lzf_decompress_verify_batch(h.djobs, h.dres, n_jobs, max_in, h.cs), results)) != LZF_OK) return rc;
+    for (uint32_t i = 0; i < n_jobs; ++i) lzf_trim::restore(results[i], shift[i]);      // (a mismatch's position comes back absolute as well)
+    return LZF_OK;
+}
+
 // ---- EncoderTable on host tables (src/raw/compress/mod.rs:40-61, :64-74, :88-99) --------------------------------------
 int lzf_table_replace_host(void* table, uint32_t table_kind, const uint8_t* input, uint64_t input_len, uint64_t pos, uint64_t* previous) {
     if (!table || (!input && input_len) || table_kind > LZF_TABLE_U16) { g_last_error = "lzf_table_replace_host: bad argument"; return LZF_E_INVALID; }

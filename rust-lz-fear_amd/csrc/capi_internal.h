@@ -76,6 +76,7 @@ struct Device {
     bool pool_kept = false;          // the default memory pool keeps its memory over synchronisation points
     uint32_t fed_slots = 0, fed_xcc_mask = 0;        // workgroups of the fed kernel resident at once, counted; 0: not counted yet
     uint32_t size_resident = 0;      // workgroups of the size kernel per CU (0: not asked yet)
+    uint32_t verify_resident = 0;    // ... and of the verify kernel
     SegLanes lanes;
     bool spare = false;              // the one record of device numbers beyond the table: nothing is kept in it
 };
@@ -91,5 +92,9 @@ int fed_decompress(Device& dv, const lzf_decompress_job* d_jobs, lzf_job_result*
 // *done = the state array the one-wave kernel skips by, or null: the pool refused the scratch and nothing was launched.
 int size_seg_front(Device& dv, const lzf_decompress_job* d_jobs, lzf_job_result* d_results, uint32_t n, const lzf_dispatch::SizePlan& plan, AsyncScratch& mem, hipStream_t st,
                    const lzf::seg_job** done, uint64_t max_in_hint);
+
+// the same for the verify call's latency class (plan .. the verdicts of the jobs of clean tiles)
+int verify_seg_front(Device& dv, const lzf_decompress_job* d_jobs, lzf_job_result* d_results, uint32_t n, const lzf_dispatch::VerifyPlan& plan, AsyncScratch& mem, hipStream_t st,
+                     const lzf::seg_job** done, uint64_t max_in_hint);
 
 }  // namespace lzf_capi

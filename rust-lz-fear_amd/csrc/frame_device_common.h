@@ -7,6 +7,8 @@
 //                              lzf_frame_decompress_device_many, lzf_frame_decompress_stream_device, lzf_frame_decompressed_size_device
 //   frame_device_index.hip     the stream index, the block index and runs of blocks: lzf_frame_stream_decompressed_size_device,
 //                              lzf_frame_block_index_device, lzf_frame_decompress_blocks_device, the two *_locate calls
+//   frame_device_verify.hip    size_frames, the block index into scratch, a verify job or a stored range per delivered block and
+//                              the fold: lzf_frame_verify_device
 //   frame_device_compress.hip  plan_cpass / compress_frames / compress_streams and the assembly kernels: lzf_frame_compress_device_many,
 //                              lzf_frame_compressed_size_device, lzf_frame_compress_stream_device, lzf_frame_compress_stream_size_device,
 //                              lzf_frame_compress_stream_bound
@@ -207,6 +209,11 @@ int fold_streams(uint32_t n_streams, const uint64_t* first, const int32_t* f_sta
                  const uint64_t* f_full, int32_t* d_status, uint64_t* d_out_len, uint64_t* d_consumed, uint64_t* d_n_frames, hipStream_t st);
 // lzf_stream_empty_kernel's launch, for a call whose streams are all empty: LZF_OK, 0, 0, 0 for every stream
 int empty_streams(uint32_t n_streams, int32_t* d_status, uint64_t* d_out_len, uint64_t* d_consumed, uint64_t* d_n_frames, hipStream_t st);
+
+// ---- frame_device_index.hip
+// lzf_frame_block_index_kernel's launch over the pass size_frames planned (after it has returned): the delivery body in its index
+// mode, frame q of the pass into x_index[frame] (x_cap[frame] entries at most; device arrays of the call's n frames).
+int index_blocks(const Pass& P, const Meta& meta, lzf_frame_block* const* x_index, const uint64_t* x_cap, uint64_t* d_n_listed, hipStream_t st);
 
 }  // namespace lzf_fdev
 

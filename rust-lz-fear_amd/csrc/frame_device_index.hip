@@ -126,6 +126,16 @@ __global__ __launch_bounds__(64) void lzf_block_run_fold_kernel(const RRunDesc* 
 
 }  // namespace
 
+namespace lzf_fdev __attribute__((visibility("hidden"))) {
+
+int index_blocks(const Pass& P, const Meta& meta, lzf_frame_block* const* x_index, const uint64_t* x_cap, uint64_t* d_n_listed, hipStream_t st) {
+    KERNEL(lzf_frame_block_index_kernel, dim3(P.n_frames), dim3(64), 0, st, meta.img<const DFrameDesc>(P.i_frames), meta.img<const DBlkDesc>(P.i_blks),
+           meta.img<const lzf_decompress_job>(P.i_jobs), meta.scr<const lzf_job_result>(P.s_res), meta.scr<const uint32_t>(P.s_sums), x_index, x_cap, d_n_listed);
+    return LZF_OK;
+}
+
+}  // namespace lzf_fdev
+
 using namespace lzf_fdev;
 
 extern "C" {
@@ -219,10 +229,8 @@ int lzf_frame_block_index_device(uint32_t n_frames, const uint8_t* const* d_in, 
     };
     RC_TRY(size_frames(n_frames, d_in, in_len, dict_len, d_out_len, d_consumed, d_status, st, sc, meta, P, more));
     if (P.n_frames && (d_index || d_n_listed))
-        KERNEL(lzf_frame_block_index_kernel, dim3(P.n_frames), dim3(64), 0, st, meta.img<const DFrameDesc>(P.i_frames), meta.img<const DBlkDesc>(P.i_blks),
-               meta.img<const lzf_decompress_job>(P.i_jobs), meta.scr<const lzf_job_result>(P.s_res), meta.scr<const uint32_t>(P.s_sums),
-               d_index ? meta.img<lzf_frame_block* const>(i_index) : (lzf_frame_block* const*)nullptr,
-               d_index ? meta.img<const uint64_t>(i_cap) : (const uint64_t*)nullptr, d_n_listed);
+        RC_TRY(index_blocks(P, meta, d_index ? meta.img<lzf_frame_block* const>(i_index) : (lzf_frame_block* const*)nullptr,
+                            d_index ? meta.img<const uint64_t>(i_cap) : (const uint64_t*)nullptr, d_n_listed, st));
     return meta.wait();                              // the image has left host memory; the kernels run on
 }
 

@@ -46,6 +46,15 @@ __global__ __launch_bounds__(64) void lzf_decoded_size_kernel(const lzf_decompre
                                                               const seg_job* __restrict__ done);
 extern template __global__ void lzf_decoded_size_kernel<48, 768, false>(const lzf_decompress_job*, lzf_job_result*, uint32_t, uint32_t*, const uint32_t*, const seg_job*);
 extern template __global__ void lzf_decoded_size_kernel<48, 768, true>(const lzf_decompress_job*, lzf_job_result*, uint32_t, uint32_t*, const uint32_t*, const seg_job*);
+// lz4_verify.hip: the size kernel's walk with compares behind the checks of every clean round — does the job decode to the bytes
+// out[out_existing_len, out_cap) already holds?  Same launch shape: one wavefront per job, jobs drawn from *ticket in the order of perm.
+// SKIP as for the size kernel: behind the verify call's latency class (lzf_verify_finish_kernel .. below) the jobs it finished are skipped.
+template <int S, int TOKCAP, bool SKIP>
+__global__ __launch_bounds__(64) void lzf_verify_kernel(const lzf_decompress_job* __restrict__ jobs, lzf_job_result* __restrict__ results,
+                                                        uint32_t n_jobs, uint32_t* __restrict__ ticket, const uint32_t* __restrict__ perm,
+                                                        const seg_job* __restrict__ done);
+extern template __global__ void lzf_verify_kernel<48, 768, false>(const lzf_decompress_job*, lzf_job_result*, uint32_t, uint32_t*, const uint32_t*, const seg_job*);
+extern template __global__ void lzf_verify_kernel<48, 768, true>(const lzf_decompress_job*, lzf_job_result*, uint32_t, uint32_t*, const uint32_t*, const seg_job*);
 // done (optional): state array of the segmented pipeline; a job it finished (done[jid].done != 0) is skipped
 template <int RING, int S, int TOKCAP>
 __global__ __launch_bounds__(128) void lzf_decompress_paired_kernel(const lzf_decompress_job* __restrict__ jobs, lzf_job_result* __restrict__ results, uint32_t n_jobs,
@@ -187,6 +196,11 @@ constexpr uint32_t kSegRegion = 256, kSegChunk = 64u * kSegRegion, kSegOverlap =
 constexpr uint32_t kSegChunkWords = kSegChunk / 32u, kSegTile = 2048;
 constexpr uint32_t kSegPrefixReach = 65535;     // existing output of this many bytes or more: no offset reaches the prefix (decompress.rs:76 reads a u16)
 static_assert(kSegChunk == (uint32_t)kFedwChunk && kSegOverlap == (uint32_t)kFedwOverlap && kSegStride == (uint32_t)kFedwStride, "lzf_fed_window.h restates the chunk geometry");
+// the verify call's latency class (lz4_verify.hip), behind plan, parse, seam and lzf_size_tile_kernel: tile bases and clean jobs, the compares of
+// every tile of a clean job (tile_base: [n_jobs][maxtile], job_min: [n_jobs], starting as ~0), the verdicts
+__global__ __launch_bounds__(64) void lzf_verify_finish_kernel(seg_ctx c, uint64_t* __restrict__ tile_base);
+__global__ __launch_bounds__(64) void lzf_verify_tile_kernel(seg_ctx c, const uint64_t* __restrict__ tile_base, unsigned long long* __restrict__ job_min);
+__global__ __launch_bounds__(256) void lzf_verify_end_kernel(seg_ctx c, const unsigned long long* __restrict__ job_min);
 __global__ void lzf_seg_plan_kernel(seg_ctx c);
 // batches of more than one block per CU: which workgroup of the resolve stage takes which job — the jobs ranked by their number of
 // sequences and dealt out in rows of n_cu, every other row reversed, so that the blocks that share a CU (workgroups k, k + n_cu,

@@ -22,22 +22,6 @@
 
 namespace lzf {
 
-namespace {
-// Inclusive wave scan of 64-bit values.  `wide` (wave-uniform) says that some lane's value may not fit the 32-bit scan.
-__device__ __forceinline__ uint64_t wave_scan_add64(uint64_t v, bool wide) {
-    if (!wide) return wave_scan_add((uint32_t)v);
-    // three 24-bit limbs: 64 lanes x 2^24 stays below 2^30 per limb, and the limbs are added up in 64 bits (no carry logic)
-    const uint64_t s0 = wave_scan_add((uint32_t)v & 0xFFFFFFu);
-    const uint64_t s1 = wave_scan_add((uint32_t)(v >> 24) & 0xFFFFFFu);
-    const uint64_t s2 = wave_scan_add((uint32_t)(v >> 48));
-    return s0 + (s1 << 24) + (s2 << 48);
-}
-__device__ __forceinline__ uint64_t readlane64(uint64_t v, uint32_t l) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((uint32_t)v, l), hi = (uint32_t)__builtin_amdgcn_readlane((uint32_t)(v >> 32), l);
-    return (uint64_t)lo | ((uint64_t)hi << 32);       // (readlane returns int: no sign extension into the high half)
-}
-}  // namespace
-
 template <int S, int TOKCAP, bool SKIP>
 __global__ __launch_bounds__(64) void lzf_decoded_size_kernel(const lzf_decompress_job* __restrict__ jobs, lzf_job_result* __restrict__ results,
                                                               uint32_t n_jobs, uint32_t* __restrict__ ticket, const uint32_t* __restrict__ perm,

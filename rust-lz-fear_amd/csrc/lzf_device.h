@@ -101,6 +101,19 @@ __device__ __forceinline__ uint32_t wave_scan_max(uint32_t v) {     // inclusive
     t = LZF_DPP(0, v, 0x142, 0xa); v = t > v ? t : v; t = LZF_DPP(0, v, 0x143, 0xc); v = t > v ? t : v;
     return v;
 }
+// Inclusive wave scan of 64-bit values.  `wide` (wave-uniform) says that some lane's value may not fit the 32-bit scan.
+__device__ __forceinline__ uint64_t wave_scan_add64(uint64_t v, bool wide) {
+    if (!wide) return wave_scan_add((uint32_t)v);
+    // three 24-bit limbs: 64 lanes x 2^24 stays below 2^30 per limb, and the limbs are added up in 64 bits (no carry logic)
+    const uint64_t s0 = wave_scan_add((uint32_t)v & 0xFFFFFFu);
+    const uint64_t s1 = wave_scan_add((uint32_t)(v >> 24) & 0xFFFFFFu);
+    const uint64_t s2 = wave_scan_add((uint32_t)(v >> 48));
+    return s0 + (s1 << 24) + (s2 << 48);
+}
+__device__ __forceinline__ uint64_t readlane64(uint64_t v, uint32_t l) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((uint32_t)v, l), hi = (uint32_t)__builtin_amdgcn_readlane((uint32_t)(v >> 32), l);
+    return (uint64_t)lo | ((uint64_t)hi << 32);       // (readlane returns int: no sign extension into the high half)
+}
 // value of the previous lane (lane 0 gets `first`)
 __device__ __forceinline__ uint32_t wave_prev(uint32_t v, uint32_t first) {
     return (uint32_t)__builtin_amdgcn_update_dpp((int)first, (int)v, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);

@@ -83,6 +83,7 @@ struct Knobs {
     // the size call's latency class
     uint32_t size_seg = kByRule;
     uint32_t size_seg_min_in = kSegMinIn;
+    uint32_t verify_seg = kByRule;                   // the verify call's latency class (its smallest input is size_seg_min_in)
     uint32_t size_force = 0u;                        // 1: its scratch refused, where the pool would refuse it (capi_drivers.hip); 2: no one-wave kernel behind it (tests: what the class finished itself)
     // compress
     uint32_t compress_kernel = kCompressByRule;
@@ -108,6 +109,9 @@ constexpr const char* launch_seg(uint32_t ring) {
 // lzf_last_size_launch: the latency class in front of the one-wave kernel / the one-wave kernel alone
 constexpr const char* kLaunchSizeSeg = "latency: lzf_seg_parse_kernel + lzf_size_tile_kernel + lzf_size_finish_kernel + lzf_decoded_size_kernel<48,768>";
 constexpr const char* kLaunchSizeWave = "lzf_decoded_size_kernel<48,768>";
+// lzf_last_verify_launch: the latency class in front of the one-wave kernel / the one-wave kernel alone
+constexpr const char* kLaunchVerifySeg = "latency: lzf_seg_parse_kernel + lzf_size_tile_kernel + lzf_verify_finish_kernel + lzf_verify_tile_kernel + lzf_verify_kernel<48,768>";
+constexpr const char* kLaunchVerifyWave = "lzf_verify_kernel<48,768>";
 
 // ---- segmented pipeline: batch limit, ring, ranks, groups ----------------------------------------------------------------------------
 constexpr uint32_t seg_blocks_per_cu(const Geometry& g, uint32_t ring) { return per_cu(g, ring + kSegRingSlack); }
@@ -240,6 +244,39 @@ inline SizePlan size_plan(const Geometry& g, const Knobs& k, uint32_t n_jobs, ui
     p.by_len = seg_ranks(g, n_jobs).by_len;
     p.last = k.size_force != 2u;
     p.seg_launch = kLaunchSizeSeg; p.last_launch = kLaunchSizeWave;
+    return p;
+}
+
+// ---- the verify call -----------------------------------------------------------------------------------------------------------------
+// The size call's arrangement: the latency class in front for a call of up to 16 jobs per CU with an input bound of at least 64 KiB,
+// the one-wave kernel last over whatever the class left.  The class needs the size layout plus, for every tile, its base position
+// (8 bytes) and, for every job, its smallest failing position (8 bytes); the same scratch cap.  The job count and the smallest
+// input are size_plan's, measured for the size call and inherited here; profiles/verify.txt has the class against the one-wave
+// kernel alone at 49 and 980 blocks of 4 MiB.
+struct VerifyLayout { SizeLayout s; uint64_t o_tile_base, o_job_min, total; };
+inline VerifyLayout verify_layout(uint32_t n, uint64_t max_in_hint) {
+    VerifyLayout l{}; Carver c;
+    l.s = size_layout(n, max_in_hint);
+    c.off = l.s.total;
+    l.o_tile_base = c.take(8ull * n * l.s.d.maxtile);
+    l.o_job_min = c.take(8ull * n);
+    l.total = c.off;
+    return l;
+}
+struct VerifyPlan {
+    bool try_seg;            // the latency class in front (it may still decline: no scratch from the pool — never an error)
+    uint32_t min_in;
+    bool by_len;             // its chunk / tile stages take the jobs longest input first
+    const char* seg_launch; const char* last_launch;
+};
+inline VerifyPlan verify_plan(const Geometry& g, const Knobs& k, uint32_t n_jobs, uint64_t max_input_len) {
+    VerifyPlan p{};
+    const bool in_class = k.verify_seg == kForced || (k.verify_seg == kByRule && n_jobs <= size_seg_max_jobs(g));
+    p.min_in = k.size_seg_min_in;
+    p.try_seg = in_class && n_jobs <= kSizeMaxJobs && max_input_len >= p.min_in &&
+                verify_layout(n_jobs, max_input_len).total <= kSizeMaxScratch;
+    p.by_len = seg_ranks(g, n_jobs).by_len;
+    p.seg_launch = kLaunchVerifySeg; p.last_launch = kLaunchVerifyWave;
     return p;
 }
 

@@ -54,9 +54,10 @@ LZF_TRIM_HD lzf_decompress_job trim(const lzf_decompress_job& job, uint64_t* shi
     *shift = s;
     return t;
 }
-// A result of the trimmed job as the untrimmed job's (out_len is unspecified on an error and stays what it is).
+// A result of the trimmed job as the untrimmed job's (out_len is unspecified on an error and stays what it is).  The verify call's
+// LZF_MISMATCH (8) carries a position in out_len: it moves back with the origin like a length.
 LZF_TRIM_HD void restore(lzf_job_result& r, uint64_t shift) {
-    if (r.status == LZF_OK) r.out_len += shift;
+    if (r.status == LZF_OK || r.status == 8) r.out_len += shift;
 }
 
 }  // namespace lzf_trim

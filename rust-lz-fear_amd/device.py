@@ -102,6 +102,19 @@ def last_size_launch():
     return ffi.lib().lzf_last_size_launch().decode()
 
 
+def decompress_verify_batch(d_jobs, d_res, n, stream=None, max_input_len=None):
+    """lzf_decompress_verify_batch: does every decode job decode to exactly the bytes out[out_existing_len, out_cap) already holds?
+    The same job array as decompress_batch; `out` is read, never written.  Per job LZF_OK with the length, ffi.MISMATCH with the first
+    differing position (or the shorter length), or the status decompressed_size_batch reports — nothing is decoded."""
+    bound = (1 << 64) - 1 if max_input_len is None else int(max_input_len)
+    ffi.check(ffi.lib().lzf_decompress_verify_batch(d_jobs.data_ptr(), d_res.data_ptr(), n, bound, _stream_ptr(stream)))
+
+
+def last_verify_launch():
+    """lzf_last_verify_launch: what this thread's last decompress_verify_batch launched."""
+    return ffi.lib().lzf_last_verify_launch().decode()
+
+
 def xxh32_batch(d_ptrs, d_lens, d_out, n, stream=None):
     ffi.check(ffi.lib().lzf_xxh32_batch(d_ptrs.data_ptr(), d_lens.data_ptr(), d_out.data_ptr(), n, _stream_ptr(stream)))
 
@@ -204,6 +217,33 @@ def frame_decompressed_size(frames, dictionary_len=0, stream=None):
     ffi.check(ffi.lib().lzf_frame_decompressed_size_device(n, ptrs, lens, int(dictionary_len), out_len.data_ptr(), consumed.data_ptr(),
                                                            status.data_ptr(), s.cuda_stream))
     return status, out_len, consumed
+
+
+def frame_verify(frames, expected, dictionary=None, stream=None):
+    """lzf_frame_verify_device: does every frame (1-D uint8 CUDA tensors) deliver exactly the bytes of `expected` (1-D uint8 CUDA
+    tensors, one per frame)?  Nothing is decoded, no output memory is taken.  Returns (status int32, at int64, consumed int64) as CUDA
+    tensors, written in order on `stream`: LZF_OK with the length; ffi.MISMATCH with the first differing position, or the shorter
+    length; FrameChecksumFail where the bytes are equal and the stored content checksum is not theirs; or the status and length
+    frame_decompressed_size reports."""
+    n, ptrs, lens = _frame_args(frames)
+    assert len(expected) == n
+    dev = frames[0].device if n else torch.device("cuda", torch.cuda.current_device())
+    status = torch.empty(n, dtype=torch.int32, device=dev)         # (empty: the call writes every entry)
+    at = torch.empty(n, dtype=torch.int64, device=dev)
+    consumed = torch.empty(n, dtype=torch.int64, device=dev)
+    if n == 0:
+        return status, at, consumed
+    _, eptrs, elens = _frame_args(expected)
+    dptr, dlen = None, 0
+    if dictionary is not None and dictionary.numel():
+        assert dictionary.dtype == torch.uint8 and dictionary.is_cuda and dictionary.is_contiguous()
+        dptr, dlen = dictionary.data_ptr(), dictionary.numel()
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    for t in (status, at, consumed):
+        t.record_stream(s)
+    ffi.check(ffi.lib().lzf_frame_verify_device(n, ptrs, lens, dptr, dlen, eptrs, elens, at.data_ptr(), consumed.data_ptr(),
+                                                status.data_ptr(), s.cuda_stream))
+    return status, at, consumed
 
 
 def frame_compress_many(settings, frames, outs, dictionary=None, stream=None, caps=None):

@@ -10,6 +10,7 @@ from . import build as _build
 
 OK, UNEXPECTED_END, MEMORY_LIMIT_EXCEEDED, ZERO_DEDUP_OFFSET, INVALID_DEDUP_OFFSET = 0, 1, 2, 3, 4
 OUTPUT_FULL, CONTRACT, OUT_CAPACITY = 5, 6, 7
+MISMATCH = 8                # the verify calls only: decodes cleanly, but not to the expected bytes
 E_NO_DEVICE, E_HIP, E_INVALID = -1, -2, -3
 TABLE_U32, TABLE_U16 = 0, 1
 KINDS_U32, KINDS_U16, KINDS_U32_FRESH_ONLY = 1, 2, 4
@@ -67,7 +68,7 @@ class FrameInfo(C.Structure):
 
 EXPORTS = [
     "lzf_abi_version", "lzf_last_error", "lzf_device_count", "lzf_compress_batch", "lzf_compressed_size_batch", "lzf_compressed_size_batch_host",
-    "lzf_decompress_batch", "lzf_decompress_batch_sized", "lzf_decompressed_size_batch", "lzf_decompressed_size_batch_host", "lzf_last_decompress_launch", "lzf_last_compress_launch", "lzf_last_size_launch", "lzf_table_replace_host", "lzf_table_offset_host", "lzf_compress2_host_writer", "lzf_table_seed_from_dictionary", "lzf_table_offset", "lzf_table_offset_batch",
+    "lzf_decompress_batch", "lzf_decompress_batch_sized", "lzf_decompressed_size_batch", "lzf_decompressed_size_batch_host", "lzf_decompress_verify_batch", "lzf_decompress_verify_batch_host", "lzf_last_verify_launch", "lzf_last_decompress_launch", "lzf_last_compress_launch", "lzf_last_size_launch", "lzf_table_replace_host", "lzf_table_offset_host", "lzf_compress2_host_writer", "lzf_table_seed_from_dictionary", "lzf_table_offset", "lzf_table_offset_batch",
     "lzf_chain_decompress_step", "lzf_chain_decompress_step_trimmed", "lzf_history_trim_batch", "lzf_history_restore_batch",
     "lzf_xxh32_batch", "lzf_copy_ranges", "lzf_compress_batch_host", "lzf_decompress_batch_host", "lzf_xxh32_batch_host",
 ]
@@ -80,7 +81,7 @@ FRAME_EXPORTS = [
     "lzf_frame_writer_new", "lzf_frame_writer_write", "lzf_frame_writer_finish", "lzf_frame_writer_sink_error", "lzf_frame_writer_free",
     "lzf_frame_get_stats", "lzf_frame_release_scratch", "lzf_frame_set_host_threads", "lzf_frame_set_memory_budget",
     "lzf_frame_set_pinned_limit", "lzf_frame_decompress_bound_device", "lzf_frame_decompress_device_many",
-    "lzf_frame_compress_device_many", "lzf_frame_decompressed_size_device", "lzf_frame_compressed_size_device", "lzf_frame_compress_stream_size_device",
+    "lzf_frame_compress_device_many", "lzf_frame_decompressed_size_device", "lzf_frame_verify_device", "lzf_frame_compressed_size_device", "lzf_frame_compress_stream_size_device",
     "lzf_frame_stream_bound_device", "lzf_frame_decompress_stream_device", "lzf_frame_compress_stream_bound", "lzf_frame_compress_stream_device",
     "lzf_frame_stream_count_device", "lzf_frame_stream_decompressed_size_device", "lzf_stream_index_locate",
     "lzf_frame_block_count_device", "lzf_frame_block_index_device", "lzf_block_index_locate", "lzf_frame_decompress_blocks_device",
@@ -213,6 +214,12 @@ def lib():
                                                        C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
         L.lzf_frame_compress_stream_size_device.argtypes = [C.POINTER(Settings), C.c_size_t, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                                                             C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(L, "lzf_decompress_verify_batch"):       # (tools/verify_bench.py loads the parent commit's library, which has no verify calls, for its baseline)
+            L.lzf_last_verify_launch.restype = C.c_char_p
+            L.lzf_decompress_verify_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p]
+            L.lzf_decompress_verify_batch_host.argtypes = [C.POINTER(DecompressJob), C.POINTER(JobResult), C.c_uint32]
+            L.lzf_frame_verify_device.argtypes = [C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t,
+                                                  C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.lzf_frame_decompressed_size_device.argtypes = [C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t,
                                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.lzf_frame_stream_bound_device.argtypes = [C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_void_p]
@@ -399,4 +406,32 @@ def decompressed_sizes_host(items):
         jobs[i].out_existing_len = it.get("existing_len", 0)
         jobs[i].output_limit = (1 << 63) - 1 if limit is None else limit
     check(lib().lzf_decompressed_size_batch_host(jobs, res, n))
+    return [(res[i].status, res[i].out_len) for i in range(n)]
+
+
+def verify_blocks_host(items):
+    """items: list of dict(input=bytes, prefix=bytes, existing=bytes, expected=bytes, limit=int).  Returns [(status, out_len)]:
+    does the block decode, behind `existing`, to exactly `expected`?  LZF_OK with the length, MISMATCH with the first differing
+    position (or the shorter length), or the size call's status — found on the device without decoding
+    (lzf_decompress_verify_batch_host)."""
+    n = len(items)
+    if n == 0:
+        return []
+    jobs = (DecompressJob * n)()
+    res = (JobResult * n)()
+    keep = []
+    for i, it in enumerate(items):
+        data, prefix = bytes(it["input"]), bytes(it.get("prefix", b""))
+        out = bytes(it.get("existing", b"")) + bytes(it.get("expected", b""))
+        keep.append((data, prefix, out))
+        limit = it.get("limit")
+        jobs[i].input = _bytes_address(data)
+        jobs[i].input_len = len(data)
+        jobs[i].prefix = _bytes_address(prefix)
+        jobs[i].prefix_len = len(prefix)
+        jobs[i].out = _bytes_address(out)
+        jobs[i].out_existing_len = len(it.get("existing", b""))
+        jobs[i].out_cap = len(out)
+        jobs[i].output_limit = (1 << 63) - 1 if limit is None else limit
+    check(lib().lzf_decompress_verify_batch_host(jobs, res, n))
     return [(res[i].status, res[i].out_len) for i in range(n)]

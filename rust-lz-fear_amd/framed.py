@@ -12,7 +12,7 @@ WINDOW_SIZE = 64 * 1024     # src/framed/mod.rs:20
 
 FRAME_ERRORS = {
     1: "CodecError(UnexpectedEnd)", 2: "CodecError(MemoryLimitExceeded)", 3: "CodecError(ZeroDeduplicationOffset)",
-    4: "CodecError(InvalidDeduplicationOffset)", 7: "OutCapacity",
+    4: "CodecError(InvalidDeduplicationOffset)", 7: "OutCapacity", 8: "Mismatch",
     16: "InputError", 17: "WrongMagic", 18: "HeaderChecksumFail", 19: "BlockChecksumFail", 20: "FrameChecksumFail",
     21: "BlockLengthOverflow", 22: "BlockSizeOverflow", 23: "UnimplementedBlocksize", 24: "UnsupportedVersion",
     25: "ReservedFlagBitsSet", 26: "ReservedBdBitsSet", 27: "InvalidBlockSize", 28: "Panic",
@@ -214,7 +214,7 @@ class CompressionSettings:
             status, out_len = device.frame_compressed_size(s, tensors, dictionary=d_dict, stream=st)
         return self._finish(st, status, out_len)
 
-    def compress_many_device(self, tensors, content_size=None, stream=None, exact=False):
+    def compress_many_device(self, tensors, content_size=None, stream=None, exact=False, verify=False):
         """`compress_many` for inputs that live on the device (1-D uint8 CUDA tensors), compressed on the device into device
         memory (lzf_frame_compress_device_many); `content_size` goes into every header (compress_with_size_unchecked).
         Outputs are sized with lzf_frame_compress_bound; the dictionary is uploaded.  Returns one uint8 CUDA tensor per input,
@@ -222,7 +222,9 @@ class CompressionSettings:
         `compress_many`.
         exact=True: the outputs are allocated from the size call (lzf_frame_compressed_size_device) instead of from the bound, and
         every returned tensor owns exactly its frame's bytes.  (The compress call is still told the bound as the capacity: its
-        contract is that nothing outside [0, out_len) is written, and out_len is what the size call reported.)"""
+        contract is that nothing outside [0, out_len) is written, and out_len is what the size call reported.)
+        verify=True: before the call returns the written frames are verified against the input tensors (lzf_frame_verify_device:
+        no decode, no output memory) — for callers who free the input next.  The first frame that is not LZF_OK raises FrameError."""
         import torch
         from . import device
         tensors = list(tensors)
@@ -247,8 +249,12 @@ class CompressionSettings:
         lens = self._finish(st, status, out_len)
         if exact:
             assert lens == sizes, "the size call and the compress call disagree"
-            return outs
-        return [outs[f][:lens[f]] for f in range(len(tensors))]
+        frames = outs if exact else [outs[f][:lens[f]] for f in range(len(tensors))]
+        if verify:
+            for code, _ in verify_frames_device(frames, tensors, dictionary=d_dict, stream=st):
+                if code != 0:
+                    raise FrameError(code)
+        return frames
 
     def compress_streams_device(self, tensors, frame_bytes, with_size=False, stream=None, exact=False):
         """Every input of `tensors` (1-D uint8 CUDA tensors) written as a stream of back-to-back frames, one frame per
@@ -356,6 +362,28 @@ def decompressed_sizes_device(frames, dictionary_len=0, stream=None):
         status, out_len, consumed = device.frame_decompressed_size(frames, dictionary_len=dictionary_len, stream=s)
     s.synchronize()
     return list(zip(status.cpu().tolist(), out_len.cpu().tolist(), consumed.cpu().tolist()))
+
+
+def verify_frames_device(frames, expected, dictionary=None, stream=None):
+    """Per frame (1-D uint8 CUDA tensors): does it deliver exactly the bytes of `expected[f]` (1-D uint8 CUDA tensors)?  Without
+    decoding and without output memory (lzf_frame_verify_device): [(status, at)] once `stream` has finished the call — (0, length);
+    (ffi.MISMATCH, the first differing position or the shorter length); (FrameChecksumFail, length) where the bytes are equal but the
+    frame's content checksum is not theirs; or what `decompressed_sizes_device` reports for a frame that does not decode.
+    `dictionary`: bytes or a uint8 CUDA tensor."""
+    import torch
+    from . import device
+    frames, expected = list(frames), list(expected)
+    if not frames:
+        return []
+    dev = frames[0].device
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    if dictionary is not None and not isinstance(dictionary, torch.Tensor):
+        dictionary = torch.frombuffer(bytearray(bytes(dictionary)), dtype=torch.uint8).to(dev) if len(dictionary) else None
+        s.wait_stream(torch.cuda.current_stream(dev))   # (the upload ran on the current stream)
+    with torch.cuda.stream(s):
+        status, at, _ = device.frame_verify(frames, expected, dictionary=dictionary, stream=s)
+    s.synchronize()
+    return list(zip(status.cpu().tolist(), at.cpu().tolist()))
 
 
 def decompress_frames_device(frames, dictionary=None, caps=None, stream=None, exact=False):
