@@ -131,6 +131,10 @@ extern "C" {
     // decompress_raw's status and output.len() per job without decoding (prefix, out and out_cap of the jobs are never dereferenced)
     pub fn lzf_decompressed_size_batch(d_jobs: *const lzf_decompress_job, d_results: *mut lzf_job_result, n_jobs: u32, max_input_len: u64, hip_stream: *mut c_void) -> c_int;
     pub fn lzf_decompressed_size_batch_host(jobs: *const lzf_decompress_job, results: *mut lzf_job_result, n_jobs: u32) -> c_int;
+    // the head of every job's block: decoding stops where the output is out_cap bytes long (out_cap is the target, out_existing_len
+    // included); out_len = min(decoded length, out_cap); what starts at or behind the target is not looked at
+    pub fn lzf_decompress_head_batch(d_jobs: *const lzf_decompress_job, d_results: *mut lzf_job_result, n_jobs: u32, hip_stream: *mut c_void) -> c_int;
+    pub fn lzf_decompress_head_batch_host(jobs: *const lzf_decompress_job, results: *mut lzf_job_result, n_jobs: u32) -> c_int;
     // compressed sizes without output: compress2's status and the bytes it would write per job, nothing written (`out` is never
     // dereferenced, out_cap is honoured, a writable table is written back: size a copy of a table that is to be compressed from later)
     pub fn lzf_compressed_size_batch(d_jobs: *const lzf_compress_job, d_results: *mut lzf_job_result, n_jobs: u32,

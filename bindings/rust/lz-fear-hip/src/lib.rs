@@ -117,4 +117,35 @@ pub mod raw {
             _ => panic!("lzfear_hip: contract / capacity"),
         }
     }
+
+    /// The first `nbytes` decoded bytes of a block, appended to `output` (which is also history, as for `decompress_raw`):
+    /// liblz4's `LZ4_decompress_safe_partial`.  Decoding stops at the sequence that reaches `output.len() + nbytes`; fewer
+    /// bytes are appended where the block ends first.  A `DecodeError` is one of a sequence that STARTS in front of that
+    /// length: what lies at or behind it is never looked at, malformed or not (include/lzfear_hip.h:
+    /// lzf_decompress_head_batch).  Returns the number of bytes appended.
+    pub fn decompress_raw_head(input: &[u8], prefix: &[u8], output: &mut Vec<u8>, nbytes: usize, output_limit: usize) -> Result<usize, DecodeError> {
+        let existing = output.len();
+        let grow = nbytes.min(input.len().saturating_mul(255).saturating_add(16));
+        output.resize(existing + grow, 0);
+        let job = sys::lzf_decompress_job {
+            input: input.as_ptr(), input_len: input.len() as u64,
+            prefix: prefix.as_ptr(), prefix_len: prefix.len() as u64,
+            out: output.as_mut_ptr(), out_existing_len: existing as u64, out_cap: (existing + grow) as u64,
+            output_limit: output_limit as u64,
+        };
+        let mut res = sys::lzf_job_result::default();
+        // (existing output of any length: the host entry point stages its last 65 535 bytes only)
+        let rc = unsafe { sys::lzf_decompress_head_batch_host(&job, &mut res, 1) };
+        assert_eq!(rc, 0, "lzfear_hip: no device / HIP error");
+        let n = if res.status == sys::LZF_OK { (res.out_len as usize).min(existing + grow).max(existing) } else { existing };
+        output.truncate(n);
+        match res.status {
+            sys::LZF_OK => Ok(n - existing),
+            sys::LZF_UNEXPECTED_END => Err(DecodeError::UnexpectedEnd),
+            sys::LZF_MEMORY_LIMIT_EXCEEDED => Err(DecodeError::MemoryLimitExceeded),
+            sys::LZF_ZERO_DEDUP_OFFSET => Err(DecodeError::ZeroDeduplicationOffset),
+            sys::LZF_INVALID_DEDUP_OFFSET => Err(DecodeError::InvalidDeduplicationOffset),
+            _ => panic!("lzfear_hip: contract"),
+        }
+    }
 }

@@ -224,7 +224,46 @@ int lzf_decompressed_size_batch(const lzf_decompress_job* d_jobs, lzf_job_result
  * Asynchronous on `hip_stream`, no host wait. */
 int lzf_decompress_verify_batch(const lzf_decompress_job* d_jobs, lzf_job_result* d_results,
                                 uint32_t n_jobs, uint64_t max_input_len, void* hip_stream);
-/* Jobs with long existing output — a Vec that block after block is appended to, a linked stream — for the two calls above.
+/* The HEAD of every job's block: decode until the output is `out_cap` bytes long and stop (liblz4's LZ4_decompress_safe_partial).
+ * A record header, a dtype/shape preamble or a file magic out of thousands of blocks costs what the heads cost, not the blocks.
+ * Same job struct as the decoder, the size call and the verify call (all four run from one array).  Here out_cap is the TARGET: the
+ * absolute output length, out_existing_len included, at which decoding stops — as the verify call reads out_cap as the end of the
+ * expected bytes.  input, prefix, out[0, out_existing_len) and output_limit mean what they mean to the decoder.
+ * The result is that of the reference's loop (src/raw/decompress.rs:61-77) with one added rule; `pos` is output.len() at the top of
+ * an iteration, the position of the sequence's first literal:
+ *   stop     the loop ends with Ok in front of the first sequence whose pos >= out_cap.  That sequence and everything behind it
+ *            is never looked at, malformed or not.
+ *   checks   a sequence with pos < out_cap is taken whole, exactly as the reference takes it: token and length bytes,
+ *            UnexpectedEnd (the whole literal run must be in the input), then the limit test :72-74, then the offset tests :83-89
+ *            — also where its literals alone already reach the target.  The first failing sequence in stream order wins; inside a
+ *            sequence the reference's order.
+ *   writes   of such a sequence the bytes at positions below out_cap are written, the rest are dropped:
+ *            out[out_existing_len, min(n, out_cap)) holds exactly the bytes the decoder would put there; no byte at or beyond
+ *            out + out_cap and no byte below out + out_existing_len is ever written.
+ *   status   LZF_OK with out_len = min(n, out_cap), n the length reached when the loop ended.  out_len < out_cap says the block
+ *            ended first; out_len == out_cap does NOT say whether more follows (the size call answers that).  Codec statuses 1..4
+ *            as above, out_len unspecified (bytes below out_cap may have been written).  LZF_CONTRACT under the decoder's
+ *            conditions for lengths: input_len, out_existing_len or prefix_len of 2 GiB - 256 or more.  LZF_OUT_CAPACITY is never
+ *            reported.
+ * What follows from that:
+ *   out_cap <= out_existing_len  is LZF_OK with out_len = out_existing_len, and no input byte is read;
+ *   a target beyond the block's end is the full decode (by one wavefront: see below);
+ *   an error in a sequence that starts at or behind the target is not seen — the price of reading only the head.  A caller who
+ *   needs the block's status asks the size call.
+ * No byte outside input[0, input_len), prefix[0, prefix_len) and out[0, out_cap) is read.
+ * lzf_history_trim_batch / lzf_history_restore_batch work on these jobs unchanged: the target moves with the origin.  `reserved`:
+ * kilo-cycles, as for the decoder.  Asynchronous on `hip_stream`, no host wait; the only scratch is a 4-byte job counter from the
+ * stream-ordered pool.
+ * One wavefront per job, whatever the target, and no class of many wavefronts for large targets: the stop saves the chunks behind
+ * the target, the bytes in front of it come at one wavefront's rate.  A caller who wants most of a large block decodes it whole
+ * (lzf_decompress_batch_sized) and slices.  Measured on one MI355X, 2026-10-21, against
+ * lzf_decompress_batch_sized of the whole blocks + lzf_copy_ranges of the heads (tools/head_bench.py, profiles/head_decode.txt), 4 MiB
+ * blocks: 980 blocks 0.24 ms against 15.1 at 64 bytes, 0.26 ms against 15.1 at 4 KiB; the CROSSOVER, from which decoding whole and
+ * slicing is not slower, lies at a target of 768 KiB for 980 blocks (at 512 KiB the head call is still 1.4 x quicker) and at 512 KiB
+ * for 49 blocks (at 384 KiB still 1.2 x quicker). */
+int lzf_decompress_head_batch(const lzf_decompress_job* d_jobs, lzf_job_result* d_results,
+                              uint32_t n_jobs, void* hip_stream);
+/* Jobs with long existing output — a Vec that block after block is appended to, a linked stream — for the calls above.
  * decompress_raw compares output.len() with output_limit and with offsets only, and no offset reaches further back than 65 535
  * bytes, so a job may be restated with its origin `shift` bytes further on without changing a byte or a status:
  *   out_existing_len < 2^30, or > out_cap:  shift = 0, the job is copied as it is;
@@ -323,6 +362,12 @@ int lzf_decompressed_size_batch_host(const lzf_decompress_job* jobs, lzf_job_res
  * and out[0, out_cap) — history and expected bytes; of a history of 1 GiB and more its last 64 KiB — are staged to the device,
  * `results` is a host array.  out_len comes back absolute, for LZF_MISMATCH as well.  Synchronous. */
 int lzf_decompress_verify_batch_host(const lzf_decompress_job* jobs, lzf_job_result* results, uint32_t n_jobs);
+/* lzf_decompress_head_batch over host buffers: `input`, `prefix` and `out` of every job are HOST pointers.  The input, the prefix
+ * and at most the last 65 535 bytes of out[0, out_existing_len) are staged to the device — existing output of any length below the
+ * target is accepted, the long-history trim included — and only out[out_existing_len, out_len) comes back; nothing else of `out`
+ * is touched.  Device room is what the block can decode to, never more than the target asks for.  `results` is a host array,
+ * out_len comes back absolute.  Synchronous. */
+int lzf_decompress_head_batch_host(const lzf_decompress_job* jobs, lzf_job_result* results, uint32_t n_jobs);
 /* lzf_compressed_size_batch over host buffers: `input` and `table` of every job are HOST pointers (staged to the device; a
  * writable table is updated in place, as lzf_compress_batch_host does), `results` a host array; `out` is ignored, out_cap is
  * honoured as above.  Synchronous. */

@@ -264,6 +264,74 @@ int lzf_decompress_verify_batch_host(const lzf_decompress_job* jobs, lzf_job_res
     return LZF_OK;
 }
 
+// The head call on host buffers.  Of a job's existing output at most the last 65 535 bytes can be a match source (an offset is a
+// u16), so that tail is all that goes up: the job is restated with its origin `shift` = out_existing_len - 65 535 bytes further on,
+// by lzf_history_trim.h's rule for the lengths (which is also the long-history trim: any out_existing_len below the target is
+// answered).  A job whose target does not lie beyond its existing output goes up as it is, without bytes: the device call answers
+// it without reading any.  The room on the device is what the block can decode to (255 bytes per input byte), not the target.
+int lzf_decompress_head_batch_host(const lzf_decompress_job* jobs, lzf_job_result* results, uint32_t n_jobs) {
+    if (n_jobs == 0) return LZF_OK;
+    if (!jobs || !results) { g_last_error = "lzf_decompress_head_batch_host: NULL argument"; return LZF_E_INVALID; }
+    int rc = ensure_device();
+    if (rc < 0) return rc;
+    constexpr uint64_t kReach = 65535;
+    std::vector<uint64_t> shift(n_jobs), keep(n_jobs), room(n_jobs);
+    std::vector<size_t> in_off(n_jobs), pre_off(n_jobs), out_off(n_jobs);
+    size_t in_total = 0, out_total = 0;
+    std::vector<Seg> up, up_out;
+    for (uint32_t i = 0; i < n_jobs; ++i) {
+        const lzf_decompress_job& j = jobs[i];
+        const bool work = j.out_cap > j.out_existing_len;
+        if ((j.input_len && !j.input) || (j.prefix_len && !j.prefix) || (work && !j.out)) {
+            g_last_error = "lzf_decompress_head_batch_host: NULL buffer with a length"; return LZF_E_INVALID;
+        }
+        keep[i] = work ? (j.out_existing_len < kReach ? j.out_existing_len : kReach) : 0;
+        shift[i] = work ? j.out_existing_len - keep[i] : 0;
+        const uint64_t want = work ? j.out_cap - j.out_existing_len : 0, most = 255ull * j.input_len + 64u;
+        room[i] = want < most ? want : most;
+        in_off[i] = in_total; in_total = align_up(in_total + j.input_len, 256);
+        if (j.input_len) up.push_back({in_off[i], const_cast<uint8_t*>(j.input), (size_t)j.input_len});
+    }
+    for (uint32_t i = 0; i < n_jobs; ++i) {
+        pre_off[i] = in_total; in_total = align_up(in_total + jobs[i].prefix_len, 256);
+        if (jobs[i].prefix_len) up.push_back({pre_off[i], const_cast<uint8_t*>(jobs[i].prefix), (size_t)jobs[i].prefix_len});
+    }
+    for (uint32_t i = 0; i < n_jobs; ++i) {
+        out_off[i] = out_total; out_total = align_up(out_total + keep[i] + room[i], 256);
+        if (keep[i]) up_out.push_back({out_off[i], jobs[i].out + shift[i], (size_t)keep[i]});
+    }
+    HostCall<lzf_decompress_job> h;
+    if ((rc = h.open(n_jobs, in_total ? in_total : 256, out_total ? out_total : 256, true)) != LZF_OK) return rc;
+    std::vector<lzf_decompress_job> dj(jobs, jobs + n_jobs);
+    for (uint32_t i = 0; i < n_jobs; ++i) {
+        dj[i].input = h.din + in_off[i];
+        dj[i].prefix = h.din + pre_off[i];
+        dj[i].out = h.dout + out_off[i];
+        if (jobs[i].out_cap > jobs[i].out_existing_len) {
+            dj[i].out_existing_len = keep[i];
+            dj[i].out_cap = jobs[i].out_cap - shift[i];
+            dj[i].output_limit = lzf_trim::limit_of(jobs[i].output_limit, shift[i]);
+        }
+    }
+    if (!up_out.empty()) {                          // (the slab is used for one move at a time: existing output first, and wait for it)
+        HIP_TRY(h.sg.upload(up_out, out_total, h.dout));
+        HIP_TRY(h.sg.join_copies(h.cs));
+        HIP_TRY(hipStreamSynchronize(h.cs));
+    }
+    if ((rc = h.send(up, in_total, dj)) != LZF_OK) return rc;
+    if ((rc = h.fetch(lzf_decompress_head_batch(h.djobs, h.dres, n_jobs, h.cs), results)) != LZF_OK) return rc;
+    std::vector<Seg> down;
+    for (uint32_t i = 0; i < n_jobs; ++i) {
+        if (results[i].status != LZF_OK) continue;
+        const uint64_t n = results[i].out_len;      // relative to the moved origin
+        if (n > keep[i] && jobs[i].out_cap > jobs[i].out_existing_len)
+            down.push_back({out_off[i] + (size_t)keep[i], jobs[i].out + jobs[i].out_existing_len, (size_t)(n - keep[i])});
+        lzf_trim::restore(results[i], shift[i]);
+    }
+    HIP_TRY(h.sg.download(down, out_total, h.dout, h.cs));
+    return LZF_OK;
+}
+
 // ---- EncoderTable on host tables (src/raw/compress/mod.rs:40-61, :64-74, :88-99) --------------------------------------
 int lzf_table_replace_host(void* table, uint32_t table_kind, const uint8_t* input, uint64_t input_len, uint64_t pos, uint64_t* previous) {
     if (!table || (!input && input_len) || table_kind > LZF_TABLE_U16) { g_last_error = "lzf_table_replace_host: bad argument"; return LZF_E_INVALID; }

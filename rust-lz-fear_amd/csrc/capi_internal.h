@@ -1,5 +1,6 @@
-// capi_internal.h — what the three translation units behind include/lzfear_hip.h share: capi.hip (the extern "C" device entry
-// points), capi_drivers.hip (the segmented and bitmap-fed decompress drivers) and capi_host.cpp (the host-buffer wrappers).
+// capi_internal.h — what the translation units behind include/lzfear_hip.h share: capi.hip (the extern "C" device entry
+// points), capi_head.hip (the head call), capi_drivers.hip (the segmented and bitmap-fed decompress drivers) and capi_host.cpp
+// (the host-buffer wrappers).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -77,6 +78,7 @@ struct Device {
     uint32_t fed_slots = 0, fed_xcc_mask = 0;        // workgroups of the fed kernel resident at once, counted; 0: not counted yet
     uint32_t size_resident = 0;      // workgroups of the size kernel per CU (0: not asked yet)
     uint32_t verify_resident = 0;    // ... and of the verify kernel
+    uint32_t head_resident = 0;      // ... and of the head kernel (capi_head.hip)
     SegLanes lanes;
     bool spare = false;              // the one record of device numbers beyond the table: nothing is kept in it
 };

@@ -115,6 +115,55 @@ def last_verify_launch():
     return ffi.lib().lzf_last_verify_launch().decode()
 
 
+def decompress_head_batch(d_jobs, d_res, n, stream=None, max_input_len=None):
+    """lzf_decompress_head_batch: the head of every decode job's block — decoding stops where the output is out_cap bytes long, out_cap
+    being the target (out_existing_len included).  The same job array as decompress_batch.  Per job LZF_OK with out_len =
+    min(decoded length, out_cap), or the codec status of a sequence that starts in front of the target; what lies behind it is not
+    looked at.  (max_input_len: accepted for _with_long_history's sake; the call has no use for it.)"""
+    ffi.check(ffi.lib().lzf_decompress_head_batch(d_jobs.data_ptr(), d_res.data_ptr(), n, _stream_ptr(stream)))
+
+
+def decompress_head_batch_long_history(d_jobs, d_res, n, stream=None):
+    """decompress_head_batch for jobs whose existing output may be 1 GiB and more: trim, decode the heads, restore, all on `stream`; the
+    target moves with the origin and out_len comes back absolute.  Returns the two scratch tensors, as decompress_batch_long_history."""
+    return _with_long_history(decompress_head_batch, d_jobs, d_res, n, stream, None)
+
+
+def block_heads(blocks, nbytes, prefix=None, stream=None):
+    """The first `nbytes` decoded bytes of every raw block in `blocks` (1-D uint8 CUDA tensors), `prefix` (a 1-D uint8 CUDA tensor) being
+    every block's dictionary: (heads, lens, statuses) — heads a [n, nbytes] uint8 CUDA tensor (row i: the head of block i, zeros behind
+    lens[i] bytes), lens int64 and statuses int32 CUDA tensors, all written in order on `stream`.  One lzf_decompress_head_batch: a
+    block is decoded no further than the sequence that reaches nbytes.  No output limit is applied."""
+    n = len(blocks)
+    dev = blocks[0].device if n else torch.device("cuda", torch.cuda.current_device())
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.stream(s):
+        heads = torch.zeros((n, nbytes), dtype=torch.uint8, device=dev)
+        if n == 0:
+            return heads, torch.zeros(0, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.int32, device=dev)
+        for t in blocks:
+            assert t.dtype == torch.uint8 and t.is_cuda and t.dim() == 1 and t.is_contiguous(), "blocks: 1-D contiguous uint8 CUDA tensors"
+        j = np.zeros(n, dtype=DJOB)
+        j["input"] = [t.data_ptr() for t in blocks]
+        j["input_len"] = [t.numel() for t in blocks]
+        if prefix is not None and prefix.numel():
+            assert prefix.dtype == torch.uint8 and prefix.is_cuda and prefix.dim() == 1 and prefix.is_contiguous()
+            j["prefix"] = prefix.data_ptr()
+            j["prefix_len"] = prefix.numel()
+        j["out"] = np.uint64(heads.data_ptr()) + np.arange(n, dtype=np.uint64) * np.uint64(nbytes)
+        j["out_cap"] = nbytes
+        j["output_limit"] = (1 << 63) - 1
+        d_jobs = to_device(j, dev)
+        d_res = torch.empty(n * RES.itemsize, dtype=torch.uint8, device=dev)
+        decompress_head_batch(d_jobs, d_res, n, stream=s)
+        r = d_res.view(torch.int64).view(n, 2)
+        lens = r[:, 0].clone()
+        statuses = d_res.view(torch.int32).view(n, 4)[:, 2].clone()
+    for t in (heads, d_jobs, d_res, lens, statuses):
+        t.record_stream(s)
+    return heads, lens, statuses
+
+
 def xxh32_batch(d_ptrs, d_lens, d_out, n, stream=None):
     ffi.check(ffi.lib().lzf_xxh32_batch(d_ptrs.data_ptr(), d_lens.data_ptr(), d_out.data_ptr(), n, _stream_ptr(stream)))
 

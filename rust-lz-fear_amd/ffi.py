@@ -68,7 +68,7 @@ class FrameInfo(C.Structure):
 
 EXPORTS = [
     "lzf_abi_version", "lzf_last_error", "lzf_device_count", "lzf_compress_batch", "lzf_compressed_size_batch", "lzf_compressed_size_batch_host",
-    "lzf_decompress_batch", "lzf_decompress_batch_sized", "lzf_decompressed_size_batch", "lzf_decompressed_size_batch_host", "lzf_decompress_verify_batch", "lzf_decompress_verify_batch_host", "lzf_last_verify_launch", "lzf_last_decompress_launch", "lzf_last_compress_launch", "lzf_last_size_launch", "lzf_table_replace_host", "lzf_table_offset_host", "lzf_compress2_host_writer", "lzf_table_seed_from_dictionary", "lzf_table_offset", "lzf_table_offset_batch",
+    "lzf_decompress_batch", "lzf_decompress_batch_sized", "lzf_decompressed_size_batch", "lzf_decompressed_size_batch_host", "lzf_decompress_verify_batch", "lzf_decompress_verify_batch_host", "lzf_last_verify_launch", "lzf_decompress_head_batch", "lzf_decompress_head_batch_host", "lzf_last_decompress_launch", "lzf_last_compress_launch", "lzf_last_size_launch", "lzf_table_replace_host", "lzf_table_offset_host", "lzf_compress2_host_writer", "lzf_table_seed_from_dictionary", "lzf_table_offset", "lzf_table_offset_batch",
     "lzf_chain_decompress_step", "lzf_chain_decompress_step_trimmed", "lzf_history_trim_batch", "lzf_history_restore_batch",
     "lzf_xxh32_batch", "lzf_copy_ranges", "lzf_compress_batch_host", "lzf_decompress_batch_host", "lzf_xxh32_batch_host",
 ]
@@ -220,6 +220,9 @@ def lib():
             L.lzf_decompress_verify_batch_host.argtypes = [C.POINTER(DecompressJob), C.POINTER(JobResult), C.c_uint32]
             L.lzf_frame_verify_device.argtypes = [C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t,
                                                   C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(L, "lzf_decompress_head_batch"):         # (tools/head_bench.py loads the parent commit's library, which has no head calls, for its baseline)
+            L.lzf_decompress_head_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+            L.lzf_decompress_head_batch_host.argtypes = [C.POINTER(DecompressJob), C.POINTER(JobResult), C.c_uint32]
         L.lzf_frame_decompressed_size_device.argtypes = [C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t,
                                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.lzf_frame_stream_bound_device.argtypes = [C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_void_p]
@@ -435,3 +438,34 @@ def verify_blocks_host(items):
         jobs[i].output_limit = (1 << 63) - 1 if limit is None else limit
     check(lib().lzf_decompress_verify_batch_host(jobs, res, n))
     return [(res[i].status, res[i].out_len) for i in range(n)]
+
+
+def block_heads_host(items):
+    """items: list of dict(input=bytes, prefix=bytes, existing=bytes, nbytes=int, limit=int).  Returns [(status, out_len, bytes)]:
+    the first `nbytes` decoded bytes of the block behind `existing` (fewer where the block ends first; out_len counts `existing`),
+    or a codec status for a sequence that starts in front of them — decoded on the device no further than asked
+    (lzf_decompress_head_batch_host)."""
+    n = len(items)
+    if n == 0:
+        return []
+    jobs = (DecompressJob * n)()
+    res = (JobResult * n)()
+    keep = []
+    for i, it in enumerate(items):
+        data, prefix, existing = bytes(it["input"]), bytes(it.get("prefix", b"")), bytes(it.get("existing", b""))
+        cap = len(existing) + it["nbytes"]
+        ob = C.create_string_buffer(max(cap, 1))
+        ob[: len(existing)] = existing
+        keep.append((data, prefix, ob))
+        limit = it.get("limit")
+        jobs[i].input = _bytes_address(data)
+        jobs[i].input_len = len(data)
+        jobs[i].prefix = _bytes_address(prefix)
+        jobs[i].prefix_len = len(prefix)
+        jobs[i].out = C.addressof(ob)
+        jobs[i].out_existing_len = len(existing)
+        jobs[i].out_cap = cap
+        jobs[i].output_limit = (1 << 63) - 1 if limit is None else limit
+    check(lib().lzf_decompress_head_batch_host(jobs, res, n))
+    return [(res[i].status, res[i].out_len,
+             buffer_bytes(keep[i][2], res[i].out_len)[jobs[i].out_existing_len:] if res[i].status == OK else b"") for i in range(n)]
