@@ -166,6 +166,12 @@ extern "C" {
     // d_in / in_len are host arrays of device addresses, the results device arrays written in stream order (d_consumed may be null)
     pub fn lzf_frame_decompressed_size_device(n_frames: u32, d_in: *const *const u8, in_len: *const usize, dict_len: usize,
                                               d_out_len: *mut u64, d_consumed: *mut u64, d_status: *mut i32, hip_stream: *mut c_void) -> c_int;
+    // frames in device memory: the first target[f] bytes of every frame, decoded no further (one wavefront per frame, nothing read back).
+    // d_in / in_len / d_out / target are host arrays, the results device arrays written in stream order.  Block checksums and the
+    // content checksum are NOT verified by this call; a target of 2 GiB - 256 or more is LZF_CONTRACT
+    pub fn lzf_frame_head_device(n_frames: u32, d_in: *const *const u8, in_len: *const usize, d_dict: *const u8, dict_len: usize,
+                                 d_out: *const *mut u8, target: *const usize, d_out_len: *mut u64, d_status: *mut i32,
+                                 hip_stream: *mut c_void) -> c_int;
     // streams of back-to-back frames in device memory (one contiguous output per stream; the pieces of an input packed back to back)
     pub fn lzf_frame_stream_bound_device(n_streams: u32, d_in: *const *const u8, in_len: *const usize, out_bound: *mut usize,
                                          hip_stream: *mut c_void) -> c_int;

@@ -257,6 +257,49 @@ int lzf_frame_verify_device(uint32_t n_frames, const uint8_t* const* d_in, const
                             const uint8_t* d_dict, size_t dict_len,
                             const uint8_t* const* d_expected, const size_t* expected_len,
                             uint64_t* d_at, uint64_t* d_consumed, int32_t* d_status, void* hip_stream);
+/* "What are the first target[f] bytes of this frame?" per frame, decoding no further: the frame form of lzf_decompress_head_batch
+ * (include/lzfear_hip.h), for a record header, a dtype/shape preamble, a file magic out of thousands of frames.  Conventions of
+ * lzf_frame_decompress_device_many: d_in / in_len / d_out / target are HOST arrays, d_in[f] / d_out[f] DEVICE addresses at any
+ * alignment (d_out[f] may be NULL where target[f] is 0); frames may alias each other, outputs must not overlap each other or any
+ * input; d_out_len / d_status are DEVICE arrays written in stream order; d_dict / dict_len: the dictionary in device memory,
+ * NULL = none.  The rule (csrc/lzf_frame_head_rules.h, one definition for the kernel and the CPU tests), with pos = the bytes
+ * delivered when the reader's decode_block is entered:
+ *   - the header is parsed always, also for target 0; a header that fails gives its status with out_len 0;
+ *   - the reader ends with LZF_OK in front of the first block entered at pos >= target[f]: that block's length word and everything
+ *     behind it is never looked at, malformed or not;
+ *   - a block entered at pos < target[f] is read as the reader reads it: the EndMark (its content checksum word must be there, else
+ *     LZF_F_INPUT_ERROR, but is not compared) ends the frame with LZF_OK and out_len = pos — the frame ended first;
+ *     LZF_F_BLOCK_SIZE_OVERFLOW for a length word above block_maxsize; LZF_F_INPUT_ERROR where the payload or its checksum word is
+ *     cut off.  A stored block's bytes below the target are copied.  A compressed block goes through the head walk of
+ *     lzf_decompress_head_batch on the job the decode states for it; a codec status 1..4 ends the frame with that status and
+ *     out_len = pos, the length in front of the failing block (bytes below the target may have been written);
+ *   - behind a block that ended in front of the target the reader's remaining stops apply: more than block_maxsize bytes is
+ *     LZF_F_BLOCK_SIZE_OVERFLOW, an empty block ends the frame with LZF_OK, both with out_len = pos.  A block that reaches the
+ *     target is asked neither question: an error at or behind the target is not seen, as in the raw call;
+ *   - LZF_OK with out_len = min(pos reached, target[f]).  out_len < target[f]: the frame ended first; out_len == target[f] does not
+ *     say whether more follows.  No byte at or beyond d_out[f] + target[f] is written.
+ * THE CHECKSUM EXCEPTION: block checksums are stepped over and the content checksum is not compared.  The size, verify and decode
+ * calls verify block checksums; this call is for reading a preamble, and hashing a 4 MiB block at ~1.3 GB/s to read 64 bytes of
+ * it would cost 3 ms, the whole point of the call lost.  A frame whose block 0 is damaged reports LZF_OK here and the damaged
+ * bytes, and LZF_F_BLOCK_CHECKSUM_FAIL from lzf_frame_decompressed_size_device.
+ * Contract: a target of 2 GiB - 256 or more is LZF_CONTRACT for that frame with nothing read (a head is short; with that bound no
+ * position of the walk leaves the decoder's 31-bit contract); a dictionary of that length is LZF_CONTRACT where a compressed block
+ * is entered.
+ * Cost: one wavefront per frame (lzf_frame_head_kernel), as many workgroups as the device holds at once drawing frames from a
+ * 4-byte ticket; a frame costs what its target asks for, not what it holds, and a target that spans many blocks is decoded at one
+ * wavefront's rate — correct, not meant to be fast.  The host packs the four arrays into one upload, enqueues the kernel, waits
+ * only for that upload to leave host memory and returns: nothing is read back, nothing is scanned or planned.  Scratch: 32 bytes
+ * per frame and the ticket, from the stream-ordered pool.
+ * Measured on one MI355X against the parent commit's library decoding the frames whole and copying the heads
+ * (lzf_frame_decompress_device_many + lzf_copy_ranges; profiles/frame_head.txt): 980 frames of one 4 MiB block 0.13 ms against
+ * 20.5 at 64 bytes and 0.18 ms against 20.5 at 4 KiB; 49 frames of 20 x 4 MiB blocks 0.057 ms against 66.6 at 64 bytes; one linked
+ * frame of 16 x 4 MiB 0.049 ms against 102.4 at 64 bytes and 53.4 ms against 102.5 at 4 MiB + 64; 30 000 frames of 64 KiB at 256
+ * bytes 0.59 ms against 16.2.  CROSSOVER for the 980 frames, the smallest target of the sweep at which decoding whole and slicing
+ * is not slower: 1 MiB (16.2 ms against 20.8 at 768 KiB, 25.9 ms against 20.9 at 1 MiB; the whole 4 MiB takes 85.3 ms against 21.9). */
+int lzf_frame_head_device(uint32_t n_frames, const uint8_t* const* d_in, const size_t* in_len,
+                          const uint8_t* d_dict, size_t dict_len,
+                          uint8_t* const* d_out, const size_t* target,
+                          uint64_t* d_out_len, int32_t* d_status, void* hip_stream);
 /* lzf_frame_compress_many for inputs that live in device memory, compressed into device memory: compress_internal
  * (src/framed/compress.rs:160-282) of every frame with the settings `s` (a host struct, shared by all frames as in
  * lzf_frame_compress_many: flags, dictionary id and content size of the header come from it).  s->dictionary must be NULL

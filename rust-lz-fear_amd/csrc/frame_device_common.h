@@ -9,6 +9,8 @@
 //                              lzf_frame_block_index_device, lzf_frame_decompress_blocks_device, the two *_locate calls
 //   frame_device_verify.hip    size_frames, the block index into scratch, a verify job or a stored range per delivered block and
 //                              the fold: lzf_frame_verify_device
+//   frame_device_head.hip      one wavefront per frame, the frame walk and the block's head walk together, nothing read back:
+//                              lzf_frame_head_device
 //   frame_device_compress.hip  plan_cpass / compress_frames / compress_streams and the assembly kernels: lzf_frame_compress_device_many,
 //                              lzf_frame_compressed_size_device, lzf_frame_compress_stream_device, lzf_frame_compress_stream_size_device,
 //                              lzf_frame_compress_stream_bound

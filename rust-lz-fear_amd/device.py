@@ -295,6 +295,43 @@ def frame_verify(frames, expected, dictionary=None, stream=None):
     return status, at, consumed
 
 
+def frame_head_raw(in_ptrs, in_lens, out_ptrs, targets, d_out_len, d_status, dictionary=None, stream=None):
+    """lzf_frame_head_device on plain addresses: frame f is in_lens[f] bytes at the device address in_ptrs[f], its first targets[f]
+    decoded bytes go to the device address out_ptrs[f] (any alignment; 0 where the target is 0).  d_out_len (int64) and d_status
+    (int32) are CUDA tensors of len(in_ptrs) entries, written in order on `stream`."""
+    n = len(in_ptrs)
+    assert len(in_lens) == n and len(out_ptrs) == n and len(targets) == n
+    dptr, dlen = None, 0
+    if dictionary is not None and dictionary.numel():
+        assert dictionary.dtype == torch.uint8 and dictionary.is_cuda and dictionary.is_contiguous()
+        dptr, dlen = dictionary.data_ptr(), dictionary.numel()
+    ffi.check(ffi.lib().lzf_frame_head_device(n, (C.c_void_p * n)(*in_ptrs), (C.c_size_t * n)(*in_lens), dptr, dlen, (C.c_void_p * n)(*out_ptrs),
+                                              (C.c_size_t * n)(*targets), d_out_len.data_ptr(), d_status.data_ptr(), _stream_ptr(stream)))
+
+
+def frame_heads(frames, nbytes, dictionary=None, stream=None):
+    """The first `nbytes` decoded bytes of every frame in `frames` (1-D uint8 CUDA tensors), `dictionary` (a 1-D uint8 CUDA tensor)
+    being every frame's dictionary: (heads, lens, statuses) — heads a [n, nbytes] uint8 CUDA tensor (row f: the head of frame f,
+    zeros behind lens[f] bytes where statuses[f] is 0), lens int64 and statuses int32 CUDA tensors, all written in order on `stream`.  One
+    lzf_frame_head_device: a frame is decoded no further than the sequence that reaches nbytes, nothing comes back to the host.
+    Block checksums and the content checksum are NOT verified (frame_decompressed_size and frame_verify do that): this is for
+    reading a preamble.  The twin of block_heads."""
+    n, _, in_lens = _frame_args(frames)
+    dev = frames[0].device if n else torch.device("cuda", torch.cuda.current_device())
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.stream(s):
+        heads = torch.zeros((n, nbytes), dtype=torch.uint8, device=dev)
+        lens = torch.zeros(n, dtype=torch.int64, device=dev)
+        statuses = torch.zeros(n, dtype=torch.int32, device=dev)
+        if n:
+            base = heads.data_ptr()
+            frame_head_raw([t.data_ptr() for t in frames], list(in_lens), [base + f * nbytes if nbytes else 0 for f in range(n)], [nbytes] * n,
+                           lens, statuses, dictionary=dictionary, stream=s)
+    for t in (heads, lens, statuses):
+        t.record_stream(s)
+    return heads, lens, statuses
+
+
 def frame_compress_many(settings, frames, outs, dictionary=None, stream=None, caps=None):
     """lzf_frame_compress_device_many: every input of `frames` (1-D uint8 CUDA tensors) compressed into an LZ4 frame in `outs`
     (1-D uint8 CUDA tensors, their lengths are the capacities) with `settings` (an ffi.Settings whose `dictionary` is NULL; the

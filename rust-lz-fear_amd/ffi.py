@@ -81,7 +81,7 @@ FRAME_EXPORTS = [
     "lzf_frame_writer_new", "lzf_frame_writer_write", "lzf_frame_writer_finish", "lzf_frame_writer_sink_error", "lzf_frame_writer_free",
     "lzf_frame_get_stats", "lzf_frame_release_scratch", "lzf_frame_set_host_threads", "lzf_frame_set_memory_budget",
     "lzf_frame_set_pinned_limit", "lzf_frame_decompress_bound_device", "lzf_frame_decompress_device_many",
-    "lzf_frame_compress_device_many", "lzf_frame_decompressed_size_device", "lzf_frame_verify_device", "lzf_frame_compressed_size_device", "lzf_frame_compress_stream_size_device",
+    "lzf_frame_compress_device_many", "lzf_frame_decompressed_size_device", "lzf_frame_verify_device", "lzf_frame_head_device", "lzf_frame_compressed_size_device", "lzf_frame_compress_stream_size_device",
     "lzf_frame_stream_bound_device", "lzf_frame_decompress_stream_device", "lzf_frame_compress_stream_bound", "lzf_frame_compress_stream_device",
     "lzf_frame_stream_count_device", "lzf_frame_stream_decompressed_size_device", "lzf_stream_index_locate",
     "lzf_frame_block_count_device", "lzf_frame_block_index_device", "lzf_block_index_locate", "lzf_frame_decompress_blocks_device",
@@ -223,6 +223,9 @@ def lib():
         if hasattr(L, "lzf_decompress_head_batch"):         # (tools/head_bench.py loads the parent commit's library, which has no head calls, for its baseline)
             L.lzf_decompress_head_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
             L.lzf_decompress_head_batch_host.argtypes = [C.POINTER(DecompressJob), C.POINTER(JobResult), C.c_uint32]
+        if hasattr(L, "lzf_frame_head_device"):             # (tools/frame_head_bench.py loads the parent commit's library, which has no frame head call, for its baseline)
+            L.lzf_frame_head_device.argtypes = [C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t,
+                                                C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p]
         L.lzf_frame_decompressed_size_device.argtypes = [C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t,
                                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.lzf_frame_stream_bound_device.argtypes = [C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_void_p]

@@ -386,6 +386,39 @@ def verify_frames_device(frames, expected, dictionary=None, stream=None):
     return list(zip(status.cpu().tolist(), at.cpu().tolist()))
 
 
+def frame_heads_device(frames, nbytes, dictionary=None, stream=None):
+    """The first `nbytes` decoded bytes of every frame (1-D uint8 CUDA tensors), decoded on the device no further than that
+    (lzf_frame_head_device): [(status, head)] once `stream` has finished the call — head a uint8 CUDA tensor of min(nbytes, the
+    frame's length) bytes where the status is 0, the bytes of the blocks in front of the failing block otherwise.  A frame
+    shorter than nbytes is status 0 with a shorter head.  Block checksums and the content checksum are NOT verified: a damaged
+    frame may report status 0 here; `decompressed_sizes_device` and `verify_frames_device` verify.  `dictionary`: bytes or a uint8
+    CUDA tensor."""
+    import torch
+    from . import device
+    frames = list(frames)
+    if not frames:
+        return []
+    dev = frames[0].device
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    if dictionary is not None and not isinstance(dictionary, torch.Tensor):
+        dictionary = torch.frombuffer(bytearray(bytes(dictionary)), dtype=torch.uint8).to(dev) if len(dictionary) else None
+        s.wait_stream(torch.cuda.current_stream(dev))   # (the upload ran on the current stream)
+    with torch.cuda.stream(s):
+        heads, lens, statuses = device.frame_heads(frames, nbytes, dictionary=dictionary, stream=s)
+    s.synchronize()
+    st, ln = statuses.cpu().tolist(), lens.cpu().tolist()
+    return [(st[f], heads[f, :ln[f]]) for f in range(len(frames))]
+
+
+def stream_frame_heads_device(stream_tensor, index, nbytes, dictionary=None, stream=None):
+    """The heads of the frames of one stream of back-to-back frames (a 1-D uint8 CUDA tensor) with `index`, its StreamIndex: one
+    (status, head) per frame the index lists as reached — every entry without LZF_SFRAME_BEHIND_STOP, the frame that stopped the
+    stream included — in the index's order.  A frame of a stream is a view of the stream tensor from the frame's in_off on, so this
+    is `frame_heads_device` over those views: one lzf_frame_head_device."""
+    reached = [e for e in index.frames if not int(e["flags"]) & ffi.SFRAME_BEHIND_STOP]
+    return frame_heads_device([stream_tensor[int(e["in_off"]):] for e in reached], nbytes, dictionary=dictionary, stream=stream)
+
+
 def decompress_frames_device(frames, dictionary=None, caps=None, stream=None, exact=False):
     """`decompress_frames` for frames that live on the device (1-D uint8 CUDA tensors), decoded on the device
     (lzf_frame_decompress_device_many).  Outputs are sized from lzf_frame_decompress_bound_device when `caps` is None — or, with
