@@ -141,6 +141,9 @@ FED_PERIODIC_COUNTER_BUILD = ("LZF_DBG_FED_COUNT=4",)
 # The analysis flavour with the parse kernel's plain-hop loop in C++ instead of hand-written assembly: tests/test_gpu_parse_hop.py
 # compares its bit maps with the product loop's, word for word.
 PARSE_TWIN_BUILD = ("LZF_ANALYSIS", "LZF_SEG_NOASM")
+# The analysis flavour with the parse kernel's section timers and counts (lzf_debug_parse_timers: tools/parse_staging.py): tests/test_gpu_parse_memo.py
+# compares its lookups of the saved walks, and the lookups that hit, with a host model.
+PARSE_TIME_BUILD = ("LZF_DBG_PARSE_TIME",)
 
 
 if __name__ == "__main__":

@@ -10,6 +10,14 @@ namespace {
 
 constexpr uint32_t S = kSegRegion;
 constexpr uint32_t kCB = kSegChunk;                // staged bytes of a chunk (with the rows: 20 480 bytes of LDS, eight chunks per CU; tokens that reach over the end take the general routine)
+// Walks of the fixed point a lane keeps beside its live one (11 VGPRs each: entry, exit, merge position, the eight words of row B).
+// LDS holds the parse kernel to two waves per SIMD, so the registers cost no residency.  -DLZF_PARSE_MEMO=2: the depth A/B of profiles/parse_memo.txt.
+#ifndef LZF_PARSE_MEMO
+#define LZF_PARSE_MEMO 1
+#endif
+constexpr uint32_t kParseMemo = LZF_PARSE_MEMO;
+static_assert(kParseMemo == 1u || kParseMemo == 2u, "one or two saved walks");
+constexpr uint32_t kNoEntry = ~0u;                 // an empty slot: no entry has this value (chunk-relative positions stay below 2^31)
 
 __device__ __forceinline__ constexpr uint32_t seg_nch(uint32_t len) {
     return len <= kSegChunk ? 1u : 1u + (len - kSegChunk + kSegStride - 1u) / kSegStride;
@@ -63,26 +71,34 @@ __global__ __launch_bounds__(256) void lzf_seg_plan_kernel(seg_ctx c) {
 //   pass 0   every lane walks from its region start and marks the tokens it visits in row A, keeps its exit;
 //   pass k   entry[i] = max(exit[0..i-1]) (lane 0: the chunk's first byte); a lane whose entry changed walks again from it,
 //            marking row B, until it steps on a token marked in row A — from there on it IS the pass-0 chain — or leaves
-//            the region; repeated until no entry changes (2-3 passes).
+//            the region; repeated until no entry changes (about five passes on compressed text and binaries).
+//            A region's result for an entry depends on the chunk's bytes and on row A alone, and neither changes during the passes:
+//            the result a new entry displaces (walked entry, exit, merge position, row B) is kept in registers, kParseMemo deep, and a
+//            lane whose entry comes back — the lane below corrected itself and its exit returned — takes it back without a walk.
+//            A pass lasts as long as its slowest walking lane, so the passes get shorter, not fewer (tools/parse_memo_model.c).
 //   result   row = (A from the merge position on) | B; exit of the chunk = max of the exits.
 // A plain hop is ONE unaligned 4-byte LDS read from position - 1: [previous token's match-length extension byte, token,
 // first literal-length extension byte, ...].  Tokens a plain hop cannot express (0xFF length bytes, the last 24 bytes of
 // the input) go through the general routine.
 // -DLZF_DBG_PARSE_TIME (analysis): cycles of a parse wave by section, summed over the launch — 0 staging (loads issued and waited for,
 // LDS stores), 1 pass 0, 2 the fixed-point passes, 3 the rows written out; [4] chunks, [5] workgroups that had one; [6] / [7] the hops the
-// wave made in the plain-hop loop (one per half of a trip: a count kept by the scalar unit inside the loop) in pass 0 / in the fixed-point passes.
+// wave made in the plain-hop loop (one per half of a trip: a count kept by the scalar unit inside the loop) in pass 0 / in the fixed-point passes;
+// [8] / [9] the lookups of the saved walks (a lane whose entry changed, in any pass) / the lookups that hit.
 // lzf_debug_parse_timers() reads (and clears) the sums: tools/parse_staging.py.
 #ifdef LZF_DBG_PARSE_TIME
-__device__ unsigned long long lzf_dbg_parse_cycles[8];
-#define PT_START() long long pt_t = clock64(); unsigned long long pt[4] = {0, 0, 0, 0}; uint32_t pt_n = 0, pt_hops[2] = {0, 0}
+__device__ unsigned long long lzf_dbg_parse_cycles[10];
+#define PT_START() long long pt_t = clock64(); unsigned long long pt[4] = {0, 0, 0, 0}; uint32_t pt_n = 0, pt_hops[2] = {0, 0}, pt_memo[2] = {0, 0}
+#define PT_MEMO(look, hit) do { pt_memo[0] += (uint32_t)__popcll(__ballot(look)); pt_memo[1] += (uint32_t)__popcll(__ballot(hit)); } while (0)
 #define PT_MARK(i) do { const long long tn_ = clock64(); pt[i] += (unsigned long long)(tn_ - pt_t); pt_t = tn_; } while (0)
 #define PT_CHUNK() (++pt_n)
 #define PT_HOP_ASM "s_add_u32 %[nh], %[nh], 1\n\t"
 #define PT_HOPS(mode, n) (pt_hops[mode] += (n))
 #define PT_REPORT() do { if (lane == 0u && pt_n) { for (int i_ = 0; i_ < 4; ++i_) atomicAdd(&lzf_dbg_parse_cycles[i_], pt[i_]); \
                                                      atomicAdd(&lzf_dbg_parse_cycles[4], (unsigned long long)pt_n); atomicAdd(&lzf_dbg_parse_cycles[5], 1ull); \
-                                                     atomicAdd(&lzf_dbg_parse_cycles[6], (unsigned long long)pt_hops[0]); atomicAdd(&lzf_dbg_parse_cycles[7], (unsigned long long)pt_hops[1]); } } while (0)
+                                                     atomicAdd(&lzf_dbg_parse_cycles[6], (unsigned long long)pt_hops[0]); atomicAdd(&lzf_dbg_parse_cycles[7], (unsigned long long)pt_hops[1]); \
+                                                     atomicAdd(&lzf_dbg_parse_cycles[8], (unsigned long long)pt_memo[0]); atomicAdd(&lzf_dbg_parse_cycles[9], (unsigned long long)pt_memo[1]); } } while (0)
 #else
+#define PT_MEMO(look, hit) do { } while (0)
 #define PT_START() do { } while (0)
 #define PT_MARK(i) do { } while (0)
 #define PT_CHUNK() do { } while (0)
@@ -346,23 +362,60 @@ __global__ __launch_bounds__(64) void lzf_seg_parse_kernel(seg_ctx c) {
         const uint32_t x0 = walk(rb0, in_input, mdummy, M0T{});
         PT_MARK(1);
         uint32_t X = in_input ? x0 : 0u, walked = rb0, mpos = rb0;
+        // the saved walks, newest first: (entry, X, mpos, row B) of results a new entry displaced.  Empty at the start of every chunk — a
+        // slot of the chunk before with the same chunk-relative entry would bring back a row of other bytes.  `fresh`: the live result is
+        // pass 0's, which is not worth a slot (the region start merges on its first hop).
+        uint32_t sv_e[kParseMemo], sv_X[kParseMemo], sv_m[kParseMemo], sv_row[kParseMemo][8];
+#pragma unroll
+        for (uint32_t k = 0; k < kParseMemo; ++k) {
+            sv_e[k] = kNoEntry; sv_X[k] = 0u; sv_m[k] = 0u;
+#pragma unroll
+            for (uint32_t i = 0; i < 8u; ++i) sv_row[k][i] = 0u;
+        }
+        bool fresh = true;
         for (uint32_t pass = 0; pass < 80u; ++pass) {
             const uint32_t entry = wave_prev(wave_scan_max(X), 0u);
             const bool redo = in_input && entry != walked && lane != 0u;
             if (!__any(redo)) break;
-            const bool inreg = redo && entry < end_r && cstart + entry < len;
-            if (redo) {
-                walked = entry;
+            // ---- the lookup, for all lanes alike (selects, no branch): the live row is read whole, the saved walk of this entry (or an
+            //      empty row) takes its place, and the live result goes to the first slot — the slot that was hit, or the oldest, makes room
+            uint32_t lb[8];
 #pragma unroll
-                for (uint32_t i = 0; i < 8u; ++i) ROWB(i) = 0u;
+            for (uint32_t i = 0; i < 8u; ++i) lb[i] = ROWB(i);
+            bool hit = false, hitk[kParseMemo], below[kParseMemo];
+#pragma unroll
+            for (uint32_t k = 0; k < kParseMemo; ++k) { below[k] = hit; hitk[k] = redo && !hit && entry == sv_e[k]; hit = hit || hitk[k]; }
+            PT_MEMO(redo, hit);
+            uint32_t rX = 0u, rM = 0u, rrow[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+#pragma unroll
+            for (uint32_t k = 0; k < kParseMemo; ++k) {
+                rX = hitk[k] ? sv_X[k] : rX; rM = hitk[k] ? sv_m[k] : rM;
+#pragma unroll
+                for (uint32_t i = 0; i < 8u; ++i) rrow[i] = hitk[k] ? sv_row[k][i] : rrow[i];
             }
+            const bool put = redo && !fresh;
+#pragma unroll
+            for (uint32_t k = kParseMemo - 1u; k > 0u; --k) {
+                const bool sh = put && !below[k];
+                sv_e[k] = sh ? sv_e[k - 1u] : sv_e[k]; sv_X[k] = sh ? sv_X[k - 1u] : sv_X[k]; sv_m[k] = sh ? sv_m[k - 1u] : sv_m[k];
+#pragma unroll
+                for (uint32_t i = 0; i < 8u; ++i) sv_row[k][i] = sh ? sv_row[k - 1u][i] : sv_row[k][i];
+            }
+            sv_e[0] = put ? walked : sv_e[0]; sv_X[0] = put ? X : sv_X[0]; sv_m[0] = put ? mpos : sv_m[0];
+#pragma unroll
+            for (uint32_t i = 0; i < 8u; ++i) { sv_row[0][i] = put ? lb[i] : sv_row[0][i]; ROWB(i) = redo ? rrow[i] : lb[i]; }
+            walked = redo ? entry : walked;
+            fresh = fresh && !redo;
+            // ---- a lane that found its entry sits the walk out, as one whose entry lies beyond its region does
+            const bool wk = redo && !hit;
+            const bool inreg = wk && entry < end_r && cstart + entry < len;
             bool mg = false;
             const uint32_t x1 = walk(inreg ? entry : end_r, inreg, mg, M1T{});
-            if (redo) {
+            if (wk) {
                 if (!inreg) { X = entry; mpos = end_r; }
                 else if (mg) { X = x0; mpos = x1; }
                 else { X = x1; mpos = end_r; }
-            }
+            } else if (hit) { X = rX; mpos = rM; }
         }
         PT_MARK(2);
         // ---- the rows and the exit
@@ -406,6 +459,7 @@ __global__ __launch_bounds__(64) void lzf_seg_parse_kernel(seg_ctx c) {
 #undef PT_CHUNK
 #undef PT_HOP_ASM
 #undef PT_HOPS
+#undef PT_MEMO
 #undef PT_REPORT
 
 // =====================================================================================================================
@@ -539,10 +593,10 @@ __global__ __launch_bounds__(64) void lzf_seg_seam_kernel(seg_ctx c) {
 }  // namespace lzf
 
 #ifdef LZF_DBG_PARSE_TIME
-// Analysis only: the section sums and counts of lzf_seg_parse_kernel since the last call with `reset` (out8 may be NULL).
-extern "C" int lzf_debug_parse_timers(unsigned long long* out8, int reset) {
-    if (out8 && hipMemcpyFromSymbol(out8, HIP_SYMBOL(lzf::lzf_dbg_parse_cycles), sizeof(unsigned long long) * 8u) != hipSuccess) return LZF_E_HIP;
-    const unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+// Analysis only: the section sums and counts of lzf_seg_parse_kernel since the last call with `reset` (out10 may be NULL).
+extern "C" int lzf_debug_parse_timers(unsigned long long* out10, int reset) {
+    if (out10 && hipMemcpyFromSymbol(out10, HIP_SYMBOL(lzf::lzf_dbg_parse_cycles), sizeof(unsigned long long) * 10u) != hipSuccess) return LZF_E_HIP;
+    const unsigned long long z[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     if (reset && hipMemcpyToSymbol(HIP_SYMBOL(lzf::lzf_dbg_parse_cycles), z, sizeof(z)) != hipSuccess) return LZF_E_HIP;
     return LZF_OK;
 }

@@ -23,7 +23,7 @@ dj['out'] = d_dec.data_ptr() + np.arange(m, dtype=np.uint64) * BS; dj['out_cap']
 d_dj = device.to_device(dj, 'cuda'); d_res2 = torch.zeros(m * 16, dtype=torch.uint8, device='cuda')
 fn = ffi.lib().lzf_debug_parse_timers
 fn.argtypes = [C.POINTER(C.c_uint64), C.c_int]
-t = (C.c_uint64 * 8)()
+t = (C.c_uint64 * 10)()
 device.decompress_batch(d_dj, d_res2, m); torch.cuda.synchronize()          # warm-up
 assert fn(None, 1) == 0
 ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
@@ -44,3 +44,5 @@ print(f"  {'sum':20s} {sec.sum() / chunks:9.0f}")
 print("hops of the wave in the plain-hop loop, per chunk, and cycles of the section per hop:")
 for name, v, hops in (("pass 0 (mode 0)", sec[1], int(t[6])), ("fixed-point passes (mode 1)", sec[2], int(t[7]))):
     print(f"  {name:28s} {hops / chunks:8.1f} hops  {v / max(hops, 1):7.1f} cycles per hop")
+# the saved walks of the fixed point: a lookup is a lane whose entry changed; a hit takes a displaced walk back instead of walking (tools/parse_memo_model.c)
+print(f"lookups of the saved walks per chunk {int(t[8]) / chunks:8.1f}, of which hit {int(t[9]) / chunks:8.1f}  ({100.0 * int(t[9]) / max(int(t[8]), 1):.1f} %)")
