@@ -79,6 +79,14 @@ pub const LZF_FBLOCK_LINKED: u32 = 4;                  // linked-block frame: ne
 pub const LZF_FBLOCK_DELIVERED: u32 = 8;               // the reader delivers this block: no stop at it or before it
 pub const LZF_FBLOCK_BEHIND_STOP: u32 = 16;            // an earlier block stopped the frame; out_off = the frame's out_len
 
+/// The streaming XXH32 state of the host (lzf_xxh32_reset / _update / _digest) and, unchanged, of the device
+/// (lzf_xxh32_update_batch / lzf_xxh32_digest_batch), 48 bytes.
+#[repr(C)] #[derive(Default, Clone, Copy)]
+pub struct lzf_xxh32_state { pub v: [u32; 4], pub buf: [u8; 16], pub fill: u32, pub seed: u32, pub total: u64 }
+pub const LZF_RESUME_MORE: u32 = 0;                    // stopped in front of a block whose bound does not fit what is left of out_cap
+pub const LZF_RESUME_NEED_INPUT: u32 = 1;              // in[0, in_len) ends inside the header, the next block or the content checksum
+pub const LZF_RESUME_DONE: u32 = 2;                    // terminal and sticky: EndMark read and content checksum verified, the empty-block stop, or an error status
+
 #[repr(C)]
 #[derive(Default, Clone, Copy)]
 pub struct lzf_chain_state { pub length: u64, pub dead: u32, pub reserved: u32 }
@@ -172,6 +180,16 @@ extern "C" {
     pub fn lzf_frame_head_device(n_frames: u32, d_in: *const *const u8, in_len: *const usize, d_dict: *const u8, dict_len: usize,
                                  d_out: *const *mut u8, target: *const usize, d_out_len: *mut u64, d_status: *mut i32,
                                  hip_stream: *mut c_void) -> c_int;
+    // resumable XXH32 on device states, and the resumable decode of frames in device memory: a cursor per frame (all zero = the
+    // start of a frame) that carries the linked-block window and the content hash from call to call
+    pub fn lzf_xxh32_update_batch(d_states: *mut lzf_xxh32_state, d_ptrs: *const *const u8, d_lens: *const u64, n: u32,
+                                  hip_stream: *mut c_void) -> c_int;
+    pub fn lzf_xxh32_digest_batch(d_states: *const lzf_xxh32_state, d_out: *mut u32, n: u32, hip_stream: *mut c_void) -> c_int;
+    pub fn lzf_frame_cursor_bytes() -> usize;
+    pub fn lzf_frame_resume_device(n_frames: u32, d_in: *const *const u8, in_len: *const usize, d_dict: *const u8, dict_len: usize,
+                                   d_cursors: *mut c_void, d_out: *const *mut u8, out_cap: *const usize,
+                                   d_out_len: *mut u64, d_consumed: *mut u64, d_status: *mut i32, d_phase: *mut u32,
+                                   hip_stream: *mut c_void) -> c_int;
     // streams of back-to-back frames in device memory (one contiguous output per stream; the pieces of an input packed back to back)
     pub fn lzf_frame_stream_bound_device(n_streams: u32, d_in: *const *const u8, in_len: *const usize, out_bound: *mut usize,
                                          hip_stream: *mut c_void) -> c_int;

@@ -164,7 +164,8 @@ void lzf_frame_release_scratch(void);
 void lzf_frame_set_host_threads(uint32_t n);
 /* Device memory one pass of lzf_frame_decompress_many / lzf_frame_compress_many may use (0 = half of what is free): more frames
  * than fit are processed in several passes; a frame that does not fit alone gets status LZF_E_NO_MEMORY (decompress) or is a
- * pass of its own (compress). */
+ * pass of its own (compress).  A frame in device memory that is over the budget decodes piece by piece through
+ * lzf_frame_resume_device, whose scratch follows the room the caller gives, not the frame. */
 void lzf_frame_set_memory_budget(size_t bytes);
 /* Pinned host memory the staging may hold (0 = default: 2 GiB; at least two 4 MiB slots).  A pass that moves more than this
  * recycles the slab as a ring of 4 MiB slots — a slot is reused when the DMA that last read it has finished — so the pinned
@@ -173,8 +174,8 @@ void lzf_frame_set_pinned_limit(size_t bytes);
 
 /* XXH32 on the host (header / content checksums; twox-hash XxHash32 in the reference). */
 uint32_t lzf_xxh32(const uint8_t* p, size_t len, uint32_t seed);
-/* Streaming form (the content hasher of a block-by-block reader, src/framed/decompress.rs:89,276-278). */
-typedef struct lzf_xxh32_state { uint32_t v[4]; uint8_t buf[16]; uint32_t fill; uint32_t seed; uint64_t total; } lzf_xxh32_state;
+/* Streaming form (the content hasher of a block-by-block reader, src/framed/decompress.rs:89,276-278).  lzf_xxh32_state is
+ * declared in lzfear_hip.h: the device's lzf_xxh32_update_batch / lzf_xxh32_digest_batch take the same 48 bytes. */
 void lzf_xxh32_reset(lzf_xxh32_state* st, uint32_t seed);
 void lzf_xxh32_update(lzf_xxh32_state* st, const uint8_t* p, size_t len);
 uint32_t lzf_xxh32_digest(const lzf_xxh32_state* st);
@@ -526,6 +527,76 @@ int lzf_frame_decompress_blocks_device(uint32_t n_runs, const uint8_t* const* d_
                                        const uint8_t* d_dict, size_t dict_len,
                                        uint8_t* const* d_out, const size_t* out_cap,
                                        uint64_t* d_out_len, int32_t* d_status, void* hip_stream);
+
+/* ---- resumable decode of frames in device memory: the device counterpart of lzf_frame_reader -----------------------------
+ * LZ4FrameReader::decode_block hands out one block at a time and into_read pulls a frame of any length through a fixed buffer
+ * (src/framed/decompress.rs:198-288).  lzf_frame_resume_device is that reader for frames in device memory: a cursor per frame
+ * that the caller comes back to.  One call decodes as many whole blocks as fit the room given, carries the 64 KiB window of a
+ * linked-block frame (:238-269) and the running content hash between calls, verifies the content checksum at the EndMark like
+ * lzf_frame_decompress_device_many, and treats "the input ends here" as COME BACK WITH MORE, not as an error.  So a frame whose
+ * output slots are over the memory budget decodes piece by piece, a frame still arriving can be started, and a linked-block
+ * frame decodes by runs with its content checksum verified.
+ * Conventions of lzf_frame_decompress_device_many: d_in, in_len, d_out, out_cap are HOST arrays of n_frames entries holding
+ * DEVICE addresses; d_out_len, d_consumed, d_status and d_phase are DEVICE arrays written in stream order; one dictionary per
+ * call.  d_cursors: n_frames x lzf_frame_cursor_bytes() bytes of DEVICE memory, 16-byte aligned, cursor f at d_cursors + f x
+ * lzf_frame_cursor_bytes().  A cursor is opaque; all zero = the start of a frame.  It holds the header's fields once parsed, the
+ * input offset of the next unread item, the bytes delivered so far, the sticky status and phase, the content hash's
+ * lzf_xxh32_state and, for linked-block frames, the reader's window: the last <= 64 KiB of (dictionary tail ++ everything
+ * delivered), in two buffers used in turn.  The caller passes the same frame bytes (in_len may have grown), the same dictionary
+ * and the same cursor on every call; d_out and out_cap are free to differ per call, and an output buffer may be reused once its
+ * bytes are consumed.  Cursors of one call must not alias; calls that share a cursor must be ordered by the caller.
+ * The rule of one call, per frame (csrc/lzf_frame_resume_rules.h, one definition for the kernels and the CPU tests):
+ *   1. A cursor in phase LZF_RESUME_DONE delivers nothing: out_len 0, status and consumed as they were; no byte of the frame is read.
+ *   2. A fresh cursor parses the header as LZ4FrameReader::new does.  A header error is DONE with that status and consumed, as
+ *      the whole-frame call reports them; a header cut off by in_len is NEED_INPUT with consumed 0, and the cursor stays fresh.
+ *   3. Blocks are taken in order, the reader's way: the length word (the EndMark ends the frame, step 6; a length above
+ *      block_maxsize is LZF_F_BLOCK_SIZE_OVERFLOW: DONE, consumed behind the word), then the payload and its checksum word, which
+ *      must lie inside in_len: a block that is cut off ends the call with NEED_INPUT in front of its length word.  A whole block
+ *      is taken while its BOUND, compressed ? min(255 x len + 16, block_maxsize) : len (lzf_frame_decompress_bound_device's
+ *      term), fits what is left of out_cap[f]; the first block that does not fit ends the call with LZF_RESUME_MORE in front of
+ *      it.  The piece is the longest such run, decided from length words alone.  No length word behind the first block that
+ *      does not fit or is cut off is read: a call's scan costs what its piece costs.  If the very first block of the call does
+ *      not fit, the call reports LZF_OUT_CAPACITY with phase MORE, out_len 0 and the cursor untouched (consumed as it was): that
+ *      status is not sticky, more room cures it.
+ *   4. The piece's blocks go through the whole-frame call's stages: block checksums, the decode (independent blocks behind the
+ *      dictionary, linked blocks behind the cursor's window and the piece so far, in lock-step), the delivery's stop rules
+ *      (block checksum, codec status, more than block_maxsize bytes, the empty block).  The first stop in block order makes the
+ *      frame DONE with its status and consumed = the end of the stopping block; the bytes of the blocks in front of it are
+ *      delivered, packed, to d_out[f][0, out_len).  Nothing at or beyond d_out[f] + out_len is written.
+ *   5. The delivered bytes update the content hash (lzf_xxh32_update_batch) and, for linked frames, the window.
+ *   6. At the EndMark, with a content checksum in the header, the stored word is compared with the digest:
+ *      LZF_F_FRAME_CHECKSUM_FAIL on a difference (the bytes of the call are delivered all the same).  A checksum word cut off by
+ *      in_len is NEED_INPUT in front of the EndMark.  Then DONE.
+ *   7. d_out_len[f]: the bytes of THIS call.  d_consumed[f]: the input offset the cursor now stands at, counted from the start
+ *      of the frame — the start of the next unread item, which in NEED_INPUT is the start of the incomplete one.  d_status[f]:
+ *      LZF_OK unless a rule above says otherwise.  d_phase[f]: LZF_RESUME_*.
+ * THE CONTRACT: for capacities that are each at least the largest block bound of the frame and an in_len that grows to the full
+ * length, the concatenation of the calls' outputs, the last status and the last consumed are exactly what
+ * lzf_frame_decompress_device_many reports for the full bytes with unlimited capacity.  THE ONE DIFFERENCE: where in_len never
+ * reaches the end of the frame, the frame rests in NEED_INPUT with LZF_OK — the bytes delivered are the whole-frame call's
+ * out_len bytes for the cut input, but LZF_F_INPUT_ERROR is the caller's to report once it knows that no more input comes, and
+ * consumed is the start of the incomplete item, not in_len.
+ * The host waits twice on the stream, as the whole-frame call does: for a 64-byte summary per frame that the bounded walk
+ * (one lane per frame, from the cursor's offset, reading the cursor itself: the host never reads a cursor) writes, and for the
+ * block table of the pieces (24 bytes per block).  It then enqueues block checksums, decode, delivery, the copies, the hash
+ * update, the digest and one kernel per call that moves the cursors and the windows, waits for its own upload of job lists
+ * to leave host memory and returns.  Scratch comes from the stream-ordered pool and follows out_cap and the piece's input,
+ * never the frame: the call never reports LZF_E_NO_MEMORY.  Pieces over the memory budget go through in passes; a piece over
+ * it alone is a pass of its own.  No global state, no host-driver lock except to read the budget.  Not graph-capturable.
+ * Every call pays the two waits, so small pieces are slow: tools/frame_resume_bench.py measures pieces against the whole-frame
+ * call (profiles/frame_resume.txt).  Returns LZF_OK or a negative LZF_E_*. */
+#define LZF_RESUME_MORE        0u  /* stopped in front of a block whose bound does not fit what is left of out_cap */
+#define LZF_RESUME_NEED_INPUT  1u  /* in[0, in_len) ends inside the header, the next block (its checksum word included),
+                                      or the content checksum: nothing of that item was consumed */
+#define LZF_RESUME_DONE        2u  /* terminal: EndMark read and content checksum verified, the empty-block stop, or an
+                                      error status; sticky */
+size_t lzf_frame_cursor_bytes(void);         /* device bytes per cursor, a multiple of 256; all zero = start of a frame */
+int lzf_frame_resume_device(uint32_t n_frames, const uint8_t* const* d_in, const size_t* in_len,
+                            const uint8_t* d_dict, size_t dict_len,
+                            void* d_cursors,                      /* n_frames x lzf_frame_cursor_bytes(), DEVICE */
+                            uint8_t* const* d_out, const size_t* out_cap,
+                            uint64_t* d_out_len, uint64_t* d_consumed, int32_t* d_status, uint32_t* d_phase,
+                            void* hip_stream);
 
 /* lzf_frame_compress_stream_device: input s becomes max(1, ceil(in_len[s] / frame_bytes)) frames, written back to back into
  * d_out[s]: the bytes are the concatenation of lzf_frame_compress_many's output for each piece of frame_bytes bytes (the last

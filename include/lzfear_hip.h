@@ -341,6 +341,22 @@ int lzf_chain_decompress_step_trimmed(const lzf_chain_step* d_steps, lzf_chain_s
 int lzf_xxh32_batch(const uint8_t* const* d_ptrs, const uint64_t* d_lens, uint32_t* d_out,
                     uint32_t n, void* hip_stream);
 
+/* Resumable XXH32: the content hasher of a block-by-block reader (src/framed/decompress.rs:89,276-278) for bytes that arrive in
+ * device memory piece by piece.  lzf_xxh32_state is the host's streaming state (lzf_xxh32_reset / _update / _digest of
+ * lzfear_frame.h) and, unchanged, the device layout: 48 bytes — the four accumulators, up to 15 bytes that do not fill a stripe
+ * yet, their count, the seed, the bytes hashed so far.  A state written by lzf_xxh32_reset on the host and uploaded is a valid
+ * start; a state downloaded after any number of device updates gives, through the host's lzf_xxh32_digest, the hash of the
+ * concatenation, and a state the host has updated goes on on the device the same way.
+ * lzf_xxh32_update_batch: d_states[i] takes d_lens[i] bytes at d_ptrs[i] (any alignment; a zero length changes nothing and its
+ *   pointer is not read).  One wavefront per state, lzf_xxh32_batch's stripe loop from the saved accumulators: one serial chain
+ *   per state, at the rate of that call's chain and no faster (profiles/frame_resume.txt).  States must not alias each other.
+ * lzf_xxh32_digest_batch: d_out[i] = the hash of everything d_states[i] has taken; the states are not changed.
+ * d_states, d_ptrs, d_lens, d_out: DEVICE arrays of n entries.  Asynchronous on `hip_stream`, no host wait, no scratch. */
+typedef struct lzf_xxh32_state { uint32_t v[4]; uint8_t buf[16]; uint32_t fill; uint32_t seed; uint64_t total; } lzf_xxh32_state;
+int lzf_xxh32_update_batch(lzf_xxh32_state* d_states, const uint8_t* const* d_ptrs, const uint64_t* d_lens,
+                           uint32_t n, void* hip_stream);
+int lzf_xxh32_digest_batch(const lzf_xxh32_state* d_states, uint32_t* d_out, uint32_t n, void* hip_stream);
+
 /* Stored blocks: copies n device byte ranges (d_src[i] -> d_dst[i], d_len[i] bytes, each at most max_len) in one
  * launch — the raw-block moves of src/framed/compress.rs:250-255 and src/framed/decompress.rs:250 without going
  * through the host.  Ranges must not overlap each other. */

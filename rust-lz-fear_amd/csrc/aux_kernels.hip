@@ -55,16 +55,10 @@ __global__ __launch_bounds__(64) void lzf_xxh32_kernel(const uint8_t* const* __r
 // step with coalesced 16-byte loads, two steps ahead, multiplies by PRIME2 in all 64 lanes at once and parks the products in
 // LDS; lanes 0..3 then run the serial chain (add, rotate, multiply — ~30 cycles a stripe, ~1.3 GB/s per hash) on LDS reads
 // that do not depend on the chain.  The chip runs thousands of such chains at once.
-__global__ __launch_bounds__(64) void lzf_xxh32_wave_kernel(const uint8_t* const* __restrict__ ptrs,
-                                                            const uint64_t* __restrict__ lens,
-                                                            uint32_t* __restrict__ out, uint32_t n) {
-    __shared__ __attribute__((aligned(16))) uint32_t buf[2][256];
-    const uint32_t g = blockIdx.x;
-    if (g >= n) return;
-    const uint32_t lane = threadIdx.x, q = lane & 3u;
-    cgu8* p = as_global(ptrs[g]);
-    const uint64_t len = lens[g];
-    uint32_t v = q == 0 ? XP1 + XP2 : q == 1 ? XP2 : q == 2 ? 0u : 0u - XP1;
+// xxh32_wave_stripes is that stripe loop over the whole stripes of p[0, len), from the accumulator v of lane & 3 to the one
+// behind them: lzf_xxh32_wave_kernel starts it from the seed, lzf_xxh32_update_kernel from a saved state.
+__device__ __forceinline__ uint32_t xxh32_wave_stripes(cgu8* p, uint64_t len, uint32_t v, uint32_t (*buf)[256], uint32_t lane) {
+    const uint32_t q = lane & 3u;
     const uint64_t chunks = len >> 10;
     const u32x4 zero = {0u, 0u, 0u, 0u};
     u32x4 r0 = chunks > 0 ? ld16(p + lane * 16u) : zero;
@@ -81,6 +75,20 @@ __global__ __launch_bounds__(64) void lzf_xxh32_wave_kernel(const uint8_t* const
     const uint64_t stripes = len >> 4;
     cgu8* sp = p + q * 4u;
     for (uint64_t s = chunks << 6; s < stripes; ++s) v = xround(v, ld4(sp + s * 16));
+    return v;
+}
+
+__global__ __launch_bounds__(64) void lzf_xxh32_wave_kernel(const uint8_t* const* __restrict__ ptrs,
+                                                            const uint64_t* __restrict__ lens,
+                                                            uint32_t* __restrict__ out, uint32_t n) {
+    __shared__ __attribute__((aligned(16))) uint32_t buf[2][256];
+    const uint32_t g = blockIdx.x;
+    if (g >= n) return;
+    const uint32_t lane = threadIdx.x, q = lane & 3u;
+    cgu8* p = as_global(ptrs[g]);
+    const uint64_t len = lens[g];
+    const uint64_t stripes = len >> 4;
+    const uint32_t v = xxh32_wave_stripes(p, len, q == 0 ? XP1 + XP2 : q == 1 ? XP2 : q == 2 ? 0u : 0u - XP1, buf, lane);
     const uint32_t r = q == 0 ? rotl32(v, 1) : q == 1 ? rotl32(v, 7) : q == 2 ? rotl32(v, 12) : rotl32(v, 18);
     uint32_t h = r + __shfl_xor(r, 1);
     h = h + __shfl_xor(h, 2);
@@ -94,6 +102,59 @@ __global__ __launch_bounds__(64) void lzf_xxh32_wave_kernel(const uint8_t* const
         h ^= h >> 15; h *= XP2; h ^= h >> 13; h *= XP3; h ^= h >> 16;
         out[g] = h;
     }
+}
+
+// Resumable XXH32 (lzfear_hip.h: lzf_xxh32_update_batch / lzf_xxh32_digest_batch): the host's streaming hasher (frame.cpp: Xxh32::update /
+// ::digest) on its own 48-byte state.  Update: one wavefront per state.  The bytes that did not fill a stripe last time are topped
+// up to one through LDS (every branch below is on values that are the same in all 64 lanes: the state's fill and the length);
+// the whole stripes behind them are xxh32_wave_stripes from the saved accumulators; what is left, fewer than 16 bytes, is parked
+// in the state.  A zero length leaves the state untouched and reads no pointer.
+__global__ __launch_bounds__(64) void lzf_xxh32_update_kernel(lzf_xxh32_state* __restrict__ states, const uint8_t* const* __restrict__ ptrs,
+                                                              const uint64_t* __restrict__ lens, uint32_t n) {
+    __shared__ __attribute__((aligned(16))) uint32_t buf[2][256];
+    __shared__ __attribute__((aligned(16))) uint8_t pend[16];
+    const uint32_t g = blockIdx.x;
+    if (g >= n) return;
+    uint64_t len = lens[g];
+    if (len == 0) return;
+    const uint32_t lane = threadIdx.x, q = lane & 3u;
+    lzf_xxh32_state* const S = states + g;
+    cgu8* p = as_global(ptrs[g]);
+    const uint32_t fill = (uint32_t)__builtin_amdgcn_readfirstlane((int)S->fill) & 15u;
+    const uint64_t total = S->total + len;
+    uint32_t v = S->v[q];
+    if (fill) {
+        const uint32_t take = len < 16u - fill ? (uint32_t)len : 16u - fill;
+        if (fill + take < 16u) {                        // still no whole stripe: the bytes join the pending ones
+            if (lane < take) S->buf[fill + lane] = p[lane];
+            if (lane == 0) { S->fill = fill + take; S->total = total; }
+            return;
+        }
+        if (lane < 16u) pend[lane] = lane < fill ? S->buf[lane] : p[lane - fill];
+        __syncthreads();
+        v = xround(v, reinterpret_cast<const uint32_t*>(pend)[q]);
+        p += take; len -= take;
+    }
+    v = xxh32_wave_stripes(p, len, v, buf, lane);
+    const uint32_t rem = (uint32_t)(len & 15u);
+    cgu8* t = p + (len & ~15ull);
+    if (lane < rem) S->buf[lane] = t[lane];
+    if (lane < 4u) S->v[lane] = v;
+    if (lane == 0) { S->fill = rem; S->total = total; }
+}
+// Digest: one thread per state (Xxh32::digest).
+__global__ __launch_bounds__(256) void lzf_xxh32_digest_kernel(const lzf_xxh32_state* __restrict__ states, uint32_t* __restrict__ out, uint32_t n) {
+    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+    if (g >= n) return;
+    const lzf_xxh32_state* const s = states + g;       // (read in place: a private copy would index its buf at run time, in scratch)
+    uint32_t h = s->total >= 16 ? rotl32(s->v[0], 1) + rotl32(s->v[1], 7) + rotl32(s->v[2], 12) + rotl32(s->v[3], 18) : s->seed + XP5;
+    h += (uint32_t)s->total;
+    cgu8* t = as_global(s->buf);
+    uint32_t rem = s->fill & 15u;
+    while (rem >= 4) { h = rotl32(h + ld4(t) * XP3, 17) * XP4; t += 4; rem -= 4; }
+    while (rem) { h = rotl32(h + (uint32_t)(*t) * XP5, 11) * XP1; ++t; --rem; }
+    h ^= h >> 15; h *= XP2; h ^= h >> 13; h *= XP3; h ^= h >> 16;
+    out[g] = h;
 }
 
 // ---------------------------------------------------------------------------------------

@@ -496,4 +496,23 @@ int lzf_xxh32_batch(const uint8_t* const* d_ptrs, const uint64_t* d_lens, uint32
     return LZF_OK;
 }
 
+// Resumable XXH32 on saved states: one wavefront per state for the update, one thread per state for the digest.
+int lzf_xxh32_update_batch(lzf_xxh32_state* d_states, const uint8_t* const* d_ptrs, const uint64_t* d_lens, uint32_t n, void* hip_stream) {
+    if (n == 0) return LZF_OK;
+    if (!d_states || !d_ptrs || !d_lens) { g_last_error = "lzf_xxh32_update_batch: NULL argument"; return LZF_E_INVALID; }
+    int rc = ensure_device();
+    if (rc < 0) return rc;
+    LAUNCH(lzf::lzf_xxh32_update_kernel, dim3(n), dim3(64), 0, static_cast<hipStream_t>(hip_stream), d_states, d_ptrs, d_lens, n);
+    return LZF_OK;
+}
+
+int lzf_xxh32_digest_batch(const lzf_xxh32_state* d_states, uint32_t* d_out, uint32_t n, void* hip_stream) {
+    if (n == 0) return LZF_OK;
+    if (!d_states || !d_out) { g_last_error = "lzf_xxh32_digest_batch: NULL argument"; return LZF_E_INVALID; }
+    int rc = ensure_device();
+    if (rc < 0) return rc;
+    LAUNCH(lzf::lzf_xxh32_digest_kernel, dim3((n + 255u) / 256u), dim3(256), 0, static_cast<hipStream_t>(hip_stream), d_states, d_out, n);
+    return LZF_OK;
+}
+
 }  // extern "C"

@@ -11,6 +11,9 @@
 //                              the fold: lzf_frame_verify_device
 //   frame_device_head.hip      one wavefront per frame, the frame walk and the block's head walk together, nothing read back:
 //                              lzf_frame_head_device
+//   frame_device_resume.hip    a cursor per frame in device memory, the bounded walk from it (lzf_frame_resume_rules.h), the pieces'
+//                              blocks through enqueue_blocks and the delivery body, the hash update and the kernel that moves the
+//                              cursors: lzf_frame_resume_device, lzf_frame_cursor_bytes
 //   frame_device_compress.hip  plan_cpass / compress_frames / compress_streams and the assembly kernels: lzf_frame_compress_device_many,
 //                              lzf_frame_compressed_size_device, lzf_frame_compress_stream_device, lzf_frame_compress_stream_size_device,
 //                              lzf_frame_compress_stream_bound
@@ -195,6 +198,11 @@ struct Pass {
     size_t s_res = 0, s_state = 0, s_sums = 0, s_rsrc = 0, s_rdst = 0, s_rlen = 0, s_lsrc = 0, s_ldst = 0, s_llen = 0, s_hlen = 0, s_hcheck = 0, s_hout = 0;
     std::vector<lzf_frame_jobs::Frame*> frames() { std::vector<lzf_frame_jobs::Frame*> l; for (auto& J : jf) l.push_back(&J); return l; }
 };
+// The block checksums (lzf_xxh32_batch) and the decode steps (the chain step, then lzf_decompress_batch_sized; with sizes_only their
+// twins that carry lengths in the place of bytes) of a planned pass, enqueued.  Reads of P: plan, n_sums, i_jobs, i_steps, i_sptr,
+// i_slen, s_res, s_state, s_sums.  The whole-frame decode, the size query and the resumable decode (frame_device_resume.hip) run
+// their blocks through it.
+int enqueue_blocks(const Pass& P, const Meta& meta, bool sizes_only, hipStream_t st);
 // The size query of n frames (lzf_frame_decompressed_size_device's body, and the per-frame half of the stream size query): the
 // decode call's scan (two waits), its plan with sizes_only (plan_frames, plan_pass: jobs' lengths and descriptors, no addresses),
 // block checksums (they decide where delivery stops), lzf_decompressed_size_batch for the decode (linked frames in lock-step,

@@ -263,24 +263,6 @@ struct StreamCtx {
     int32_t* s_status; uint64_t* s_out_len; uint64_t* s_consumed; uint64_t* s_n_frames;    // device, per stream
 };
 
-// The block checksums and the decode steps of a planned pass, enqueued: the decode itself, or with sizes_only its twin that
-// carries lengths in the place of bytes (lzf_decompressed_size_batch, and lzf_chain_size_step_kernel between the steps).
-int enqueue_blocks(const Pass& P, const Meta& meta, bool sizes_only, hipStream_t st) {
-    lzf_decompress_job* const d_jobs = meta.img<lzf_decompress_job>(P.i_jobs);
-    lzf_job_result* const d_res = meta.scr<lzf_job_result>(P.s_res);
-    const lzf_frame_jobs::Plan& pl = P.plan;
-    if (P.n_sums) RC_TRY(lzf_xxh32_batch(meta.img<const uint8_t* const>(P.i_sptr), meta.img<const uint64_t>(P.i_slen), meta.scr<uint32_t>(P.s_sums), P.n_sums, st));
-    for (size_t k = 0; k < pl.n_steps; ++k) {
-        const lzf_chain_step* const steps = meta.img<const lzf_chain_step>(P.i_steps) + k * pl.n_chain;
-        lzf_chain_state* const state = meta.scr<lzf_chain_state>(P.s_state);
-        if (pl.n_chain && sizes_only) KERNEL(lzf_chain_size_step_kernel, dim3(pl.n_chain), dim3(256), 0, st, steps, state, pl.n_chain, d_jobs, (const lzf_job_result*)d_res);
-        else if (pl.n_chain) RC_TRY(lzf_chain_decompress_step_trimmed(steps, state, pl.n_chain, d_jobs, d_res, st));
-        const size_t a = pl.step_off[k], c = pl.step_off[k + 1] - a;
-        if (c) RC_TRY((sizes_only ? lzf_decompressed_size_batch : lzf_decompress_batch_sized)(d_jobs + a, d_res + a, (uint32_t)c, lzf_frame_jobs::step_max_input(pl, k), st));
-    }
-    return LZF_OK;
-}
-
 // lzf_frame_decompress_device_many's work for n >= 1 frames on a usable device; with `sx` the frames are placed behind each
 // other in their streams' outputs on the device (count-only delivery, lzf_stream_place_kernel) and folded into per-stream
 // results at the end (lzf_stream_fold_kernel).
@@ -368,6 +350,24 @@ int decode_frames(const uint32_t n, const uint8_t* const* d_in, const size_t* in
 }  // namespace
 
 namespace lzf_fdev __attribute__((visibility("hidden"))) {
+
+// The block checksums and the decode steps of a planned pass, enqueued: the decode itself, or with sizes_only its twin that
+// carries lengths in the place of bytes (lzf_decompressed_size_batch, and lzf_chain_size_step_kernel between the steps).
+int enqueue_blocks(const Pass& P, const Meta& meta, bool sizes_only, hipStream_t st) {
+    lzf_decompress_job* const d_jobs = meta.img<lzf_decompress_job>(P.i_jobs);
+    lzf_job_result* const d_res = meta.scr<lzf_job_result>(P.s_res);
+    const lzf_frame_jobs::Plan& pl = P.plan;
+    if (P.n_sums) RC_TRY(lzf_xxh32_batch(meta.img<const uint8_t* const>(P.i_sptr), meta.img<const uint64_t>(P.i_slen), meta.scr<uint32_t>(P.s_sums), P.n_sums, st));
+    for (size_t k = 0; k < pl.n_steps; ++k) {
+        const lzf_chain_step* const steps = meta.img<const lzf_chain_step>(P.i_steps) + k * pl.n_chain;
+        lzf_chain_state* const state = meta.scr<lzf_chain_state>(P.s_state);
+        if (pl.n_chain && sizes_only) KERNEL(lzf_chain_size_step_kernel, dim3(pl.n_chain), dim3(256), 0, st, steps, state, pl.n_chain, d_jobs, (const lzf_job_result*)d_res);
+        else if (pl.n_chain) RC_TRY(lzf_chain_decompress_step_trimmed(steps, state, pl.n_chain, d_jobs, d_res, st));
+        const size_t a = pl.step_off[k], c = pl.step_off[k + 1] - a;
+        if (c) RC_TRY((sizes_only ? lzf_decompressed_size_batch : lzf_decompress_batch_sized)(d_jobs + a, d_res + a, (uint32_t)c, lzf_frame_jobs::step_max_input(pl, k), st));
+    }
+    return LZF_OK;
+}
 
 int size_frames(uint32_t n, const uint8_t* const* d_in, const size_t* in_len, size_t dict_len, uint64_t* d_out_len, uint64_t* d_consumed,
                 int32_t* d_status, hipStream_t st, Scan& sc, Meta& meta, Pass& P, const std::function<void(const Scan&)>& more) {

@@ -259,6 +259,9 @@ __global__ void lzf_xxh32_kernel(const uint8_t* const* __restrict__ ptrs, const 
                                  uint32_t* __restrict__ out, uint32_t n);
 __global__ void lzf_xxh32_wave_kernel(const uint8_t* const* __restrict__ ptrs, const uint64_t* __restrict__ lens,
                                       uint32_t* __restrict__ out, uint32_t n);
+__global__ void lzf_xxh32_update_kernel(lzf_xxh32_state* __restrict__ states, const uint8_t* const* __restrict__ ptrs,
+                                        const uint64_t* __restrict__ lens, uint32_t n);
+__global__ void lzf_xxh32_digest_kernel(const lzf_xxh32_state* __restrict__ states, uint32_t* __restrict__ out, uint32_t n);
 __global__ void lzf_copy_ranges_kernel(const uint8_t* const* __restrict__ src, uint8_t* const* __restrict__ dst,
                                        const uint64_t* __restrict__ len, uint32_t n);
 __global__ void lzf_seed_table_kernel(lzf_u32_table* __restrict__ t, const uint8_t* __restrict__ dict, uint64_t dict_len);

@@ -168,6 +168,21 @@ def xxh32_batch(d_ptrs, d_lens, d_out, n, stream=None):
     ffi.check(ffi.lib().lzf_xxh32_batch(d_ptrs.data_ptr(), d_lens.data_ptr(), d_out.data_ptr(), n, _stream_ptr(stream)))
 
 
+XXH32_STATE = np.dtype([("v", "<u4", (4,)), ("buf", "u1", (16,)), ("fill", "<u4"), ("seed", "<u4"), ("total", "<u8")])     # lzf_xxh32_state
+assert XXH32_STATE.itemsize == 48
+
+
+def xxh32_update_batch(d_states, d_ptrs, d_lens, n, stream=None):
+    """lzf_xxh32_update_batch: state i (48 bytes at d_states + 48 i, the host's lzf_xxh32_state) takes d_lens[i] bytes at the device
+    address d_ptrs[i].  d_states: a uint8 CUDA tensor of 48 n bytes; d_ptrs, d_lens: uint64 / int64 CUDA tensors."""
+    ffi.check(ffi.lib().lzf_xxh32_update_batch(d_states.data_ptr(), d_ptrs.data_ptr(), d_lens.data_ptr(), n, _stream_ptr(stream)))
+
+
+def xxh32_digest_batch(d_states, d_out, n, stream=None):
+    """lzf_xxh32_digest_batch: d_out[i] (uint32 as an int32 CUDA tensor) = the hash of everything state i has taken."""
+    ffi.check(ffi.lib().lzf_xxh32_digest_batch(d_states.data_ptr(), d_out.data_ptr(), n, _stream_ptr(stream)))
+
+
 def copy_ranges(d_src_ptrs, d_dst_ptrs, d_lens, n, max_len, stream=None):
     """Stored blocks moved on the device (lzf_copy_ranges); the three arrays are uint64 device tensors."""
     ffi.check(ffi.lib().lzf_copy_ranges(d_src_ptrs.data_ptr(), d_dst_ptrs.data_ptr(), d_lens.data_ptr(), n, max_len, _stream_ptr(stream)))
@@ -330,6 +345,51 @@ def frame_heads(frames, nbytes, dictionary=None, stream=None):
     for t in (heads, lens, statuses):
         t.record_stream(s)
     return heads, lens, statuses
+
+
+def frame_cursor_bytes():
+    """lzf_frame_cursor_bytes: device bytes per cursor of frame_resume."""
+    return int(ffi.lib().lzf_frame_cursor_bytes())
+
+
+def new_frame_cursors(n, device):
+    """n zeroed cursors for frame_resume ([n, lzf_frame_cursor_bytes()] uint8): all zero = the start of a frame."""
+    return torch.zeros((n, frame_cursor_bytes()), dtype=torch.uint8, device=device)
+
+
+def frame_resume(frames, in_lens, cursors, outs, dictionary=None, stream=None):
+    """lzf_frame_resume_device, the raw call: frame f is the first in_lens[f] bytes of frames[f] (None: all of them), decoded from
+    where cursors[f] stands into outs[f] (1-D uint8 CUDA tensors, their lengths are the room of this call), as many whole blocks as
+    fit.  `cursors`: what new_frame_cursors returned, the same rows on every call.  Returns (status int32, out_len int64, consumed
+    int64, phase int32) as CUDA tensors, written in order on `stream`: the bytes of this call, the input offset the cursor now
+    stands at, ffi.RESUME_MORE / RESUME_NEED_INPUT / RESUME_DONE."""
+    n, ptrs, lens = _frame_args(frames)
+    assert len(outs) == n and cursors.dtype == torch.uint8 and cursors.is_cuda and cursors.is_contiguous()
+    assert cursors.numel() == n * frame_cursor_bytes(), "cursors: one row of frame_cursor_bytes() per frame"
+    if in_lens is not None:
+        assert len(in_lens) == n and all(0 <= int(l) <= t.numel() for l, t in zip(in_lens, frames))
+        lens = (C.c_size_t * n)(*[int(l) for l in in_lens])
+    dev = frames[0].device if n else torch.device("cuda", torch.cuda.current_device())
+    status = torch.empty(n, dtype=torch.int32, device=dev)         # (empty: the call writes every entry)
+    out_len = torch.empty(n, dtype=torch.int64, device=dev)
+    consumed = torch.empty(n, dtype=torch.int64, device=dev)
+    phase = torch.empty(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return status, out_len, consumed, phase
+    for t in outs:
+        assert t.dtype == torch.uint8 and t.is_cuda and t.dim() == 1 and t.is_contiguous(), "outs: 1-D contiguous uint8 CUDA tensors"
+    optr = (C.c_void_p * n)(*[t.data_ptr() for t in outs])
+    caps = (C.c_size_t * n)(*[t.numel() for t in outs])
+    dptr, dlen = None, 0
+    if dictionary is not None and dictionary.numel():
+        assert dictionary.dtype == torch.uint8 and dictionary.is_cuda and dictionary.is_contiguous()
+        dptr, dlen = dictionary.data_ptr(), dictionary.numel()
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    for t in (status, out_len, consumed, phase):
+        t.record_stream(s)
+    ffi.check(ffi.lib().lzf_frame_resume_device(n, ptrs, lens, dptr, dlen, cursors.data_ptr(), optr, caps, out_len.data_ptr(), consumed.data_ptr(),
+                                                status.data_ptr(), phase.data_ptr(), s.cuda_stream))
+    return status, out_len, consumed, phase
 
 
 def frame_compress_many(settings, frames, outs, dictionary=None, stream=None, caps=None):

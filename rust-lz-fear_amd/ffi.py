@@ -71,6 +71,7 @@ EXPORTS = [
     "lzf_decompress_batch", "lzf_decompress_batch_sized", "lzf_decompressed_size_batch", "lzf_decompressed_size_batch_host", "lzf_decompress_verify_batch", "lzf_decompress_verify_batch_host", "lzf_last_verify_launch", "lzf_decompress_head_batch", "lzf_decompress_head_batch_host", "lzf_last_decompress_launch", "lzf_last_compress_launch", "lzf_last_size_launch", "lzf_table_replace_host", "lzf_table_offset_host", "lzf_compress2_host_writer", "lzf_table_seed_from_dictionary", "lzf_table_offset", "lzf_table_offset_batch",
     "lzf_chain_decompress_step", "lzf_chain_decompress_step_trimmed", "lzf_history_trim_batch", "lzf_history_restore_batch",
     "lzf_xxh32_batch", "lzf_copy_ranges", "lzf_compress_batch_host", "lzf_decompress_batch_host", "lzf_xxh32_batch_host",
+    "lzf_xxh32_update_batch", "lzf_xxh32_digest_batch",
 ]
 FRAME_EXPORTS = [
     "lzf_settings_default", "lzf_frame_compress_bound", "lzf_frame_compress", "lzf_frame_read_header",
@@ -85,7 +86,9 @@ FRAME_EXPORTS = [
     "lzf_frame_stream_bound_device", "lzf_frame_decompress_stream_device", "lzf_frame_compress_stream_bound", "lzf_frame_compress_stream_device",
     "lzf_frame_stream_count_device", "lzf_frame_stream_decompressed_size_device", "lzf_stream_index_locate",
     "lzf_frame_block_count_device", "lzf_frame_block_index_device", "lzf_block_index_locate", "lzf_frame_decompress_blocks_device",
+    "lzf_frame_cursor_bytes", "lzf_frame_resume_device",
 ]
+RESUME_MORE, RESUME_NEED_INPUT, RESUME_DONE = 0, 1, 2       # LZF_RESUME_*: the phase lzf_frame_resume_device reports
 
 
 class StreamFrame(C.Structure):
@@ -250,6 +253,14 @@ def lib():
         L.lzf_frame_decompress_blocks_device.argtypes = [C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p),
                                                          C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p),
                                                          C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(L, "lzf_frame_resume_device"):           # (tools/frame_resume_bench.py loads the parent commit's library, which has no resumable calls, for its baseline)
+            L.lzf_xxh32_update_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+            L.lzf_xxh32_digest_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+            L.lzf_frame_cursor_bytes.restype = C.c_size_t
+            L.lzf_frame_cursor_bytes.argtypes = []
+            L.lzf_frame_resume_device.argtypes = [C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t, C.c_void_p,
+                                                  C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p]
         _lib = L
     return _lib
 

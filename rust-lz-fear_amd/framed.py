@@ -606,6 +606,62 @@ def read_frame_range_device(frame_tensor, index, start, stop, dictionary=None, s
     return out[start - base:stop - base]
 
 
+class FrameCursorDevice:
+    """LZ4FrameReader for a frame in device memory (a 1-D uint8 CUDA tensor), decoded on the device piece by piece
+    (lzf_frame_resume_device): a cursor the caller comes back to.  `read_into(out)` decodes as many whole blocks as fit `out`
+    and says where it stopped; the 64 KiB window of a linked-block frame and the content hash are carried on the device, the
+    content checksum is verified at the EndMark.  The frame tensor may still be filling: pass the bytes that are there as
+    `in_len`, and a frame that ends inside an item reports ffi.RESUME_NEED_INPUT — come back with more.  `dictionary`: bytes or a
+    uint8 CUDA tensor, the same for every call."""
+
+    def __init__(self, frame_tensor, dictionary=None):
+        import torch
+        from . import device
+        self.frame = frame_tensor
+        dev = frame_tensor.device
+        if dictionary is not None and not isinstance(dictionary, torch.Tensor):
+            dictionary = torch.frombuffer(bytearray(bytes(dictionary)), dtype=torch.uint8).to(dev) if len(dictionary) else None
+        self.dictionary = dictionary
+        self.cursor = device.new_frame_cursors(1, dev)
+        self.phase, self.status, self.consumed = ffi.RESUME_MORE, 0, 0
+
+    @property
+    def finished(self):
+        """The frame is over: the EndMark was read (and the content checksum verified), or it stopped with `status`."""
+        return self.phase == ffi.RESUME_DONE
+
+    def read_into(self, out_tensor, in_len=None, stream=None):
+        """Decode the next whole blocks that fit `out_tensor` (1-D uint8 CUDA) from the first `in_len` bytes of the frame (None:
+        all of them).  Returns (n_bytes, status, phase) once the stream has finished the call: out_tensor[:n_bytes] is the next
+        piece of the content.  status ffi.OUT_CAPACITY with phase RESUME_MORE: not even the next block fits, pass more room."""
+        import torch
+        from . import device
+        s = stream if stream is not None else torch.cuda.current_stream(self.frame.device)
+        with torch.cuda.stream(s):
+            status, out_len, consumed, phase = device.frame_resume([self.frame], None if in_len is None else [in_len], self.cursor, [out_tensor],
+                                                                   dictionary=self.dictionary, stream=s)
+        s.synchronize()
+        self.status, self.phase, self.consumed = int(status.cpu()[0]), int(phase.cpu()[0]), int(consumed.cpu()[0])
+        return int(out_len.cpu()[0]), self.status, self.phase
+
+
+def iter_frame_pieces_device(frame_tensor, piece_bytes, dictionary=None):
+    """The content of one frame in device memory, piece by piece through ONE buffer of `piece_bytes` bytes: yields views of that
+    buffer (valid until the next step), each the next whole blocks that fit.  piece_bytes must hold the frame's largest block
+    bound (block_maxsize always does).  Raises FrameError where the frame fails, the content checksum included, or ends early."""
+    import torch
+    cur = FrameCursorDevice(frame_tensor, dictionary=dictionary)
+    buf = torch.empty(int(piece_bytes), dtype=torch.uint8, device=frame_tensor.device)
+    while not cur.finished:
+        n, status, phase = cur.read_into(buf)
+        if status != 0:
+            raise FrameError(status)
+        if phase == ffi.RESUME_NEED_INPUT:
+            raise FrameError(16)                # InputError: the frame ends inside an item, and no more input comes
+        if n:
+            yield buf[:n]
+
+
 class FrameBlockReader:
     """The C ABI's block-by-block reader (lzf_frame_reader_*, include/lzfear_frame.h) over a frame in memory:
     `LZ4FrameReader::new` + `decode_block` (src/framed/decompress.rs:102-161,198-282), one call = one block."""
