@@ -86,6 +86,10 @@ pub struct lzf_xxh32_state { pub v: [u32; 4], pub buf: [u8; 16], pub fill: u32, 
 pub const LZF_RESUME_MORE: u32 = 0;                    // stopped in front of a block whose bound does not fit what is left of out_cap
 pub const LZF_RESUME_NEED_INPUT: u32 = 1;              // in[0, in_len) ends inside the header, the next block or the content checksum
 pub const LZF_RESUME_DONE: u32 = 2;                    // terminal and sticky: EndMark read and content checksum verified, the empty-block stop, or an error status
+pub const LZF_APPEND_MORE: u32 = 0;                    // stopped in front of a block whose bound does not fit what is left of out_cap
+pub const LZF_APPEND_NEED_INPUT: u32 = 1;              // what is left of the offer is less than one block and FINISH is not set
+pub const LZF_APPEND_DONE: u32 = 2;                    // EndMark (and content checksum) written, or an error status; sticky
+pub const LZF_APPEND_FINISH: u32 = 1;                  // flags[f]: the offer ends the stream
 
 #[repr(C)]
 #[derive(Default, Clone, Copy)]
@@ -189,6 +193,13 @@ extern "C" {
     pub fn lzf_frame_resume_device(n_frames: u32, d_in: *const *const u8, in_len: *const usize, d_dict: *const u8, dict_len: usize,
                                    d_cursors: *mut c_void, d_out: *const *mut u8, out_cap: *const usize,
                                    d_out_len: *mut u64, d_consumed: *mut u64, d_status: *mut i32, d_phase: *mut u32,
+                                   hip_stream: *mut c_void) -> c_int;
+    // the streaming frame writer for inputs in device memory: a write cursor per frame (lzf_frame_wcursor_bytes() zeroed device bytes =
+    // nothing written yet) that carries the header flag, the stream's table, the last 64 KiB taken and the content hash from call to call
+    pub fn lzf_frame_wcursor_bytes() -> usize;
+    pub fn lzf_frame_append_device(s: *const lzf_settings, n_frames: u32, d_in: *const *const u8, in_len: *const usize, flags: *const u32,
+                                   d_dict: *const u8, dict_len: usize, d_cursors: *mut c_void, d_out: *const *mut u8, out_cap: *const usize,
+                                   d_out_len: *mut u64, d_taken: *mut u64, d_status: *mut i32, d_phase: *mut u32,
                                    hip_stream: *mut c_void) -> c_int;
     // streams of back-to-back frames in device memory (one contiguous output per stream; the pieces of an input packed back to back)
     pub fn lzf_frame_stream_bound_device(n_streams: u32, d_in: *const *const u8, in_len: *const usize, out_bound: *mut usize,

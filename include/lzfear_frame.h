@@ -598,6 +598,73 @@ int lzf_frame_resume_device(uint32_t n_frames, const uint8_t* const* d_in, const
                             uint64_t* d_out_len, uint64_t* d_consumed, int32_t* d_status, uint32_t* d_phase,
                             void* hip_stream);
 
+/* ---- streaming frame writer in device memory ---------------------------------------------------------------------------------
+ * The reference's compressor is incremental by construction: compress_internal (src/framed/compress.rs:221-276) reads
+ * block_size bytes per turn and carries the table and the last 64 KiB.  lzf_frame_append_device is that writer for inputs in
+ * device memory: a write cursor per frame that the caller comes back to with the next bytes of the stream.  A frame longer than
+ * the memory the caller can spare for input plus bound, a frame whose bytes appear on the device over time and a linked-block
+ * frame fed by runs are written this way; lzf_frame_resume_device reads them back the same way.
+ * Conventions of lzf_frame_compress_device_many: d_in, in_len, flags, d_out, out_cap are HOST arrays of n_frames entries (device
+ * addresses at any alignment); d_out_len, d_taken, d_status, d_phase are DEVICE arrays of n_frames entries, written in stream
+ * order.  s->dictionary must be NULL (LZF_E_INVALID); one `s` and one dictionary per call, and the caller passes the same ones on
+ * every call of a cursor.  d_cursors: n_frames x lzf_frame_wcursor_bytes() bytes of DEVICE memory, 16-byte aligned, cursor f at
+ * d_cursors + f x lzf_frame_wcursor_bytes().  A cursor is opaque; all zero = nothing written yet.  It holds whether the header is
+ * out, the bytes taken so far, the sticky status and phase, the content hash's lzf_xxh32_state and, for linked-block frames, the
+ * stream's lzf_u32_table and the writer's window: the last 64 KiB of what was taken.  Cursors of one call must not alias; calls
+ * that share a cursor are ordered by the caller; d_in[f] of one call may be reused once that call's work is done in stream order.
+ * The rule of one call, per frame (csrc/lzf_frame_append_rules.h, one definition for the kernels, the host and the CPU tests):
+ *   1. A cursor in phase LZF_APPEND_DONE writes nothing: out_len 0, taken 0, status as it was.
+ *   2. A bad block size makes the frame DONE with LZF_F_INVALID_BLOCK_SIZE / LZF_F_PANIC, as in the whole call.
+ *   3. What is taken is decided from host arguments alone.  With bs = s->block_size the offer d_in[f][0, in_len[f]) is cut as
+ *      the reference cuts it: whole blocks of bs from its start, plus a shorter last block only under LZF_APPEND_FINISH.  The call
+ *      takes the longest run of these blocks whose bytes t satisfy lzf_frame_compress_bound(s, t) <= out_cap[f] (the bound always
+ *      counts header, EndMark and checksum words: slightly conservative for a cursor whose header is out).  d_taken[f] = t.
+ *   4. If not even the first block fits — or, under FINISH with nothing to take, out_cap[f] < lzf_frame_compress_bound(s, 0) —
+ *      the call reports LZF_OUT_CAPACITY with phase MORE and taken 0; the cursor is untouched and the status is not sticky.
+ *   5. If fewer than bs bytes are offered without FINISH, nothing is taken or written, the cursor is untouched and the phase is
+ *      NEED_INPUT: the caller offers those bytes again together with what follows them.
+ *   6. A cursor whose header is not out writes the header first (:163-200; content size from `s`).  Every taken block then goes
+ *      through the whole call's stages: independent blocks each behind the dictionary and the read-only template table; linked
+ *      blocks in lock-step over the frames of the call, block 0 of a call behind the whole dictionary on a fresh cursor and
+ *      behind the cursor's window otherwise, later blocks behind the caller's input, the stream's table (seeded from the template
+ *      on a fresh cursor) carried by the cursor with table.offset(forget) (:271-275) applied between blocks and across the call
+ *      boundary.  Per block: the length word (stored on LZF_OUTPUT_FULL), the payload, the optional block checksum.
+ *   7. A block status other than LZF_OK / LZF_OUTPUT_FULL makes the frame DONE with the first such status in block order; no
+ *      byte of this call is written for that frame, out_len and taken are 0.
+ *   8. The taken bytes update the content hash; for linked frames the window becomes the last 64 KiB of the taken bytes.
+ *   9. If FINISH is set and the whole offer was taken, the call writes the EndMark and, with a content checksum, the digest; DONE.
+ *  10. Otherwise the phase is MORE if a block was left for lack of room, NEED_INPUT if only a part-block or nothing is left.
+ *  11. Everything is packed into d_out[f][0, out_len); nothing at or beyond d_out[f] + out_len is written.
+ * THE CONTRACT: for any cut of an input into offers (untaken tails offered again), any capacities of at least
+ * lzf_frame_compress_bound(s, bs) and FINISH on the final offer, the concatenation of the calls' outputs is byte for byte the
+ * frame lzf_frame_compress_device_many writes for the concatenated input with the same settings and dictionary, and the sum of
+ * taken is the input's length.
+ * The host plans from in_len, flags, out_cap and `s` alone: it never reads a cursor, reads nothing back, waits only for its own
+ * upload of job lists to leave host memory and never reports LZF_E_NO_MEMORY.  So a DONE cursor costs the compression of its
+ * offer and writes nothing.  Three kernels settle what depends on the cursor: a prepare kernel (block 0's history, job and table
+ * offsets, the table of a fresh cursor), the append form of the assembly kernel (header only when it is not out, EndMark only
+ * when finishing) and a commit kernel that alone moves the cursors and copies the windows.  Scratch comes from the
+ * stream-ordered pool and follows the offer, never the frame; offers over the memory budget go through in passes.  Not
+ * graph-capturable.  Measured on one MI355X (tools/frame_append_bench.py, profiles/frame_append.txt; medians of 5): one call with
+ * FINISH costs the whole call (49 inputs of 20 x 4 MiB blocks 312.5 ms against lzf_frame_compress_device_many's 312.1; one linked input
+ * of 16 x 4 MiB 1614.4 against 1613.5); the linked input in pieces of 1 / 4 blocks 1612.5 / 1614.6 ms; the independent inputs in pieces
+ * of 1 / 4 / 16 blocks 2246.1 / 632.7 / 452.0 ms (few blocks per call leave the device idle: offer many); the 64 MiB linked input under a
+ * 32 MiB budget through one reused 4 MiB input buffer 1614.2 ms with 8.1 MiB of pool scratch at its peak (whole: 1611.7 ms, 68.1 MiB).
+ * Not timed: offers below one block, capacities that leave blocks behind, dictionaries, a producer slower than the writer.
+ * Returns LZF_OK or a negative LZF_E_*. */
+#define LZF_APPEND_MORE        0u  /* stopped in front of a block whose bound does not fit what is left of out_cap */
+#define LZF_APPEND_NEED_INPUT  1u  /* what is left of the offer is less than one block and FINISH is not set */
+#define LZF_APPEND_DONE        2u  /* EndMark (and content checksum) written, or an error status; sticky */
+#define LZF_APPEND_FINISH      1u  /* flags[f]: the offer ends the stream (the reader's short read / EOF, :227-231) */
+size_t lzf_frame_wcursor_bytes(void);        /* device bytes per cursor, a multiple of 256; all zero = nothing written yet */
+int lzf_frame_append_device(const lzf_settings* s, uint32_t n_frames,
+                            const uint8_t* const* d_in, const size_t* in_len, const uint32_t* flags,
+                            const uint8_t* d_dict, size_t dict_len,
+                            void* d_cursors,                      /* n_frames x lzf_frame_wcursor_bytes(), DEVICE */
+                            uint8_t* const* d_out, const size_t* out_cap,
+                            uint64_t* d_out_len, uint64_t* d_taken, int32_t* d_status, uint32_t* d_phase,
+                            void* hip_stream);
+
 /* lzf_frame_compress_stream_device: input s becomes max(1, ceil(in_len[s] / frame_bytes)) frames, written back to back into
  * d_out[s]: the bytes are the concatenation of lzf_frame_compress_many's output for each piece of frame_bytes bytes (the last
  * one shorter) with the same settings and dictionary.  With s->has_content_size every frame's header carries its own piece's

@@ -22,13 +22,13 @@ ANALYSIS_LIB_PATH = os.path.join(PKG_DIR, "liblzfear_hip_analysis.so")
 PRODUCT_HIP = ["capi.hip", "capi_drivers.hip", "lz4_decompress_batched.hip", "lz4_decompress_paired.hip", "lz4_seg_front.hip", "lz4_seg_tiles.hip", "lz4_seg_order.hip", "lz4_seg_resolve.hip",
                "lz4_decompress_fed.hip", "lz4_decoded_size.hip", "lz4_decoded_size_seg.hip", "lz4_verify.hip", "lz4_decode_head.hip", "capi_head.hip", "lz4_compress.hip",
                "lz4_compress_compact.hip", "lz4_compress_team.hip", "aux_kernels.hip",
-               "frame_device_scan.hip", "frame_device_decode.hip", "frame_device_index.hip", "frame_device_verify.hip", "frame_device_head.hip", "frame_device_resume.hip", "frame_device_compress.hip"]
+               "frame_device_scan.hip", "frame_device_decode.hip", "frame_device_index.hip", "frame_device_verify.hip", "frame_device_head.hip", "frame_device_resume.hip", "frame_device_append.hip", "frame_device_compress.hip"]
 ANALYSIS_HIP = ["analysis/lz4_decompress.hip"]
 CXX_SOURCES = ["frame.cpp", "host_staging.cpp", "capi_host.cpp"]
 HEADERS = ["kernels.h", "lzf_device.h", "lz4_decompress_batch_phase.inc", "lz4_decompress_parse_phase.inc", "lz4_decompress_feed_phase.inc", "lzf_seg_common.h",
            "analysis/capi_analysis.inc", "capi_internal.h", "capi_order.h", "lzf_dispatch.h",
            "lzf_copy_helpers.h", "lzf_out_ring.h", "lzf_phase_timers.h", "lzf_parse_helpers.h", "lzf_compress_common.h", "lzf_simt.h", "lz4_compress_team.inc",
-           "host_staging.h", "lzf_frame_scan.h", "lzf_stream_walk.h", "lzf_stream_index.h", "lzf_block_index.h", "frame_jobs.h", "frame_device_common.h", "lzf_frame_layout.h", "lzf_size_rules.h", "lzf_verify_rules.h", "lzf_head_rules.h", "lzf_frame_head_rules.h", "lzf_frame_resume_rules.h", "lz4_decode_head_copies.inc", "lz4_decode_head_walk.inc", "lzf_chain_step.h", "lzf_history_trim.h", "lzf_fed_window.h", "frame_deliver_body.inc",
+           "host_staging.h", "lzf_frame_scan.h", "lzf_stream_walk.h", "lzf_stream_index.h", "lzf_block_index.h", "frame_jobs.h", "frame_device_common.h", "lzf_frame_layout.h", "lzf_size_rules.h", "lzf_verify_rules.h", "lzf_head_rules.h", "lzf_frame_head_rules.h", "lzf_frame_resume_rules.h", "lzf_frame_append_rules.h", "lz4_decode_head_copies.inc", "lz4_decode_head_walk.inc", "lzf_chain_step.h", "lzf_history_trim.h", "lzf_fed_window.h", "frame_deliver_body.inc",
            os.path.join(ROOT, "include", "lzfear_hip.h"), os.path.join(ROOT, "include", "lzfear_frame.h")]
 
 

@@ -14,6 +14,9 @@
 //   frame_device_resume.hip    a cursor per frame in device memory, the bounded walk from it (lzf_frame_resume_rules.h), the pieces'
 //                              blocks through enqueue_blocks and the delivery body, the hash update and the kernel that moves the
 //                              cursors: lzf_frame_resume_device, lzf_frame_cursor_bytes
+//   frame_device_append.hip    a write cursor per frame in device memory (lzf_frame_append_rules.h): the offer's blocks through the
+//                              compress plan and launches, the prepare, append-assembly and commit kernels:
+//                              lzf_frame_append_device, lzf_frame_wcursor_bytes
 //   frame_device_compress.hip  plan_cpass / compress_frames / compress_streams and the assembly kernels: lzf_frame_compress_device_many,
 //                              lzf_frame_compressed_size_device, lzf_frame_compress_stream_device, lzf_frame_compress_stream_size_device,
 //                              lzf_frame_compress_stream_bound
@@ -77,6 +80,14 @@ struct DBlkDesc {
     uint32_t sum_idx;           // block checksum of the pass, kNone: none
     uint32_t want_sum, len;     // len: a stored block's length
 };
+
+// per block of a compress pass, for the assembly kernels (frame_device_compress.hip, frame_device_append.hip)
+struct CBlkDesc {
+    const uint8_t* raw;         // the block in the caller's input: a stored block's payload
+    const uint8_t* slot;        // its job's output: a compressed block's payload
+    uint32_t job, raw_len;      // job of the pass (its result), the block's length
+};
+constexpr uint32_t kBlockSums = 1u, kContentSum = 2u;
 
 // ---- the wave-wide sums of the one-wavefront-per-frame / per-stream kernels
 __device__ inline uint64_t wave_sum(uint64_t v) {
@@ -224,6 +235,10 @@ int empty_streams(uint32_t n_streams, int32_t* d_status, uint64_t* d_out_len, ui
 // lzf_frame_block_index_kernel's launch over the pass size_frames planned (after it has returned): the delivery body in its index
 // mode, frame q of the pass into x_index[frame] (x_cap[frame] entries at most; device arrays of the call's n frames).
 int index_blocks(const Pass& P, const Meta& meta, lzf_frame_block* const* x_index, const uint64_t* x_cap, uint64_t* d_n_listed, hipStream_t st);
+
+// ---- frame_device_compress.hip
+// lzf_frame_patch_kernel's launch: the checksum words d_val[k] at their unaligned places d_at[k] (NULL: skipped), k < n; n == 0: no launch
+int patch_words(uint8_t* const* d_at, const uint32_t* d_val, size_t n, hipStream_t st);
 
 }  // namespace lzf_fdev
 

@@ -29,12 +29,6 @@ struct CFrameDesc {
     uint32_t hdr_idx;           // the frame's header image (streams with a content size: one per piece length), 0: the call's one
 };
 static_assert(sizeof(CFrameDesc) == 32, "compress frame descriptor");
-struct CBlkDesc {
-    const uint8_t* raw;         // the block in the caller's input: a stored block's payload
-    const uint8_t* slot;        // its job's output: a compressed block's payload
-    uint32_t job, raw_len;      // job of the pass (its result), the block's length
-};
-constexpr uint32_t kBlockSums = 1u, kContentSum = 2u;
 
 // compress.rs:221-281 once the blocks are compressed, one frame per wavefront, 64 blocks per round (lzf_frame_layout.h's rule).
 // Round one finds the frame's status: the first block, in block order, whose status is neither LZF_OK nor LZF_OUTPUT_FULL.
@@ -395,7 +389,7 @@ int compress_frames(const lzf_settings* s, const uint32_t n, const uint8_t* cons
         if (P.n_hash)                                           // (on the caller's stream: a forked checksum stream did not pay)
             RC_TRY(lzf_xxh32_batch(meta.img<const uint8_t* const>(P.i_hptr), meta.img<const uint64_t>(P.i_hlen), val + n_sums, P.n_hash, st));
         const size_t n_at = n_sums + P.n_hash;
-        if (n_at) KERNEL(lzf_frame_patch_kernel, dim3((uint32_t)((n_at + 255u) / 256u)), dim3(256), 0, st, (uint8_t* const*)at, (const uint32_t*)val, (uint32_t)n_at);
+        RC_TRY(patch_words(at, val, n_at, st));
     }
     return meta.wait();                                         // the image has left host memory; the launches run on
 }
@@ -432,6 +426,13 @@ int compress_streams(const lzf_settings* s, size_t frame_bytes, uint32_t n_strea
                            per.at<uint64_t>(o_len), per.at<int32_t>(0), st, &cx, false);
 }
 }  // namespace
+
+namespace lzf_fdev {
+int patch_words(uint8_t* const* d_at, const uint32_t* d_val, size_t n, hipStream_t st) {
+    if (n) KERNEL(lzf_frame_patch_kernel, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, st, d_at, d_val, (uint32_t)n);
+    return LZF_OK;
+}
+}  // namespace lzf_fdev
 
 extern "C" {
 

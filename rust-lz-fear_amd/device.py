@@ -392,6 +392,54 @@ def frame_resume(frames, in_lens, cursors, outs, dictionary=None, stream=None):
     return status, out_len, consumed, phase
 
 
+def frame_write_cursor_bytes():
+    """lzf_frame_wcursor_bytes: device bytes per write cursor of frame_append."""
+    return int(ffi.lib().lzf_frame_wcursor_bytes())
+
+
+def new_frame_write_cursors(n, device=None):
+    """n zeroed write cursors for frame_append ([n, lzf_frame_wcursor_bytes()] uint8): all zero = nothing written yet."""
+    device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
+    return torch.zeros((n, frame_write_cursor_bytes()), dtype=torch.uint8, device=device)
+
+
+def frame_append(settings, offers, flags, cursors, outs, dictionary=None, stream=None, in_lens=None, caps=None):
+    """lzf_frame_append_device, the raw call: offers[f] (1-D uint8 CUDA tensors; in_lens[f] bytes of them, default all) are the
+    next bytes of stream f, flags[f] is 0 or ffi.APPEND_FINISH, and what the call takes of them is compressed behind cursors[f]
+    into outs[f] (1-D uint8 CUDA tensors; caps[f], default their lengths, is the room of this call).  `cursors`: what
+    new_frame_write_cursors returned, the same rows on every call, with the same `settings` (an ffi.Settings whose `dictionary`
+    is NULL) and `dictionary` (a uint8 CUDA tensor).  Returns (status int32, out_len int64, taken int64, phase int32) as CUDA
+    tensors, written in order on `stream`; nothing is synchronised and nothing comes back to the host."""
+    n, ptrs, lens = _frame_args(offers)
+    assert len(outs) == n and len(flags) == n and cursors.dtype == torch.uint8 and cursors.is_cuda and cursors.is_contiguous()
+    assert cursors.numel() == n * frame_write_cursor_bytes(), "cursors: one row of frame_write_cursor_bytes() per frame"
+    if in_lens is not None:
+        assert len(in_lens) == n and all(0 <= int(l) <= t.numel() for l, t in zip(in_lens, offers))
+        lens = (C.c_size_t * n)(*[int(l) for l in in_lens])
+    dev = cursors.device
+    status = torch.empty(n, dtype=torch.int32, device=dev)         # (empty: the call writes every entry)
+    out_len = torch.empty(n, dtype=torch.int64, device=dev)
+    taken = torch.empty(n, dtype=torch.int64, device=dev)
+    phase = torch.empty(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return status, out_len, taken, phase
+    for t in outs:
+        assert t.dtype == torch.uint8 and t.is_cuda and t.dim() == 1 and t.is_contiguous(), "outs: 1-D contiguous uint8 CUDA tensors"
+    optr = (C.c_void_p * n)(*[t.data_ptr() for t in outs])
+    caps = (C.c_size_t * n)(*([t.numel() for t in outs] if caps is None else caps))
+    dptr, dlen = None, 0
+    if dictionary is not None and dictionary.numel():
+        assert dictionary.dtype == torch.uint8 and dictionary.is_cuda and dictionary.is_contiguous()
+        dptr, dlen = dictionary.data_ptr(), dictionary.numel()
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    for t in (status, out_len, taken, phase):
+        t.record_stream(s)
+    ffi.check(ffi.lib().lzf_frame_append_device(C.byref(settings), n, ptrs, lens, (C.c_uint32 * n)(*[int(x) for x in flags]), dptr, dlen,
+                                                cursors.data_ptr(), optr, caps, out_len.data_ptr(), taken.data_ptr(), status.data_ptr(),
+                                                phase.data_ptr(), s.cuda_stream))
+    return status, out_len, taken, phase
+
+
 def frame_compress_many(settings, frames, outs, dictionary=None, stream=None, caps=None):
     """lzf_frame_compress_device_many: every input of `frames` (1-D uint8 CUDA tensors) compressed into an LZ4 frame in `outs`
     (1-D uint8 CUDA tensors, their lengths are the capacities) with `settings` (an ffi.Settings whose `dictionary` is NULL; the

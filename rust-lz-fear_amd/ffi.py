@@ -87,8 +87,11 @@ FRAME_EXPORTS = [
     "lzf_frame_stream_count_device", "lzf_frame_stream_decompressed_size_device", "lzf_stream_index_locate",
     "lzf_frame_block_count_device", "lzf_frame_block_index_device", "lzf_block_index_locate", "lzf_frame_decompress_blocks_device",
     "lzf_frame_cursor_bytes", "lzf_frame_resume_device",
+    "lzf_frame_wcursor_bytes", "lzf_frame_append_device",
 ]
 RESUME_MORE, RESUME_NEED_INPUT, RESUME_DONE = 0, 1, 2       # LZF_RESUME_*: the phase lzf_frame_resume_device reports
+APPEND_MORE, APPEND_NEED_INPUT, APPEND_DONE = 0, 1, 2       # LZF_APPEND_*: the phase lzf_frame_append_device reports
+APPEND_FINISH = 1                                           # LZF_APPEND_FINISH: flags[f], the offer ends the stream
 
 
 class StreamFrame(C.Structure):
@@ -261,6 +264,12 @@ def lib():
             L.lzf_frame_resume_device.argtypes = [C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t, C.c_void_p,
                                                   C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                   C.c_void_p]
+        if hasattr(L, "lzf_frame_append_device"):           # (a library of an earlier commit, loaded for a baseline, has no streaming writer)
+            L.lzf_frame_wcursor_bytes.restype = C.c_size_t
+            L.lzf_frame_wcursor_bytes.argtypes = []
+            L.lzf_frame_append_device.argtypes = [C.POINTER(Settings), C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_uint32),
+                                                  C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 

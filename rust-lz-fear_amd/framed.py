@@ -256,6 +256,37 @@ class CompressionSettings:
                     raise FrameError(code)
         return frames
 
+    def compress_pieces_device(self, pieces, content_size=None, stream=None):
+        """ONE frame written piece by piece on the device (lzf_frame_append_device): `pieces` yields 1-D uint8 CUDA tensors, the
+        stream's bytes one after another; every piece is offered to a FrameWriterDevice together with the tail the call before
+        left untaken (less than one block), and the end of `pieces` finishes the frame.  Yields uint8 CUDA tensors, the frame's
+        bytes in order: their concatenation is what `compress_many_device` returns for the concatenated input.  A piece may be
+        reused by the caller once the next item has been yielded.  `content_size` goes into the header as it stands
+        (compress_with_size_unchecked).  Raises FrameError."""
+        import torch
+        w, tail, L = None, None, ffi.lib()
+        for piece in pieces:
+            if w is None:
+                w = FrameWriterDevice(self, content_size=content_size, device=piece.device)
+            offer = piece if tail is None or not tail.numel() else torch.cat([tail, piece])
+            out = torch.empty(L.lzf_frame_compress_bound(C.byref(w.settings), offer.numel()), dtype=torch.uint8, device=piece.device)
+            view, taken, status, _ = w.write(offer, out, stream=stream)
+            if status != 0:
+                raise FrameError(status)
+            tail = offer[taken:].clone()
+            if view.numel():
+                yield view
+        if w is None:
+            w = FrameWriterDevice(self, content_size=content_size)
+        dev = w.cursor.device
+        last = tail if tail is not None else torch.empty(0, dtype=torch.uint8, device=dev)
+        out = torch.empty(L.lzf_frame_compress_bound(C.byref(w.settings), last.numel()), dtype=torch.uint8, device=dev)
+        view, taken, status, phase = w.write(last, out, finish=True, stream=stream)
+        if status != 0:
+            raise FrameError(status)
+        assert taken == last.numel() and phase == ffi.APPEND_DONE
+        yield view
+
     def compress_streams_device(self, tensors, frame_bytes, with_size=False, stream=None, exact=False):
         """Every input of `tensors` (1-D uint8 CUDA tensors) written as a stream of back-to-back frames, one frame per
         `frame_bytes` input bytes (lzf_frame_compress_stream_device): the bytes of `compress_many_device` over the pieces,
@@ -604,6 +635,52 @@ def read_frame_range_device(frame_tensor, index, start, stop, dictionary=None, s
         raise FrameError(st)
     assert int(out_len.item()) == total
     return out[start - base:stop - base]
+
+
+class FrameWriterDevice:
+    """The incremental frame writer for bytes in device memory (lzf_frame_append_device): a write cursor the caller comes back
+    to.  `settings`: a CompressionSettings (its dictionary is used unless `dictionary` — bytes or a uint8 CUDA tensor — is
+    given) or an ffi.Settings without a host dictionary.  The stream's table, the last 64 KiB taken and the content hash are
+    carried on the device; nothing of a call comes back to the host but its four result words."""
+
+    def __init__(self, settings, dictionary=None, content_size=None, device=None):
+        import torch
+        from . import device as dev_mod
+        dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
+        if isinstance(settings, CompressionSettings):
+            if dictionary is None:
+                dictionary = settings._dictionary or None
+            settings = settings._struct(content_size)
+            settings.dictionary = None                      # (the device call takes the dictionary in device memory)
+            settings.dictionary_len = 0
+        if dictionary is not None and not isinstance(dictionary, torch.Tensor):
+            dictionary = torch.frombuffer(bytearray(bytes(dictionary)), dtype=torch.uint8).to(dev) if len(dictionary) else None
+        self.settings, self.dictionary = settings, dictionary
+        self.cursor = dev_mod.new_frame_write_cursors(1, dev)
+        self.phase, self.status, self.taken = ffi.APPEND_MORE, 0, 0
+
+    @property
+    def finished(self):
+        """The frame is over: the EndMark is written, or it stopped with `status`."""
+        return self.phase == ffi.APPEND_DONE
+
+    def write(self, tensor, out, finish=False, stream=None):
+        """Offer `tensor` (1-D uint8 CUDA), the next bytes of the stream; `finish`: they are its last.  Whole blocks of it (under
+        `finish` the shorter last one too) are taken as far as their frame bound fits `out` (1-D uint8 CUDA).  Returns
+        (piece_view, taken, status, phase) once the stream has finished the call: out[:n], the next bytes of the frame; the
+        bytes of `tensor` that were taken — offer tensor[taken:] again in front of what follows; the status (ffi.OUT_CAPACITY with
+        phase APPEND_MORE: not even one block fits, pass more room); ffi.APPEND_MORE / APPEND_NEED_INPUT / APPEND_DONE."""
+        import torch
+        from . import device as dev_mod
+        s = stream if stream is not None else torch.cuda.current_stream(self.cursor.device)
+        with torch.cuda.stream(s):
+            status, out_len, taken, phase = dev_mod.frame_append(self.settings, [tensor], [ffi.APPEND_FINISH if finish else 0], self.cursor, [out],
+                                                                 dictionary=self.dictionary, stream=s)
+        s.synchronize()
+        self.status, self.phase = int(status.cpu()[0]), int(phase.cpu()[0])
+        t = int(taken.cpu()[0])
+        self.taken += t
+        return out[:int(out_len.cpu()[0])], t, self.status, self.phase
 
 
 class FrameCursorDevice:
